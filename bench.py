@@ -28,8 +28,15 @@ survivors.  value = (global rows) x samples x steps / max-over-ranks wall time: 
 same at every N > 1 (strong scaling over 2 / 4 / 8); the line carries the rows of every rank and max / mean.
 
 Printed JSON also carries "roofline" (dominant kernel = chi2_scan_kernel, HBM-bound; achieved =
-algorithmic bytes / mean HIP-event duration of the kernel over the timed steps) and
-"cpu_baseline" (the C oracle's scan on the same rows, one row chunk per host thread, a bounded number of passes).
+algorithmic bytes / mean HIP-event duration of the kernel over the timed steps).  A plain run stops there: set up, warm up,
+time the K steps, write the outputs (--dump-outputs), print the line once.  --full adds the legs after the timed region,
+each re-emitting the line: the kernel's spread over >= 200 more launches, the measured stream-read ceiling, the same scan
+on a 4.3-GB matrix, "cpu_baseline" (the C oracle's scan on the same rows, one row chunk per host thread, a bounded number
+of passes) and the end-to-end `phenotypeseeker modeling` wall-clock.
+
+--dump-outputs DIR writes what the last timed step computed -- the survivors as psk_get_results hands them to a caller,
+ascending by row -- as DIR/<name>.npy in float64 (a fixed, seeded sample of the rows if they would exceed 64 MB; ranks of
+N > 1 write their own slab's, <name>_rank<r>.npy).  The inputs are a function of the arguments alone.
 """
 import argparse
 import json
@@ -93,6 +100,37 @@ def host_cpus():
     if quota is not None:
         n = min(n, max(1, int(quota + 0.999)))
     return max(1, min(n, 512))
+
+
+DUMP_BYTES = 64 << 20     # --dump-outputs: all files of all ranks together
+
+
+def write_outputs(out_dir, res, n_pass, k, budget_bytes=DUMP_BYTES, suffix=""):
+    """--dump-outputs: the survivors of one scan (engine.get_results: ascending by row) as float64 .npy files, one per field
+    the scan fills, plus n_pass.  k-mer words of k <= 26 fit a double exactly; wider ones are written as two 32-bit halves.
+    Rows beyond the byte budget are sampled with a fixed seed (the same rows of the same survivors every run).  Returns the
+    names written."""
+    n = int(n_pass)
+    words = np.asarray(res["word"], dtype=np.uint64)
+    cols = {"row": res["row"], "chi2": res["stat"], "p": res["p"], "n_with": res["n_with"]}
+    if 2 * k <= 53:
+        cols["kmer"] = words
+    else:
+        cols["kmer_hi32"], cols["kmer_lo32"] = words >> np.uint64(32), words & np.uint64(0xFFFFFFFF)
+    cap = max(1, (int(budget_bytes) - 8 - 4096) // (8 * len(cols)))      # (n_pass, and 128-byte .npy headers)
+    keep = None
+    if n > cap:
+        keep = np.sort(np.random.default_rng(20240613).choice(n, cap, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    written = []
+    for name, col in [("n_pass", np.array([n]))] + sorted(cols.items()):
+        a = np.asarray(col)
+        if keep is not None and name != "n_pass":
+            a = a[keep]
+        fn = name + suffix + ".npy"
+        np.save(os.path.join(out_dir, fn), a.astype(np.float64))
+        written.append(fn)
+    return written
 
 
 def _drop_from_page_cache(path):
@@ -308,15 +346,21 @@ def main():
                     help="fasta: count synthetic genomes on the GPU (default, BASELINE cfg 2); "
                          "matrix: device-generated presence matrix of --rows rows (quick runs)")
     ap.add_argument("--rows", type=int, default=1 << 25)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, run the legs as well: kernel spread, stream-read ceiling, the 4.3-GB matrix, "
+                         "CPU baseline, end-to-end modeling (each can be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the survivors of the last timed step as DIR/<name>.npy (float64, at most 64 MB in all)")
     ap.add_argument("--cpu-sample-rows", type=int, default=40_000_000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-e2e", action="store_true",
-                    help="skip the end-to-end `phenotypeseeker modeling` wall-clock (FASTA files -> .pkl) on the same data")
+                    help="--full: skip the end-to-end `phenotypeseeker modeling` wall-clock (FASTA files -> .pkl) on the same data")
     ap.add_argument("--no-hbm-only", action="store_true",
-                    help="skip the beyond-cache block (the same scan over a device-generated 4.3-GB matrix): what tools/make_profiles.sh "
-                         "passes, so that the profiler's average for the headline kernel covers the headline matrix only")
+                    help="--full: skip the beyond-cache block (the same scan over a device-generated 4.3-GB matrix): what "
+                         "tools/make_profiles.sh passes, so that the profiler's average for the headline kernel covers the headline "
+                         "matrix only")
     ap.add_argument("--e2e-cold", action="store_true",
-                    help="drop the FASTA files of the end-to-end leg from the page cache before the run (N = 1)")
+                    help="--full: drop the FASTA files of the end-to-end leg from the page cache before the run (N = 1)")
     ap.add_argument("--share-gpu", action="store_true",
                     help="map ranks onto the visible GPUs modulo their count (tests on a one-GPU box, with the host "
                          "transport named by PSK_DIST_TRANSPORT; RCCL refuses two ranks on one device)")
@@ -324,6 +368,8 @@ def main():
                     help="N = 1 only: run the N > 1 step (scan + export + all-gather) on a one-rank group, to measure "
                          "what the exchange adds per step on one GPU; the line carries \"exchange\": \"forced\"")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # launcher-free: fan out here, before anything of this process has touched the GPU (launch.py imports the
         # standard library only; the children are fresh processes, not an exec of a process that has initialised HIP)
@@ -515,6 +561,11 @@ def main():
         drain(0)   # the last exchange completes inside the timed region
     grp.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        # the last timed scan is the last one ended: its survivors are what get_results hands over
+        phase("outputs of the last timed step")
+        write_outputs(args.dump_outputs, ctx.get_results(npass), npass, k, budget_bytes=DUMP_BYTES // world,
+                      suffix="_rank%d" % rank if sharded else "")
     phase("reductions of the result line")
     elapsed = grp.allreduce_max(elapsed)
     cells_total = grp.allreduce_sum(int(M) * n) * args.steps
@@ -571,14 +622,17 @@ def main():
     line = ResultLine(rank, out)
     watchdog.on_dump(line.on_deadline)       # a launch that runs into its deadline re-emits what there is, with the stuck phase
     legs = out["legs"] = {}
-    todo = ["kernel_spread", "stream_ceiling"] + ([] if args.no_hbm_only else ["hbm_only"])
-    if world == 1 and not args.no_cpu_baseline:
-        todo.append("cpu_baseline")
-    if args.workload == "fasta" and not args.no_e2e:
-        todo.append("e2e")
+    todo = []
+    if args.full:        # a plain run has no legs: its one line, printed at the end, is the record
+        todo = ["kernel_spread", "stream_ceiling"] + ([] if args.no_hbm_only else ["hbm_only"])
+        if world == 1 and not args.no_cpu_baseline:
+            todo.append("cpu_baseline")
+        if args.workload == "fasta" and not args.no_e2e:
+            todo.append("e2e")
     for name_ in todo:
         legs[name_] = "pending"
-    line.emit()
+    if todo:
+        line.emit()
     rf = out["roofline"]
 
     def leg(name_, fn):

@@ -12,7 +12,7 @@ pytestmark = pytest.mark.gpu
 
 
 def test_bench_json_contract():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--full",
                         "--samples", "64", "--length", "200000", "--cpu-sample-rows", "200000"], cwd=ROOT, timeout=600,
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -61,6 +61,48 @@ def test_bench_json_contract():
         assert key in ph["phases_s"], ph
 
 
+def test_plain_bench_is_lean_and_dumps_the_last_steps_survivors(tmp_path, oracle):
+    """Without --full: set up, warm up, the K timed steps, the outputs, ONE line and no legs.  --dump-outputs writes the
+    survivors of the last timed scan; two runs with the same arguments write the same arrays, and they are the C oracle's
+    scan of the same genomes."""
+    import numpy as np
+    from phenotypeseeker_amd.synth import GenomeSet
+    n, length, k = 64, 200000, 13
+    recs, dumps = [], []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                            "--samples", str(n), "--length", str(length), "--kmer", str(k),
+                            "--dump-outputs", str(tmp_path / run)], cwd=ROOT, timeout=600, capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, lines
+        recs.append(json.loads(lines[0]))
+        dumps.append({f[:-4]: np.load(tmp_path / run / f) for f in sorted(os.listdir(tmp_path / run))})
+    d = recs[0]
+    assert d["line"] == "final" and d["legs"] == {} and "cpu_baseline" not in d and "e2e" not in d
+    assert "kernel_ms_launches" not in d["roofline"] and "hbm_only" not in d["roofline"]
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["ms_per_step"] > 0 and d["higher_is_better"] is True
+    cells = d["config"]["rows_per_gpu"] * n
+    assert abs(d["value"] * d["ms_per_step"] * 1e-3 / cells - 1) < 1e-9        # value = cells x steps / (steps x ms_per_step)
+    a, b = dumps
+    assert sorted(a) == ["chi2", "kmer", "n_pass", "n_with", "p", "row"] and sorted(b) == sorted(a)
+    assert all(v.dtype == np.float64 for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert all(np.array_equal(a[key], b[key]) for key in a)
+    assert int(a["n_pass"][0]) == d["config"]["survivors"] == len(a["row"]) > 0
+    # the same scan on the host: counted, united and packed by the oracle, chi2 + Bonferroni over the same union
+    gs = GenomeSet(n, length, seed=12345)
+    lists = [oracle.count_kmers(gs.sample(i)[1], k)[0] for i in range(n)]
+    uw = oracle.union(lists)
+    assert len(uw) == d["config"]["rows_per_gpu"]
+    pheno = [1 if i % 2 == 0 else 0 for i in range(n)]
+    bits = oracle.presence_bits(lists, uw, wpr=d["config"]["words_per_row_stored"])
+    ref = oracle.chi2_scan(bits, pheno, np.ones(n), n, 2, n - 2, 0.05, False, len(uw))
+    keep = np.nonzero(ref["keep"])[0]
+    assert np.array_equal(a["row"], keep.astype(np.float64)) and np.array_equal(a["kmer"], uw[keep].astype(np.float64))
+    assert np.allclose(a["chi2"], ref["stat"][keep], rtol=1e-12) and np.allclose(a["p"], ref["p"][keep], rtol=1e-12, atol=0)
+    assert np.array_equal(a["n_with"], ref["n_with"][keep])
+
+
 def test_bench_two_ranks_run_the_sharded_pipeline():
     """N > 1: ONE dataset, the word space cut at pilot quantiles, every rank its slab (both ingest modes), survivors
     all-gathered; the line carries the rows of every rank, whose sum is the one-rank union.  Two ranks share the one
@@ -80,7 +122,7 @@ def test_bench_two_ranks_run_the_sharded_pipeline():
         env_t = dict(env, MASTER_PORT=str(port)) if transport == "gloo" else {k_: v for k_, v in env.items() if k_ != "PSK_DIST_TRANSPORT"}
         for var in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
             env_t.pop(var, None)
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--ingest", ingest] + size
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--full", "--ingest", ingest] + size
         if transport == "gloo":
             cmd.append("--no-e2e")   # the CLI children of the e2e leg would open a second gloo group on the same port
         r = subprocess.run(cmd, env=env_t, cwd=ROOT, timeout=900, capture_output=True, text=True)
@@ -146,7 +188,7 @@ def test_bench_line_survives_the_death_of_the_e2e_leg():
     import time
     env = {k_: v for k_, v in os.environ.items() if k_ not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "PSK_DIST_TRANSPORT", "PSK_RDZV_DIR",
                                                             "PSK_RDZV_FILE", "PSK_LAUNCH_NONCE")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--samples", "64", "--length", "200000",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--full", "--samples", "64", "--length", "200000",
            "--kmer", "16", "--steps", "4", "--warmup", "1"]
 
     def run(action, launch_timeout):
@@ -250,7 +292,7 @@ def test_bench_under_the_drivers_launcher():
                                                             "PSK_RDZV_FILE", "PSK_LAUNCH_NONCE")}
     launcher = "torch.distributed" + ".run"
     cmd = [sys.executable, "-m", launcher, "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29641",
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--samples", "64", "--length", "200000", "--kmer", "16",
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--full", "--samples", "64", "--length", "200000", "--kmer", "16",
            "--steps", "3", "--warmup", "1", "--no-e2e"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, timeout=900, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]

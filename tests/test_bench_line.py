@@ -42,6 +42,36 @@ def test_result_line_is_emitted_early_and_again_after_every_leg(capsys):
     assert capsys.readouterr().out == ""
 
 
+def test_dumped_outputs_are_float64_within_budget_and_sampled_the_same_way_every_run(tmp_path):
+    import numpy as np
+    n = 5000
+    rng = np.random.default_rng(3)
+    res = {"row": np.sort(rng.choice(1 << 30, n, replace=False)).astype(np.uint64),
+           "word": rng.integers(0, 1 << 62, n, dtype=np.uint64), "stat": rng.random(n) * 40, "p": rng.random(n) * 1e-9,
+           "n_with": rng.integers(2, 60, n).astype(np.int32)}
+    # everything fits: every row, as it came, k = 13 words in one exact float64 array
+    names = bench.write_outputs(str(tmp_path / "all"), res, n, 13)
+    assert sorted(names) == ["chi2.npy", "kmer.npy", "n_pass.npy", "n_with.npy", "p.npy", "row.npy"]
+    got = {f[:-4]: np.load(tmp_path / "all" / f) for f in names}
+    assert all(v.dtype == np.float64 for v in got.values()) and got["n_pass"].tolist() == [n]
+    assert np.array_equal(got["chi2"], res["stat"]) and np.array_equal(got["row"], res["row"].astype(np.float64))
+    # k = 31: the words in two 32-bit halves; over the budget: a fixed sample of the rows, in row order, the same every time
+    budget = 64 * 1024
+    for d in ("s1", "s2"):
+        names = bench.write_outputs(str(tmp_path / d), res, n, 31, budget_bytes=budget, suffix="_rank1")
+    assert sorted(names) == ["chi2_rank1.npy", "kmer_hi32_rank1.npy", "kmer_lo32_rank1.npy", "n_pass_rank1.npy",
+                             "n_with_rank1.npy", "p_rank1.npy", "row_rank1.npy"]
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in names) <= budget
+    s1 = {f: np.load(tmp_path / "s1" / f) for f in names}
+    assert all(np.array_equal(s1[f], np.load(tmp_path / "s2" / f)) for f in names)
+    assert s1["n_pass_rank1.npy"].tolist() == [n] and 0 < len(s1["row_rank1.npy"]) < n
+    rows = s1["row_rank1.npy"]
+    assert np.all(np.diff(rows) > 0) and np.isin(rows, res["row"].astype(np.float64)).all()
+    at = np.searchsorted(res["row"].astype(np.float64), rows)
+    words = (s1["kmer_hi32_rank1.npy"].astype(np.uint64) << np.uint64(32)) | s1["kmer_lo32_rank1.npy"].astype(np.uint64)
+    assert np.array_equal(words, res["word"][at]) and np.array_equal(s1["p_rank1.npy"], res["p"][at])
+
+
 def test_the_watchdog_hook_re_emits_the_line_when_a_rank_is_asked_where_it_is(tmp_path, capsys):
     from phenotypeseeker_amd import watchdog
     old = dict(watchdog._state)

@@ -14,7 +14,7 @@ samples = sys.argv[1] if len(sys.argv) > 1 else "128"
 length = sys.argv[2] if len(sys.argv) > 2 else "300000"
 out_dir = os.path.join(ROOT, "gpurun_out", "r04_phases")
 os.makedirs(out_dir, exist_ok=True)
-size = ["--samples", samples, "--length", length, "--kmer", "16", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"]
+size = ["--full", "--samples", samples, "--length", length, "--kmer", "16", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"]
 runs = []
 for n, ingest in ((1, None), (2, "filter"), (2, "exchange"), (4, "filter"), (4, "exchange"), (8, "filter"), (8, "exchange")):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n)] + size
