@@ -220,6 +220,10 @@ int psk_export_survivors(psk_ctx *ctx, void *device_dst, uint64_t cap_records, u
  * work queued on that stream afterwards -- the RCCL all-gather -- is ordered behind it without a host
  * synchronisation; the next scan that writes the same result set waits on the device for the export to finish. */
 int psk_export_survivors_async(psk_ctx *ctx, void *device_dst, uint64_t cap_records, void *stream);
+/* Whether the current matrix has an exception-coded copy for the unweighted chi2 scan (*encoded = 1; 65..256 samples,
+ * rows mostly within 7 samples of all-absent or all-present), and how many of its rows sit in the side matrix of dense
+ * rows (*overflow_rows).  Measurement and tests only: the scan picks its form by itself (PSK_SCAN_DENSE=1 forces the dense one). */
+int psk_compact_info(const psk_ctx *ctx, int *encoded, uint64_t *overflow_rows);
 /* HIP-event duration of the last scan kernel launch in milliseconds (for bench.py). */
 double psk_last_scan_ms(const psk_ctx *ctx);
 /* Re-launches the last chi2 scan `reps` times back to back on the context's stream and

@@ -3,6 +3,8 @@
 // chi2_scan_kernel   replaces phenotypes.get_kmers_tested / conduct_chi_squared_test and helpers
 //                    (modeling.py:677-714, :759-858)
 // ttest_scan_kernel  replaces conduct_t_test / get_samples_distribution_for_ttest (:716-757)
+// chi2_scan_kernel_cx  the unweighted chi2 scan over the exception-coded copy of the matrix (presence_compact.hip), when
+//                      there is one: same survivors, a third of the bytes at config 2
 //
 // Layout: bits[M][wpr] u64, wpr even, so a row is wpr/2 16-byte chunks.  G = next power of two
 // >= wpr/2 lanes own one row; every lane issues one 16-byte load per row (global_load_dwordx4,
@@ -133,6 +135,16 @@ __device__ __forceinline__ double chi2_exact(double A, double B, double C, doubl
     return stat;
 }
 
+// the division-free pre-test of a unit-weight 2 x 2 table: chi2 = T (AD - BC)^2 / (R1 R0 K1 K0) cannot be ruled out
+// against thr.  Host and device evaluate it in the same IEEE double operations (-ffp-contract=off): the host's candidate
+// table of the exception-coded scan (cx_fill_tables) decides bit for bit what the dense kernel decides.
+__host__ __device__ __forceinline__ bool chi2_pretest(double A, double B, double C, double D, double thr)
+{
+    const double R1 = A + B, R0 = C + D, K1 = A + C, K0 = B + D, T = R1 + R0;
+    const double det = A * D - B * C;
+    const double lhs = T * det * det, rhs = thr * R1 * R0 * K1 * K0;
+    return !(lhs < rhs * (1.0 - 1e-9));  // NaN compares false -> a candidate
+}
 
 // ---- rows -----------------------------------------------------------------------------------------
 // G = 0 stands for "half a lane per row" (8-byte rows, two per 16-byte load)
@@ -569,11 +581,7 @@ __global__ __launch_bounds__(LUT ? SC_LUT_THREADS : SC_THREADS) void chi2_scan_k
                 continue;
             }
             const double A = (double)a, B = (double)(P.n1 - (int)a), C = (double)c, D = (double)(P.n0 - (int)c);
-            // division-free pre-test: chi2 = T (AD - BC)^2 / (R1 R0 K1 K0)
-            const double R1 = A + B, R0 = C + D, K1 = A + C, K0 = B + D, T = R1 + R0;
-            const double det = A * D - B * C;
-            const double lhs = T * det * det, rhs = P.thr * R1 * R0 * K1 * K0;
-            const bool cand = freq_ok && g == 0 && !(lhs < rhs * (1.0 - 1e-9));  // NaN compares false -> a candidate
+            const bool cand = freq_ok && g == 0 && chi2_pretest(A, B, C, D, P.thr);
             if (MODE == 2) {
                 q = queue_rows(cand, row, make_int2((int)a, (int)c), q_row, q_val, q, lane);
                 continue;
@@ -592,6 +600,131 @@ __global__ __launch_bounds__(LUT ? SC_LUT_THREADS : SC_THREADS) void chi2_scan_k
         }
     }
     if (!WEIGHTED) publish_segment(P);   // weighted: chi2w_finalize_kernel publishes
+}
+
+// ---- the unweighted scan over the exception-coded rows (presence_compact.hip) ------------------------------------------
+// One lane per row: a lane's 16-byte load holds two slots, so a wave instruction reads 1 KB.  A slot's header gives e and
+// whether the exceptions are the present or the absent samples; the class table in LDS (1 = case, 0x100 = control, 0 = NA)
+// summed over the e indices gives (a', c'), hence (a, c).  Whether (a, c) is a candidate -- frequency filter and the
+// division-free pre-test -- is one bit of a table the host filled for this scan (cx_fill_tables, the same double
+// operations as chi2_pretest); candidates take chi2_scan_kernel's MODE 0 path (chi2_exact, exp, keep rule), so stat and p
+// are the dense kernel's bits.  The rows with more than CX_MAX_E exceptions are a side matrix of dense rows that the last
+// workgroups of the SAME launch scan as chi2_scan_kernel does (CPR 16-byte chunks per row, one lane each), reporting
+// their original row ids: a second launch would add a kernel boundary to every step.
+constexpr int CX_BM_WORDS = ((CX_MAX_SAMPLES / 2 + 1) * (CX_MAX_SAMPLES / 2 + 1) + 31) / 32;   // (n1 + 1)(n0 + 1) bits, n1 + n0 <= 256
+#ifndef PSK_CX_UNROLL
+#define PSK_CX_UNROLL 4
+#endif
+#ifndef PSK_CX_NT
+#define PSK_CX_NT 0   // plain loads: 57.4 us against 60.7 us with the nontemporal hint at config 2
+#endif
+constexpr int CX_UNROLL = PSK_CX_UNROLL;   // 16-byte loads in flight per lane
+struct CxScanArgs {
+    ScanArgs s;                  // the scan: unit weights, masks inline
+    const u32x4 *slots;          // two slots per 16 bytes
+    const u32x4 *ov;             // overflow rows, dense, cpr chunks each, ascending
+    const uint32_t *ov_row;      // ... their row ids
+    uint64_t n_ov;
+    uint32_t slot_blocks;        // workgroups [0, slot_blocks) stream the slots, the others the overflow rows
+    uint32_t hdr_ok;             // bit (header & 15): a row of that e and base can pass the frequency filter (all set with NA samples)
+    int bm_words;
+    uint32_t bm[CX_BM_WORDS];    // bit a * (n0 + 1) + c: the table (a, c) is a candidate
+};
+// travels in the kernel arguments, like the masks: an unweighted scan uploads nothing
+static_assert(sizeof(CxScanArgs) <= 4096, "the kernel arguments of a launch are limited to 4 KB");
+
+template <int CPR>
+__global__ __launch_bounds__(SC_THREADS) void chi2_scan_kernel_cx(const CxScanArgs X)
+{
+    static_assert(SC_THREADS == CX_MAX_SAMPLES, "the class table is filled one sample per thread");
+    const ScanArgs &P = X.s;
+    __shared__ uint16_t s_cls[CX_MAX_SAMPLES];
+    __shared__ uint32_t s_bm[CX_BM_WORDS];
+    {
+        const int t = threadIdx.x;
+        const uint64_t b = 1ull << (t & 63);
+        s_cls[t] = (P.m1_inl[t >> 6] & b) ? 1 : (P.m0_inl[t >> 6] & b) ? 0x100 : 0;
+        for (int i = t; i < X.bm_words; i += SC_THREADS) s_bm[i] = X.bm[i];
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int n0p = P.n0 + 1;
+    auto candidate = [&](int a, int c) -> bool { const int bit = a * n0p + c; return (s_bm[bit >> 5] >> (bit & 31)) & 1u; };
+    auto evaluate = [&](uint64_t row, int a, int c) {   // chi2_scan_kernel MODE 0
+        const double A = (double)a, B = (double)(P.n1 - a), C = (double)c, D = (double)(P.n0 - c);
+        const double stat = chi2_exact(A, B, C, D);
+        const double p = exp(-0.5 * stat);
+        const bool keep = (P.omit_B && p < P.pcut) || (p < P.pcut_bonf);
+        if (keep) {
+            const uint64_t idx = reserve_slot(P);
+            P.res_row[idx] = row;
+            P.res_stat[idx] = stat;
+            P.res_p[idx] = p;
+            P.res_nw[idx] = a + c;
+        }
+    };
+    if (blockIdx.x < X.slot_blocks) {
+        const uint64_t n_pairs = (P.M + 1) / 2;   // the buffer holds whole pairs; an odd last row's partner is not a row
+        const uint64_t wave = (uint64_t)blockIdx.x * (SC_THREADS / 64) + (threadIdx.x >> 6);
+        const uint64_t stride = (uint64_t)X.slot_blocks * (SC_THREADS / 64) * 64 * CX_UNROLL;
+        for (uint64_t p0 = wave * 64 * CX_UNROLL; p0 < n_pairs; p0 += stride) {
+            u32x4 x[CX_UNROLL];
+#pragma unroll
+            for (int u = 0; u < CX_UNROLL; u++) {
+                const uint64_t pi = p0 + u * 64 + lane;
+                x[u] = pi < n_pairs ? (PSK_CX_NT ? __builtin_nontemporal_load(&X.slots[pi]) : X.slots[pi]) : (u32x4)(0u);
+            }
+#pragma unroll
+            for (int u = 0; u < CX_UNROLL; u++)
+#pragma unroll
+                for (int sub = 0; sub < 2; sub++) {
+                    const uint64_t row = 2 * (p0 + u * 64 + lane) + sub;
+                    const uint32_t lo = sub ? x[u].z : x[u].x, hi = sub ? x[u].w : x[u].y;
+                    const uint32_t h = lo & 0xffu;
+                    if (row >= P.M || (h & CX_HDR_OVF) || !((X.hdr_ok >> (h & 15u)) & 1u)) continue;
+                    const uint32_t e = h & 7u;
+                    uint32_t sum = 0;
+                    if (e > 0) sum += s_cls[(lo >> 8) & 0xffu];
+                    if (e > 1) sum += s_cls[(lo >> 16) & 0xffu];
+                    if (e > 2) sum += s_cls[lo >> 24];
+                    if (e > 3) sum += s_cls[hi & 0xffu];
+                    if (e > 4) sum += s_cls[(hi >> 8) & 0xffu];
+                    if (e > 5) sum += s_cls[(hi >> 16) & 0xffu];
+                    if (e > 6) sum += s_cls[hi >> 24];
+                    int a = (int)(sum & 0xffu), c = (int)(sum >> 8);
+                    if (h & CX_HDR_BASE) { a = P.n1 - a; c = P.n0 - c; }
+                    if (candidate(a, c)) evaluate(row, a, c);
+                }
+        }
+    } else {
+        constexpr int RPW = 64 / CPR;   // rows per wave step
+        const int g = lane & (CPR - 1);
+        const uint64_t m1a = P.m1_inl[2 * g], m1b = P.m1_inl[2 * g + 1], m0a = P.m0_inl[2 * g], m0b = P.m0_inl[2 * g + 1];
+        const uint64_t wave = (uint64_t)(blockIdx.x - X.slot_blocks) * (SC_THREADS / 64) + (threadIdx.x >> 6);
+        const uint64_t total_waves = (uint64_t)(gridDim.x - X.slot_blocks) * (SC_THREADS / 64);
+        const uint64_t n_steps = (X.n_ov + RPW - 1) / RPW;
+        for (uint64_t s0 = wave * CX_UNROLL; s0 < n_steps; s0 += total_waves * CX_UNROLL) {
+            u32x4 x[CX_UNROLL];
+#pragma unroll
+            for (int u = 0; u < CX_UNROLL; u++) {
+                const uint64_t r = (s0 + u) * RPW + lane / CPR;
+                x[u] = r < X.n_ov ? (PSK_CX_NT ? __builtin_nontemporal_load(&X.ov[r * CPR + g]) : X.ov[r * CPR + g]) : (u32x4)(0u);
+            }
+#pragma unroll
+            for (int u = 0; u < CX_UNROLL; u++) {
+                const uint64_t r = (s0 + u) * RPW + lane / CPR;
+                const uint64_t xa = ((uint64_t)x[u].y << 32) | x[u].x, xb = ((uint64_t)x[u].w << 32) | x[u].z;
+                uint32_t a = __popcll(xa & m1a) + __popcll(xb & m1b);
+                uint32_t c = __popcll(xa & m0a) + __popcll(xb & m0b);
+                if (CPR == 2) {
+                    a += __shfl_xor(a, 1, 64);
+                    c += __shfl_xor(c, 1, 64);
+                }
+                if (r < X.n_ov && g == 0 && candidate((int)a, (int)c)) evaluate(X.ov_row[r], (int)a, (int)c);
+            }
+        }
+    }
+    publish_segment(P);
 }
 
 // Second pass of the weighted chi2 scan: one workgroup per result segment, one candidate per lane.  The 2 x 2 table is
@@ -1151,14 +1284,11 @@ int group_lanes(const ScanArgs &a)
 
 // result arrays (SoA) inside ctx->res: row u64 | stat f64 | p f64 | mx f64 | my f64 | nw i32, each
 // SC_NSEG * seg_cap entries; seg_cap bounds the rows the blocks of one segment can visit
-int setup_results(psk_ctx *ctx, ScanArgs &a, dim3 grid, int G, int unroll, int set, int threads = SC_THREADS)
+// (rows_per_block: the most rows one workgroup of the launch visits)
+int setup_results_rows(psk_ctx *ctx, ScanArgs &a, dim3 grid, uint64_t rows_per_block, int set)
 {
-    const uint64_t rpw = sc_rpw(G);
-    const uint64_t n_steps = (a.M + rpw - 1) / rpw;
-    const uint64_t total_waves = (uint64_t)grid.x * (threads / 64);
-    const uint64_t iters = (n_steps + total_waves * unroll - 1) / (total_waves * unroll);
     const uint64_t blocks_per_seg = ((uint64_t)grid.x + SC_NSEG - 1) / SC_NSEG;
-    uint64_t seg_cap = blocks_per_seg * (threads / 64) * iters * unroll * rpw;
+    uint64_t seg_cap = blocks_per_seg * rows_per_block;
     if (seg_cap < 64) seg_cap = 64;
     if (seg_cap >= (1ull << 32)) return psk_fail(ctx, PSK_ERANGE, "result segment too large");
     const uint64_t cap = seg_cap * SC_NSEG;
@@ -1185,6 +1315,15 @@ int setup_results(psk_ctx *ctx, ScanArgs &a, dim3 grid, int G, int unroll, int s
     ctx->slot[set].seg_cap = seg_cap;
     if (set == ctx->res_set) ctx->results_valid = false;  // the last ended scan's results are about to go
     return PSK_OK;
+}
+
+int setup_results(psk_ctx *ctx, ScanArgs &a, dim3 grid, int G, int unroll, int set, int threads = SC_THREADS)
+{
+    const uint64_t rpw = sc_rpw(G);
+    const uint64_t n_steps = (a.M + rpw - 1) / rpw;
+    const uint64_t total_waves = (uint64_t)grid.x * (threads / 64);
+    const uint64_t iters = (n_steps + total_waves * unroll - 1) / (total_waves * unroll);
+    return setup_results_rows(ctx, a, grid, (threads / 64) * iters * unroll * rpw, set);
 }
 
 // per-segment counts of the scan that wrote result set `set`, as its kernels left them in pinned host memory (after
@@ -1266,14 +1405,91 @@ int pick_result_set(psk_ctx *ctx, int *set_out, bool keep_results = false)
     return PSK_OK;
 }
 
-int run_chi2(psk_ctx *ctx, ScanArgs &a, bool weighted, int reps, double *ms_total, double *ms_each = nullptr)
+// ---- exception-coded path: launch shape and the per-scan tables ----
+// Workgroups of the two parts in proportion to their bytes, under scan_grid's cap; slot_blocks = the first part's.
+dim3 cx_grid(const psk_ctx *ctx, uint64_t M, uint64_t n_ov, int cpr, uint32_t *slot_blocks)
 {
-    const int G = group_lanes(a);
-    const dim3 grid = scan_grid(ctx, a.M, G, SC_UNROLL, a.lut != nullptr || a.lut6 != nullptr);
+    const uint64_t wpb = SC_THREADS / 64;
+    const uint64_t n_pairs = (M + 1) / 2, ov_rpw = 64 / cpr;
+    uint64_t bs = ((n_pairs + 64 * CX_UNROLL - 1) / (64 * CX_UNROLL) + wpb - 1) / wpb;
+    uint64_t bo = (((n_ov + ov_rpw - 1) / ov_rpw + CX_UNROLL - 1) / CX_UNROLL + wpb - 1) / wpb;
+    static const int mult = [] { const char *e = getenv("PSK_GRID_MULT"); const int v = e ? atoi(e) : 0; return v > 0 ? v : PSK_SC_GRID_MULT; }();
+    const uint64_t cap = (uint64_t)(ctx->n_cu > 0 ? ctx->n_cu : 256) * mult;
+    if (bs + bo > cap) {
+        const double slot_bytes = 16.0 * n_pairs, ov_bytes = 16.0 * cpr * n_ov;
+        const uint64_t s = (uint64_t)(cap * slot_bytes / (slot_bytes + ov_bytes) + 0.5);
+        bs = std::min(bs, std::max<uint64_t>(s, 1));
+        bo = std::min(bo, cap - bs);
+        if (n_ov && bo == 0) { bo = 1; bs = std::max<uint64_t>(bs - 1, 1); }
+    }
+    if (bs + bo < SC_NSEG) bs = SC_NSEG - bo;   // every result segment needs a workgroup to publish its count
+    *slot_blocks = (uint32_t)bs;
+    return dim3((unsigned)(bs + bo));
+}
+
+// the most rows one workgroup of chi2_scan_kernel_cx visits
+uint64_t cx_rows_per_block(const CxScanArgs &x, dim3 grid, int cpr)
+{
+    const uint64_t wpb = SC_THREADS / 64;
+    const uint64_t n_pairs = (x.s.M + 1) / 2, ov_rpw = 64 / cpr;
+    const uint64_t ws = (uint64_t)x.slot_blocks * wpb, wo = (uint64_t)(grid.x - x.slot_blocks) * wpb;
+    const uint64_t cs = (n_pairs + 64 - 1) / 64, co = (x.n_ov + ov_rpw - 1) / ov_rpw;   // wave steps
+    const uint64_t rs = ws ? (cs + ws * CX_UNROLL - 1) / (ws * CX_UNROLL) * wpb * CX_UNROLL * 128 : 0;
+    const uint64_t ro = wo ? (co + wo * CX_UNROLL - 1) / (wo * CX_UNROLL) * wpb * CX_UNROLL * ov_rpw : 0;
+    return std::max(rs, ro);
+}
+
+// The candidate table over (a, c) -- chi2_scan_kernel's frequency filter and chi2_pretest, in the same double
+// operations -- and the headers that can pass the frequency filter at all (no NA: a + c = the row's popcount).
+void cx_fill_tables(CxScanArgs &x, int n_samples)
+{
+    const ScanArgs &a = x.s;
+    memset(x.bm, 0, sizeof(x.bm));
+    const int n0p = a.n0 + 1;
+    for (int ai = 0; ai <= a.n1; ai++)
+        for (int ci = 0; ci <= a.n0; ci++) {
+            const int n_w = ai + ci, n_wo = (a.n1 - ai) + (a.n0 - ci);
+            const bool freq_ok = !(n_w < a.min_samples || n_wo < 2 || n_w > a.max_samples);
+            const double A = (double)ai, B = (double)(a.n1 - ai), C = (double)ci, D = (double)(a.n0 - ci);
+            if (freq_ok && chi2_pretest(A, B, C, D, a.thr)) {
+                const int bit = ai * n0p + ci;
+                x.bm[bit >> 5] |= 1u << (bit & 31);
+            }
+        }
+    x.bm_words = ((a.n1 + 1) * n0p + 31) / 32;
+    x.hdr_ok = 0;
+    for (int h = 0; h < 16; h++) {
+        const int e = h & 7, pc = (h & (int)CX_HDR_BASE) ? n_samples - e : e;
+        const bool ok = a.n1 + a.n0 != n_samples || !(pc < a.min_samples || n_samples - pc < 2 || pc > a.max_samples);
+        if (ok) x.hdr_ok |= 1u << h;
+    }
+}
+
+// One chi2 scan as the host launches it: the dense kernels' arguments, and the exception-coded path when it runs
+struct Chi2Launch {
+    CxScanArgs x;      // x.s: every form's arguments; the rest: chi2_scan_kernel_cx's
+    bool compact = false;
+    int cpr = 0;
+    dim3 grid;
+};
+
+void launch_chi2_any(psk_ctx *ctx, const Chi2Launch &L)
+{
+    const ScanArgs &a = L.x.s;
+    if (L.compact) {
+        if (L.cpr == 1) chi2_scan_kernel_cx<1><<<L.grid, SC_THREADS, 0, ctx->stream>>>(L.x);
+        else chi2_scan_kernel_cx<2><<<L.grid, SC_THREADS, 0, ctx->stream>>>(L.x);
+        return;
+    }
+    launch_chi2(pick_chi2_mode(ctx, ctx->last.weighted, a.pcut, a.pcut_bonf, a.omit_B), group_lanes(a), L.grid, ctx->stream, a);
+}
+
+int run_chi2(psk_ctx *ctx, const Chi2Launch &L, int reps, double *ms_total, double *ms_each = nullptr)
+{
     *ms_total = 0;
     for (int r = 0; r < reps; r++) {
         PSK_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-        launch_chi2(pick_chi2_mode(ctx, weighted, a.pcut, a.pcut_bonf, a.omit_B), G, grid, ctx->stream, a);
+        launch_chi2_any(ctx, L);
         PSK_HIP(ctx, hipGetLastError());
         PSK_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
         PSK_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the kernel has written the counts to pinned memory
@@ -1287,10 +1503,13 @@ int run_chi2(psk_ctx *ctx, ScanArgs &a, bool weighted, int reps, double *ms_tota
 
 }  // namespace
 
-static int fill_chi2_args(psk_ctx *ctx, ScanArgs &a, int set)
+// The arguments of the last chi2 scan (ctx->last) for result set `set`.  Unit weights on a matrix with an exception-coded
+// copy run chi2_scan_kernel_cx over it, unless PSK_SCAN_DENSE=1 (read per call: A/B runs and tests in one build).
+static int fill_chi2_args(psk_ctx *ctx, Chi2Launch &CL, int set)
 {
     const ScanParams &L = ctx->last;
-    a = ScanArgs();
+    CL.x.s = ScanArgs();
+    ScanArgs &a = CL.x.s;
     a.bits = reinterpret_cast<const u32x4 *>(ctx->bits.p);
     a.M = ctx->n_kmers;
     const int mw = mask_words(ctx);
@@ -1320,9 +1539,23 @@ static int fill_chi2_args(psk_ctx *ctx, ScanArgs &a, int set)
         a.e0 = lut6_gamma(a.cpr) * L.W1 + 1e-36;
         a.e1 = lut6_gamma(a.cpr) * L.W0 + 1e-36;
     }
+    a.n1 = L.n1; a.n0 = L.n0;
+    const char *dense_env = getenv("PSK_SCAN_DENSE");
+    CL.compact = ctx->cx_valid && !L.weighted && L.inline_masks && !(dense_env && atoi(dense_env) != 0);
+    if (CL.compact) {
+        CxScanArgs &x = CL.x;
+        CL.cpr = a.cpr;
+        x.slots = ctx->cx_slots.as<u32x4>();
+        x.ov = ctx->cx_ov.as<u32x4>();
+        x.ov_row = ctx->cx_ov_row.as<uint32_t>();
+        x.n_ov = ctx->cx_n_ov;
+        CL.grid = cx_grid(ctx, a.M, x.n_ov, CL.cpr, &x.slot_blocks);
+        cx_fill_tables(x, ctx->n_samples);
+        return setup_results_rows(ctx, a, CL.grid, cx_rows_per_block(x, CL.grid, CL.cpr), set);
+    }
     const bool table = a.lut != nullptr || a.lut6 != nullptr;
-    return setup_results(ctx, a, scan_grid(ctx, a.M, G, SC_UNROLL, table), G, table ? lut_unroll(G) : SC_UNROLL, set,
-                         table ? SC_LUT_THREADS : SC_THREADS);
+    CL.grid = scan_grid(ctx, a.M, G, SC_UNROLL, table);
+    return setup_results(ctx, a, CL.grid, G, table ? lut_unroll(G) : SC_UNROLL, set, table ? SC_LUT_THREADS : SC_THREADS);
 }
 
 // Launches the scan and returns without waiting; psk_scan_end collects it.  Lets a caller queue other work (the
@@ -1393,16 +1626,13 @@ static int chi2_scan_launch(psk_ctx *ctx, const int8_t *pheno, const double *wei
     ctx->last.omit_B = omit_B ? 1 : 0;
     ctx->last.n_kmers_global = n_kmers_global;
     ctx->last.n1 = n1; ctx->last.n0 = n0; ctx->last.W1 = W1; ctx->last.W0 = W0;
-    ScanArgs a;
-    PSK_TRY(fill_chi2_args(ctx, a, set));
-    a.n1 = n1; a.n0 = n0;
+    Chi2Launch CL;
+    PSK_TRY(fill_chi2_args(ctx, CL, set));
     ctx->last_scan_kind = 1;
     if (ctx->n_kmers) {
         ScanSlot &sl = ctx->slot[set];
-        const int G = group_lanes(a);
-        const dim3 grid = scan_grid(ctx, a.M, G, SC_UNROLL, a.lut != nullptr || a.lut6 != nullptr);
         PSK_HIP(ctx, hipEventRecord(sl.ev0, ctx->stream));
-        launch_chi2(pick_chi2_mode(ctx, ctx->last.weighted, a.pcut, a.pcut_bonf, a.omit_B), G, grid, ctx->stream, a);
+        launch_chi2_any(ctx, CL);
         PSK_HIP(ctx, hipGetLastError());
         PSK_HIP(ctx, hipEventRecord(sl.ev1, ctx->stream));
         sl.in_flight = true;
@@ -1464,11 +1694,10 @@ static int rescan(psk_ctx *ctx, int reps, double *mean_ms, double *ms_each)
     PSK_HIP(ctx, hipSetDevice(ctx->device));
     int set = 0;
     PSK_TRY(pick_result_set(ctx, &set));
-    ScanArgs a;
-    PSK_TRY(fill_chi2_args(ctx, a, set));
-    a.n1 = ctx->last.n1; a.n0 = ctx->last.n0; a.W1 = ctx->last.W1; a.W0 = ctx->last.W0;
+    Chi2Launch CL;
+    PSK_TRY(fill_chi2_args(ctx, CL, set));
     double ms = 0;
-    PSK_TRY(run_chi2(ctx, a, ctx->last.weighted, reps, &ms, ms_each));
+    PSK_TRY(run_chi2(ctx, CL, reps, &ms, ms_each));
     ctx->last_scan_ms = ms / reps;
     PSK_TRY(fetch_counts(ctx, set));
     if (mean_ms) *mean_ms = ms / reps;

@@ -217,7 +217,9 @@ extern "C" int psk_build_presence(psk_ctx *ctx, uint64_t *n_kmers)
     // their host images -- gigabytes of pages: 0.5 s to unmap -- are handed to a helper thread once the build is done with its own
     // allocations (psk_internal.h: gz_release_host)
     gz_release_device(ctx);
-    const int rc = build_presence_impl(ctx, n_kmers);
+    compact_release(ctx);   // the previous matrix's encoded copy goes before the new matrix is allocated
+    int rc = build_presence_impl(ctx, n_kmers);
+    if (rc == PSK_OK) rc = compact_encode(ctx);   // every route's matrix: the unweighted scan's exception-coded copy
     gz_release_host(ctx, false);
     return rc;
 }
@@ -506,6 +508,7 @@ extern "C" int psk_intersect_db(psk_ctx *ctx, const uint64_t *db_words, uint64_t
     PSK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->n_kmers = kept;
     ctx->last.valid = false;
+    PSK_TRY(compact_encode(ctx));
     if (n_kmers) *n_kmers = kept;
     return PSK_OK;
 }
@@ -519,6 +522,7 @@ extern "C" int psk_set_presence(psk_ctx *ctx, const uint64_t *words, const uint6
         return psk_fail(ctx, PSK_EINVAL, "words_per_row must be %d for %d samples", padded_wpr(n_samples), n_samples);
     if (!bits && n_kmers) return psk_fail(ctx, PSK_EINVAL, "null matrix");
     PSK_HIP(ctx, hipSetDevice(ctx->device));
+    compact_release(ctx);
     reset_lists(ctx, n_samples);
     ctx->n_samples = n_samples;
     ctx->wpr = words_per_row;
@@ -534,6 +538,7 @@ extern "C" int psk_set_presence(psk_ctx *ctx, const uint64_t *words, const uint6
         }
         PSK_HIP(ctx, hipMemcpy(ctx->bits.p, bits, n_kmers * (uint64_t)words_per_row * 8, hipMemcpyHostToDevice));
     }
+    PSK_TRY(compact_encode(ctx));
     PSK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->have_presence = true;
     ctx->dense_hint = -1;
@@ -547,6 +552,7 @@ extern "C" int psk_synth_presence(psk_ctx *ctx, uint64_t n_kmers, int n_samples,
     if (ctx->n_in_flight > 0) return psk_fail(ctx, PSK_ESTATE, "a scan is in flight on this matrix: psk_scan_end first");
     if (n_samples < 1 || n_kmers < 1) return psk_fail(ctx, PSK_EINVAL, "bad shape");
     PSK_HIP(ctx, hipSetDevice(ctx->device));
+    compact_release(ctx);
     reset_lists(ctx, n_samples);
     ctx->n_samples = n_samples;
     ctx->wpr = padded_wpr(n_samples);
@@ -558,6 +564,7 @@ extern "C" int psk_synth_presence(psk_ctx *ctx, uint64_t n_kmers, int n_samples,
     synth_presence_kernel<<<div_up(n_kmers * (uint64_t)ctx->wpr, 256), 256, 0, ctx->stream>>>(
         ctx->bits.as<uint64_t>(), n_kmers, ctx->wpr, n_samples, seed);
     PSK_HIP(ctx, hipGetLastError());
+    PSK_TRY(compact_encode(ctx));
     PSK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->have_presence = true;
     ctx->dense_hint = -1;

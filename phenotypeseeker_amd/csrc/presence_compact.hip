@@ -1,0 +1,156 @@
+// Exception-coded copy of the presence matrix for the unweighted chi2 scan (assoc_scan.hip chi2_scan_kernel_cx).
+//
+// A k-mer union of bacterial genomes is core-or-rare: at config 2 (256 x 5 Mbp, k = 13) 91.5 % of the rows differ from
+// all-absent or all-present in at most 7 samples.  Such a row needs one 8-byte slot -- a header byte (e = the number of
+// exceptions, whether they are the present or the absent samples) and the exceptions' sample indices as u8 -- against a
+// 32-byte dense row.  Rows with more exceptions are flagged in their slot and copied, ascending, into a side matrix of
+// dense rows with their row ids.  The scan then streams 8 B per row plus the side matrix (about 0.35 of the dense bytes
+// at config 2) and reads nothing else per row.  The dense matrix stays as it is: every other reader uses it.
+//
+// Two passes over the dense matrix: the first counts the overflow rows of every workgroup (whose exclusive scan places
+// them), the host decides from the total whether to keep a copy (CX_MAX_SHARE, CX_MAX_OVF_DIV), the second writes slots and side matrix.
+// PSK_TRACE=1 prints the decision and the time of the build.
+#include "dev_utils.h"
+#include "psk_internal.h"
+
+#include <chrono>
+
+namespace {
+
+constexpr int CX_THREADS = 256;
+typedef unsigned long long cx_u64x2 __attribute__((ext_vector_type(2)));
+
+// the row's words (wpr = 2 or 4), restricted to the n valid samples
+__device__ __forceinline__ int cx_load_row(const uint64_t *__restrict__ bits, uint64_t r, int wpr, int n, uint64_t w[4])
+{
+    const cx_u64x2 *p = reinterpret_cast<const cx_u64x2 *>(bits + r * (uint64_t)wpr);
+    const cx_u64x2 a = p[0];
+    const cx_u64x2 b = wpr == 4 ? p[1] : (cx_u64x2){0ull, 0ull};
+    w[0] = a.x; w[1] = a.y; w[2] = b.x; w[3] = b.y;
+    int pc = 0;
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        const int valid = n - 64 * c;
+        w[c] &= valid <= 0 ? 0ull : valid >= 64 ? ~0ull : (1ull << valid) - 1ull;
+        pc += __popcll(w[c]);
+    }
+    return pc;
+}
+
+__global__ __launch_bounds__(CX_THREADS) void cx_count_kernel(const uint64_t *__restrict__ bits, uint64_t M, int wpr, int n,
+                                                             uint32_t *__restrict__ counts)
+{
+    const uint64_t r = (uint64_t)blockIdx.x * CX_THREADS + threadIdx.x;
+    bool ovf = false;
+    if (r < M) {
+        uint64_t w[4];
+        const int pc = cx_load_row(bits, r, wpr, n, w);
+        ovf = min(pc, n - pc) > CX_MAX_E;
+    }
+    const int cnt = __syncthreads_count(ovf);
+    if (threadIdx.x == 0) counts[blockIdx.x] = (uint32_t)cnt;
+}
+
+// offs: exclusive scan of cx_count_kernel's counts (same grid)
+__global__ __launch_bounds__(CX_THREADS) void cx_encode_kernel(const uint64_t *__restrict__ bits, uint64_t M, int wpr, int n,
+                                                              const uint32_t *__restrict__ offs, uint64_t *__restrict__ slots,
+                                                              uint64_t *__restrict__ ov, uint32_t *__restrict__ ov_row)
+{
+    __shared__ uint32_t s_wave[CX_THREADS / 64];
+    const uint64_t r = (uint64_t)blockIdx.x * CX_THREADS + threadIdx.x;
+    uint64_t w[4] = {0ull, 0ull, 0ull, 0ull};
+    int pc = 0;
+    if (r < M) pc = cx_load_row(bits, r, wpr, n, w);
+    const bool absent = pc > n - pc;           // the exceptions are the absent samples
+    const int e = absent ? n - pc : pc;
+    const bool ovf = r < M && e > CX_MAX_E;
+    uint32_t total;
+    const uint32_t pos = psk_block_excl_scan_u32<CX_THREADS>(ovf ? 1u : 0u, &total, s_wave);   // ascending within the workgroup
+    if (r >= M) return;
+    if (ovf) {
+        const uint64_t j = (uint64_t)offs[blockIdx.x] + pos;
+        for (int c = 0; c < wpr; c++) ov[j * wpr + c] = w[c];
+        ov_row[j] = (uint32_t)r;
+        slots[r] = CX_HDR_OVF;
+        return;
+    }
+    uint64_t slot = (uint64_t)e | (absent ? CX_HDR_BASE : 0u);
+    int k = 1;
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        const int valid = n - 64 * c;
+        uint64_t x = absent ? ~w[c] & (valid <= 0 ? 0ull : valid >= 64 ? ~0ull : (1ull << valid) - 1ull) : w[c];
+        while (x) {   // at most CX_MAX_E bits over the whole row
+            slot |= (uint64_t)(64 * c + __builtin_ctzll(x)) << (8 * k);
+            k++;
+            x &= x - 1;
+        }
+    }
+    slots[r] = slot;
+}
+
+}  // namespace
+
+void compact_release(psk_ctx *ctx)
+{
+    dev_release(ctx->cx_slots);
+    dev_release(ctx->cx_ov);
+    dev_release(ctx->cx_ov_row);
+    ctx->cx_valid = false;
+    ctx->cx_n_ov = 0;
+}
+
+int compact_encode(psk_ctx *ctx)
+{
+    ctx->cx_valid = false;
+    const uint64_t M = ctx->n_kmers;
+    const int n = ctx->n_samples, wpr = ctx->wpr;
+    const bool trace = getenv("PSK_TRACE") != nullptr;
+    if (n < CX_MIN_SAMPLES || n > CX_MAX_SAMPLES || M == 0 || M > 0xffffffffull || (wpr != 2 && wpr != 4)) {
+        compact_release(ctx);
+        return PSK_OK;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint64_t nb = div_up(M, CX_THREADS);
+    PSK_TRY(dev_reserve(ctx, ctx->flags, nb * 4));
+    PSK_TRY(dev_reserve(ctx, ctx->misc, 64));
+    uint32_t *cnt = ctx->flags.as<uint32_t>(), *d_total = ctx->misc.as<uint32_t>() + 6;
+    const uint64_t *bits = ctx->bits.as<uint64_t>();
+    cx_count_kernel<<<(unsigned)nb, CX_THREADS, 0, ctx->stream>>>(bits, M, wpr, n, cnt);
+    PSK_HIP(ctx, hipGetLastError());
+    PSK_TRY(dev_exclusive_scan_u32(ctx, cnt, cnt, nb, d_total));
+    uint32_t n_ov = 0;
+    PSK_HIP(ctx, hipMemcpyAsync(&n_ov, d_total, 4, hipMemcpyDeviceToHost, ctx->stream));
+    PSK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const double dense = (double)M * wpr * 8, enc = (double)M * 8 + (double)n_ov * (wpr * 8 + 4);
+    if (enc > CX_MAX_SHARE * dense || (uint64_t)n_ov * CX_MAX_OVF_DIV > M) {
+        compact_release(ctx);
+        if (trace)
+            fprintf(stderr, "[psk] compact rows: declined (%.3f of the dense bytes; %llu of %llu rows overflow)\n", enc / dense,
+                    (unsigned long long)n_ov, (unsigned long long)M);
+        return PSK_OK;
+    }
+    PSK_TRY(dev_reserve(ctx, ctx->cx_slots, (M + 1) / 2 * 16));
+    PSK_TRY(dev_reserve(ctx, ctx->cx_ov, (n_ov ? n_ov : 1) * (uint64_t)wpr * 8));
+    PSK_TRY(dev_reserve(ctx, ctx->cx_ov_row, (n_ov ? n_ov : 1) * 4ull));
+    cx_encode_kernel<<<(unsigned)nb, CX_THREADS, 0, ctx->stream>>>(bits, M, wpr, n, cnt, ctx->cx_slots.as<uint64_t>(),
+                                                                  ctx->cx_ov.as<uint64_t>(), ctx->cx_ov_row.as<uint32_t>());
+    PSK_HIP(ctx, hipGetLastError());
+    ctx->cx_n_ov = n_ov;
+    ctx->cx_valid = true;
+    if (trace) {
+        PSK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        fprintf(stderr, "[psk] compact rows: %.3f ms, %.1f MB of slots + %.1f MB of overflow rows (%llu of %llu) = %.3f of the dense bytes\n",
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), M * 8 / 1e6,
+                n_ov * (wpr * 8.0 + 4) / 1e6, (unsigned long long)n_ov, (unsigned long long)M, enc / dense);
+    }
+    return PSK_OK;
+}
+
+extern "C" int psk_compact_info(const psk_ctx *ctx, int *encoded, uint64_t *overflow_rows)
+{
+    if (!ctx) return PSK_EINVAL;
+    if (encoded) *encoded = ctx->cx_valid ? 1 : 0;
+    if (overflow_rows) *overflow_rows = ctx->cx_valid ? ctx->cx_n_ov : 0;
+    return PSK_OK;
+}

@@ -172,6 +172,11 @@ struct psk_ctx {
     int wpr = 0;  // u64 words per row: 1 up to 64 samples, else even
     DevBuf union_words, bits;
     bool have_presence = false;
+    // exception-coded copy of `bits` for the unweighted chi2 scan (presence_compact.hip): one 8-byte slot per row, and the
+    // rows with more than CX_MAX_E exceptions as dense rows of a side matrix with their row ids.  cx_valid = false: none
+    DevBuf cx_slots, cx_ov, cx_ov_row;
+    bool cx_valid = false;
+    uint64_t cx_n_ov = 0;
 
     // scan state
     DevBuf mask1, phe, res_count, res_sorted;
@@ -208,6 +213,21 @@ void psk_forget_lane_slices(psk_ctx *ctx);   // kmer_count.hip
         int rc_ = (expr);          \
         if (rc_ != PSK_OK) return rc_; \
     } while (0)
+
+// ---- exception-coded rows (presence_compact.hip) ----------------------------------------------------------------------
+// Slot of a row (u64, little endian): byte 0 = header -- bits 0..2 e, bit 3 "the exceptions are the ABSENT samples",
+// bit 4 overflow (e > CX_MAX_E: the row is in the side matrix) --, bytes 1..e = the exceptions' sample indices, ascending.
+constexpr int CX_MAX_E = 7;
+constexpr uint32_t CX_HDR_BASE = 8, CX_HDR_OVF = 16;
+constexpr int CX_MIN_SAMPLES = 65, CX_MAX_SAMPLES = 256;   // up to 64 samples a dense row is already 8 bytes
+// Encoded when slots + side matrix + its row ids take at most CX_MAX_SHARE of the dense matrix's bytes and at most
+// 1 / CX_MAX_OVF_DIV of the rows overflow: a core-or-rare matrix.  Config 2 (256 x 5 Mbp, k = 13): 0.35 and 8.5 %.  The
+// device-generated matrix of psk_synth_presence (19 % random-density rows: 0.46 at 256 samples) is declined, so that
+// the scans of generated matrices -- bench.py's beyond-cache leg among them -- keep measuring the dense stream.
+constexpr double CX_MAX_SHARE = 0.6;
+constexpr uint64_t CX_MAX_OVF_DIV = 8;
+int compact_encode(psk_ctx *ctx);     // (re)builds the copy of the current matrix, or declines and frees it
+void compact_release(psk_ctx *ctx);
 
 int dev_reserve(psk_ctx *ctx, DevBuf &b, size_t bytes);  // grow-only, contents NOT preserved
 void dev_release(DevBuf &b);

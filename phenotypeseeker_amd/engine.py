@@ -356,6 +356,12 @@ class PskContext:
         a = np.ascontiguousarray(arr)
         self._check(self._lib.psk_dev_copy(self._h, ctypes.c_void_p(int(ptr)), _ptr(a), a.nbytes, 0, 0), "psk_dev_copy")
 
+    def compact_info(self):
+        """(has the matrix an exception-coded copy for the unweighted chi2 scan, rows of its dense side matrix)"""
+        enc, n_ov = ctypes.c_int(), ctypes.c_uint64()
+        self._check(self._lib.psk_compact_info(self._h, ctypes.byref(enc), ctypes.byref(n_ov)), "psk_compact_info")
+        return bool(enc.value), n_ov.value
+
     def last_scan_ms(self):
         return self._lib.psk_last_scan_ms(self._h)
 
