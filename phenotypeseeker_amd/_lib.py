@@ -14,6 +14,11 @@ class PskError(RuntimeError):
         self.code = code
 
 
+def env_flag(name):
+    """A PSK_* flag as the library reads it (docs/KNOBS.md): on when set to anything but "" or "0"."""
+    return os.environ.get(name, "") not in ("", "0")
+
+
 PSK_EGZIP = -6    # include/psk.h: (PSK_NO_GPU_GZ=1 only, since r05) a file input is gzip-compressed; the caller inflates it and uses the in-memory call
 
 

@@ -1,7 +1,10 @@
 // Context lifecycle, error reporting and device-memory helpers of libpsk.so.
 #include "psk_internal.h"
 
+#include <algorithm>
+#include <cerrno>
 #include <chrono>
+#include <climits>
 
 #include <mutex>
 
@@ -26,6 +29,55 @@ std::string psk_error_text(psk_ctx *ctx)
 {
     std::lock_guard<std::mutex> lk(g_err_mu);
     return ctx ? ctx->err : g_init_error;
+}
+
+// The PSK_* knobs (psk_internal.h)
+const char *env_str(const char *name)
+{
+    const char *v = getenv(name);
+    return v && *v ? v : nullptr;
+}
+
+bool env_flag(const char *name) { const char *v = env_str(name); return v && strcmp(v, "0") != 0; }
+
+int env_int(psk_ctx *ctx, const char *name, int64_t lo, int64_t hi, int64_t *out, bool *set)
+{
+    const char *v = env_str(name);
+    if (set) *set = v != nullptr;
+    if (!v) return PSK_OK;
+    char *end = nullptr;
+    errno = 0;
+    const long long x = strtoll(v, &end, 10);
+    if (errno || end == v || *end || x < lo || x > hi)
+        return psk_fail(ctx, PSK_EINVAL, "%s=%s: expected an integer in [%lld, %lld]", name, v, (long long)lo, (long long)hi);
+    *out = x;
+    return PSK_OK;
+}
+
+int env_choice(psk_ctx *ctx, const char *name, std::initializer_list<int> allowed, int *out)
+{
+    const char *v = env_str(name);
+    int64_t x = *out;
+    if (!v || (env_int(ctx, name, INT_MIN, INT_MAX, &x) == PSK_OK && std::find(allowed.begin(), allowed.end(), x) != allowed.end())) {
+        *out = (int)x;
+        return PSK_OK;
+    }
+    std::string list;
+    for (int a : allowed) list += (list.empty() ? "" : ", ") + std::to_string(a);
+    return psk_fail(ctx, PSK_EINVAL, "%s=%s: expected one of %s", name, v, list.c_str());
+}
+
+int env_real(psk_ctx *ctx, const char *name, double lo, double hi, double *out)
+{
+    const char *v = env_str(name);
+    if (!v) return PSK_OK;
+    char *end = nullptr;
+    errno = 0;
+    const double x = strtod(v, &end);
+    if (errno || end == v || *end || !(x > lo && x <= hi))
+        return psk_fail(ctx, PSK_EINVAL, "%s=%s: expected a number in (%g, %g]", name, v, lo, hi);
+    *out = x;
+    return PSK_OK;
 }
 
 void psk_set_error_text(psk_ctx *ctx, const std::string &text)
@@ -99,11 +151,6 @@ struct PinnedCache {
     size_t bytes = 0;
 };
 PinnedCache g_pinned;
-size_t pinned_cache_limit()
-{
-    const char *e = getenv("PSK_PINNED_CACHE_MB");
-    return (size_t)(e && *e ? strtoull(e, nullptr, 10) : 1024) << 20;
-}
 }  // namespace
 
 int pinned_acquire(psk_ctx *ctx, size_t need, void **buf, size_t *cap)
@@ -141,7 +188,7 @@ void pinned_release(psk_ctx *ctx, void *buf, size_t cap)
     if (!buf) return;
     {
         std::lock_guard<std::mutex> lk(g_pinned.mu);
-        if (cap && g_pinned.bytes + cap <= pinned_cache_limit()) {
+        if (cap && g_pinned.bytes + cap <= ctx->pinned_cache_mb << 20) {
             g_pinned.held.push_back({buf, cap, ctx->device});
             g_pinned.bytes += cap;
             return;
@@ -182,6 +229,11 @@ extern "C" int psk_init(int device, psk_ctx **ctx_out)
     psk_ctx *ctx = new (std::nothrow) psk_ctx();
     if (!ctx) return psk_fail(nullptr, PSK_ENOMEM, "out of host memory");
     ctx->device = device;
+    if (env_int(nullptr, "PSK_GRID_MULT", 1, 1 << 16, &ctx->grid_mult) || env_int(nullptr, "PSK_COPY_STREAMS", 1, 4, &ctx->copy_streams) ||
+        env_int(nullptr, "PSK_PINNED_CACHE_MB", 0, 1 << 30, &ctx->pinned_cache_mb)) {
+        delete ctx;
+        return PSK_EINVAL;
+    }
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) ctx->n_cu = prop.multiProcessorCount;
     if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess ||
@@ -198,7 +250,7 @@ extern "C" void psk_free(psk_ctx *ctx)
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    const bool trace = getenv("PSK_TRACE") != nullptr;
+    const bool trace = env_flag("PSK_TRACE");
     const auto t0 = std::chrono::steady_clock::now();
     auto lap = [&](const char *what) {
         if (trace) fprintf(stderr, "[psk] psk_free: %s at %.1f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());

@@ -1004,8 +1004,8 @@ size_t lut_bytes(int chunks, int nm) { return (size_t)chunks * 32 * 16 * nm * 8;
 // 0 = the per-sample kernels (PSK_NO_LUT, or rows wider than 16 lanes)
 int lut_chunks(int cpr, int nm)
 {
-    if (getenv("PSK_NO_LUT") || cpr > 16) return 0;
-    int c = getenv("PSK_LUT_HALF") ? (cpr + 1) / 2 : cpr;
+    if (env_flag("PSK_NO_LUT") || cpr > 16) return 0;
+    int c = env_flag("PSK_LUT_HALF") ? (cpr + 1) / 2 : cpr;
     while (c > 0 && lut_bytes(c, nm) > SC_LUT_MAX_BYTES) c--;
     return c;
 }
@@ -1058,16 +1058,12 @@ void launch_chi2(int mode, int G, dim3 grid, hipStream_t st, const ScanArgs &a)
 // pre-test -- the last chi2 scan of this matrix kept more than 0.1 % of the rows, or, with no history, the keep rule
 // itself lets that many through under the null hypothesis (p < cut holds for a fraction `cut` of unassociated rows).
 // PSK_CHI2_MODE=0|2 forces one (A/B runs).
-int pick_chi2_mode(const psk_ctx *ctx, bool weighted, double pcut, double pcut_bonf, int omit_B)
+int pick_chi2_mode(psk_ctx *ctx, bool weighted, double pcut, double pcut_bonf, int omit_B, int *mode)
 {
-    if (weighted) return 1;
-    const char *env = getenv("PSK_CHI2_MODE");   // read per call: tests cross the two forms inside one process
-    const int forced = env ? atoi(env) : -1;
-    if (forced == 0 || forced == 2) return forced;
-    if (ctx->dense_hint >= 0) return ctx->dense_hint ? 2 : 0;
     double expect = pcut_bonf;
     if (omit_B && pcut > expect) expect = pcut;
-    return expect > 1e-3 ? 2 : 0;
+    *mode = weighted ? 1 : ctx->dense_hint >= 0 ? (ctx->dense_hint ? 2 : 0) : expect > 1e-3 ? 2 : 0;
+    return weighted ? PSK_OK : env_choice(ctx, "PSK_CHI2_MODE", {0, 2}, mode);   // read per scan: tests cross the two forms in one process
 }
 
 // Second pass of the Welch scan: one workgroup per result segment, one candidate per lane.  The candidate's moments are
@@ -1257,7 +1253,7 @@ int build_moment_lut(psk_ctx *ctx, const double *tab, int chunks, int nm, const 
 int build_moment_lut6(psk_ctx *ctx, const double *tab, int cpr, int nm, const float **lut6_out)
 {
     *lut6_out = nullptr;
-    if (getenv("PSK_NO_LUT") || getenv("PSK_LUT_F64") || cpr > 16 || lut6_bytes(cpr, nm) > SC_LUT_MAX_BYTES) return PSK_OK;
+    if (env_flag("PSK_NO_LUT") || env_flag("PSK_LUT_F64") || cpr > 16 || lut6_bytes(cpr, nm) > SC_LUT_MAX_BYTES) return PSK_OK;
     PSK_TRY(dev_reserve(ctx, ctx->lut, lut6_bytes(cpr, nm)));
     const int n = cpr * SC_L6_ENTRIES;
     if (nm == 2) moment_lut6_kernel<2><<<div_up((uint64_t)n, 256), 256, 0, ctx->stream>>>(tab, cpr, ctx->lut.as<float>());
@@ -1366,6 +1362,9 @@ __global__ void pack_segments_kernel(const uint8_t *__restrict__ src, uint64_t c
     }
 }
 
+// most workgroups of a scan launch: PSK_GRID_MULT (read by psk_init) per CU
+uint64_t scan_grid_cap(const psk_ctx *ctx) { return (uint64_t)(ctx->n_cu > 0 ? ctx->n_cu : 256) * (ctx->grid_mult ? ctx->grid_mult : PSK_SC_GRID_MULT); }
+
 dim3 scan_grid(const psk_ctx *ctx, uint64_t M, int G, int unroll, bool lut = false)
 {
     // the table-in-LDS form: one 1024-thread workgroup per CU (its 64-120 KB of LDS admit no second one), and one
@@ -1375,8 +1374,7 @@ dim3 scan_grid(const psk_ctx *ctx, uint64_t M, int G, int unroll, bool lut = fal
     const uint64_t steps = (M + rpw - 1) / rpw;
     const uint64_t waves = (steps + unroll - 1) / unroll;
     uint64_t blocks = (waves + SC_THREADS / 64 - 1) / (SC_THREADS / 64);
-    static const int mult = [] { const char *e = getenv("PSK_GRID_MULT"); const int v = e ? atoi(e) : 0; return v > 0 ? v : PSK_SC_GRID_MULT; }();
-    const uint64_t cap = (uint64_t)(ctx->n_cu > 0 ? ctx->n_cu : 256) * mult;
+    const uint64_t cap = scan_grid_cap(ctx);
     if (blocks > cap) blocks = cap;
     if (blocks < SC_NSEG) blocks = SC_NSEG;  // every result segment needs a workgroup to publish its count
     return dim3((unsigned)blocks);
@@ -1413,8 +1411,7 @@ dim3 cx_grid(const psk_ctx *ctx, uint64_t M, uint64_t n_ov, int cpr, uint32_t *s
     const uint64_t n_pairs = (M + 1) / 2, ov_rpw = 64 / cpr;
     uint64_t bs = ((n_pairs + 64 * CX_UNROLL - 1) / (64 * CX_UNROLL) + wpb - 1) / wpb;
     uint64_t bo = (((n_ov + ov_rpw - 1) / ov_rpw + CX_UNROLL - 1) / CX_UNROLL + wpb - 1) / wpb;
-    static const int mult = [] { const char *e = getenv("PSK_GRID_MULT"); const int v = e ? atoi(e) : 0; return v > 0 ? v : PSK_SC_GRID_MULT; }();
-    const uint64_t cap = (uint64_t)(ctx->n_cu > 0 ? ctx->n_cu : 256) * mult;
+    const uint64_t cap = scan_grid_cap(ctx);
     if (bs + bo > cap) {
         const double slot_bytes = 16.0 * n_pairs, ov_bytes = 16.0 * cpr * n_ov;
         const uint64_t s = (uint64_t)(cap * slot_bytes / (slot_bytes + ov_bytes) + 0.5);
@@ -1469,6 +1466,7 @@ void cx_fill_tables(CxScanArgs &x, int n_samples)
 struct Chi2Launch {
     CxScanArgs x;      // x.s: every form's arguments; the rest: chi2_scan_kernel_cx's
     bool compact = false;
+    int mode = 0;      // of the dense kernels (pick_chi2_mode)
     int cpr = 0;
     dim3 grid;
 };
@@ -1481,7 +1479,7 @@ void launch_chi2_any(psk_ctx *ctx, const Chi2Launch &L)
         else chi2_scan_kernel_cx<2><<<L.grid, SC_THREADS, 0, ctx->stream>>>(L.x);
         return;
     }
-    launch_chi2(pick_chi2_mode(ctx, ctx->last.weighted, a.pcut, a.pcut_bonf, a.omit_B), group_lanes(a), L.grid, ctx->stream, a);
+    launch_chi2(L.mode, group_lanes(a), L.grid, ctx->stream, a);
 }
 
 int run_chi2(psk_ctx *ctx, const Chi2Launch &L, int reps, double *ms_total, double *ms_each = nullptr)
@@ -1540,8 +1538,7 @@ static int fill_chi2_args(psk_ctx *ctx, Chi2Launch &CL, int set)
         a.e1 = lut6_gamma(a.cpr) * L.W0 + 1e-36;
     }
     a.n1 = L.n1; a.n0 = L.n0;
-    const char *dense_env = getenv("PSK_SCAN_DENSE");
-    CL.compact = ctx->cx_valid && !L.weighted && L.inline_masks && !(dense_env && atoi(dense_env) != 0);
+    CL.compact = ctx->cx_valid && !L.weighted && L.inline_masks && !env_flag("PSK_SCAN_DENSE");
     if (CL.compact) {
         CxScanArgs &x = CL.x;
         CL.cpr = a.cpr;
@@ -1553,6 +1550,7 @@ static int fill_chi2_args(psk_ctx *ctx, Chi2Launch &CL, int set)
         cx_fill_tables(x, ctx->n_samples);
         return setup_results_rows(ctx, a, CL.grid, cx_rows_per_block(x, CL.grid, CL.cpr), set);
     }
+    PSK_TRY(pick_chi2_mode(ctx, L.weighted, a.pcut, a.pcut_bonf, a.omit_B, &CL.mode));
     const bool table = a.lut != nullptr || a.lut6 != nullptr;
     CL.grid = scan_grid(ctx, a.M, G, SC_UNROLL, table);
     return setup_results(ctx, a, CL.grid, G, table ? lut_unroll(G) : SC_UNROLL, set, table ? SC_LUT_THREADS : SC_THREADS);

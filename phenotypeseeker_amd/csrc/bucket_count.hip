@@ -588,11 +588,10 @@ BsBufs bs_bufs(const CountLane &L, uint32_t slot)
     return d;
 }
 
-uint32_t bs_cap()
+int bs_cap(psk_ctx *ctx, uint32_t *cap)
 {
-    const char *e = getenv("PSK_BS_CAP");   // tests: a small capacity forces the fall-back (read per call)
-    const long v = e ? atol(e) : 0;
-    return (uint32_t)(v > 0 && v < (long)BS_CAP_MAX ? v : (long)BS_CAP_MAX);
+    *cap = BS_CAP_MAX;
+    return env_int(ctx, "PSK_BS_CAP", 1, BS_CAP_MAX, cap);   // tests: a small capacity forces the fall-back (read per call)
 }
 
 template <int K>
@@ -684,12 +683,14 @@ int chain_enqueue_w(psk_ctx *ctx, CountLane &L, uint64_t clean_len, uint64_t n)
         PSK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(bs_sort_kernel<W>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                          (int)bsort_lds_bytes<W>()));
     }
+    uint32_t cap = 0;
+    PSK_TRY(bs_cap(ctx, &cap));
     W *wtmp = L.dc_mtemp.as<W>();
     uint32_t *ctmp = reinterpret_cast<uint32_t *>(wtmp + n + 8);
     const uint32_t resident = (uint32_t)SortGeo<W>::WGS_PER_CU * (uint32_t)(ctx->n_cu > 0 ? ctx->n_cu : 256);
     const uint32_t sort_wgs = ctx->bs_nb < resident ? ctx->bs_nb : resident;
     bs_sort_kernel<W><<<sort_wgs, SortGeo<W>::THREADS, bsort_lds_bytes<W>(), ctx->stream>>>(L.dc_part.as<W>(), d.cnt, d.base, ctx->bs_spl.as<W>(),
-                                                                                          ctx->bs_nb, (W)(hi - 1u), bs_cap(), wtmp, ctmp, d.uniq, d.flag);
+                                                                                          ctx->bs_nb, (W)(hi - 1u), cap, wtmp, ctmp, d.uniq, d.flag);
     PSK_HIP(ctx, hipGetLastError());
     bs_totals_kernel<<<1, 1024, 0, ctx->stream>>>(d.cnt, d.uniq, d.uoff, d.flag, ctx->bs_nb, L.pinned_cnt);
     PSK_HIP(ctx, hipGetLastError());
@@ -754,7 +755,7 @@ int group_enqueue_w(psk_ctx *ctx, CountLane *const *lanes, const uint64_t *clean
     p.n = (uint32_t)count;
     slab_bounds_w(ctx, &p.lo, &p.hi);
     p.last_word = (W)(p.hi - 1u);
-    p.cap = bs_cap();
+    PSK_TRY(bs_cap(ctx, &p.cap));
     p.mp = BsMap<W>{(W)ctx->bs_lo, ctx->bs_shift, ctx->bs_nb};
     p.spl = ctx->bs_spl.as<W>();
     p.ct = ctx->bs_ct.as<uint16_t>();
@@ -851,7 +852,7 @@ bool bucket_route_ok(const psk_ctx *ctx, uint64_t n)
 int bucket_splitters_from(psk_ctx *ctx, const SampleList &S, uint64_t windows)
 {
     if (ctx->bs_ready || ctx->dense_mode || !bs_k_ok(ctx) || S.n_unique < 32768 || !S.words) return PSK_OK;
-    if (getenv("PSK_NO_BUCKET_SORT")) return PSK_OK;   // read per call: tests cross the two routes in one process
+    if (env_flag("PSK_NO_BUCKET_SORT")) return PSK_OK;   // read per call: tests cross the two routes in one process
     // about 2,400 words per bucket (the LDS sort takes 8,192): a genome gives 2,048 buckets, a rank's eighth of it 256
     uint32_t nb = 64;
     while (nb < BS_NB && (uint64_t)nb * 2400 < S.n_unique) nb <<= 1;
@@ -885,7 +886,7 @@ int bucket_chain_finalize(psk_ctx *ctx, CountLane &L, SampleList &S, uint64_t n_
     }
 #endif
     if (L.pinned_cnt[3]) {
-        if (getenv("PSK_TRACE")) fprintf(stderr, "bucketed sort: a sample takes the fall-back (a bucket or a sub-bin overflowed)\n");
+        if (env_flag("PSK_TRACE")) fprintf(stderr, "bucketed sort: a sample takes the fall-back (a bucket or a sub-bin overflowed)\n");
         *fell_back = true;
         return PSK_OK;   // the caller runs the radix route on dc_part (bucket_fallback_keys)
     }

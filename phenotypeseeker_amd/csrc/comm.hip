@@ -34,7 +34,7 @@ RcclApi g_rccl;
 int load_rccl(psk_ctx *ctx)
 {
     if (g_rccl.lib) return PSK_OK;
-    const char *names[] = {getenv("PSK_RCCL_LIB"), "librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
+    const char *names[] = {env_str("PSK_RCCL_LIB"), "librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
     void *lib = nullptr;
     for (const char *nm : names) {
         if (!nm || !*nm) continue;

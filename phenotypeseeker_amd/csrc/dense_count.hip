@@ -548,7 +548,7 @@ void dense_configure(psk_ctx *ctx)
 {
     ctx->dense_mode = false;
     ctx->dense_b0 = ctx->dense_nb = 0;
-    if (getenv("PSK_NO_DENSE")) return;
+    if (env_flag("PSK_NO_DENSE")) return;
     const int k = ctx->k;
     // below 2^21 words a bucket holds too large a share of a sample's keys for one workgroup; above 2^26 the bitmap
     // outgrows the list it replaces
@@ -650,7 +650,7 @@ int dense_chain_enqueue(psk_ctx *ctx, CountLane &L, int sample_idx, uint64_t cle
     L.raw_used = true;
     // few keys per bucket (a genome): the presence-bit pass, which leaves over-full buckets to the table pass that
     // dense_chain_finalize runs when the totals report any; many (reads at depth): the table pass at once
-    const bool sparse = n / nb < 4096 && !getenv("PSK_DC_TABLE");
+    const bool sparse = n / nb < 4096 && !env_flag("PSK_DC_TABLE");
     if (sparse)
         dc_count_sparse_kernel<<<nb, SP_THREADS, 0, ctx->stream>>>(L.dc_part.as<uint16_t>(), d.cnt, d.base, ctx->dense_b0, S.bitmap,
                                                                    d.mt_w, d.mt_f, d.uniq, d.multi, d.need);
@@ -694,11 +694,10 @@ int dense_chain_finalize(psk_ctx *ctx, CountLane &L, uint64_t *n_kept, uint64_t 
 }
 
 // ---- a group of samples in one launch chain (psk_count_kmers_batch, genomes at k = 11..13) -------------------------------
-int dense_group_size()
+int dense_group_size(psk_ctx *ctx, int *G)
 {
-    const char *e = getenv("PSK_DC_GROUP");   // read per call: tests cross group sizes in one process
-    const int v = e ? atoi(e) : DC_GROUP;
-    return v < 1 ? 1 : (v > DC_GROUP ? DC_GROUP : v);
+    *G = DC_GROUP;
+    return env_int(ctx, "PSK_DC_GROUP", 1, DC_GROUP, G);   // read per call: tests cross group sizes in one process
 }
 
 void dense_lane_bytes(const psk_ctx *ctx, size_t max_len, size_t out[5])
@@ -711,7 +710,7 @@ void dense_lane_bytes(const psk_ctx *ctx, size_t max_len, size_t out[5])
 }
 
 // may this sample's chain ride in a group?  (few keys per bucket: the presence-bit pass; read sets take the table pass alone)
-bool dense_group_ok(const psk_ctx *ctx, uint64_t n) { return ctx->dense_mode && n > 0 && n / ctx->dense_nb < 4096 && !getenv("PSK_DC_TABLE"); }
+bool dense_group_ok(const psk_ctx *ctx, uint64_t n) { return ctx->dense_mode && n > 0 && n / ctx->dense_nb < 4096 && !env_flag("PSK_DC_TABLE"); }
 
 template <int K>
 static int launch_group_tiles(psk_ctx *ctx, const DcBatch &p, uint32_t tiles)

@@ -1221,12 +1221,6 @@ struct GzFile {
     int nul_slot = -1;    // its entry of the writing pass's per-file tables
 };
 
-size_t gz_env(const char *name, size_t dflt)
-{
-    const char *s = std::getenv(name);
-    return s && *s ? (size_t)std::strtoull(s, nullptr, 10) : dflt;
-}
-
 // zlib, every member of the file (what gzip.decompress and glistmaker's reader do); false: *err says why not
 bool gz_host_inflate(const uint8_t *d, size_t n, std::vector<uint8_t> &out, std::string *err)
 {
@@ -1288,16 +1282,18 @@ uint64_t gz_image_layout(int n, const size_t *sizes, uint64_t *at)
 // Measured (r05): 8 / 16 / 32 genomes of 5 Mbp as .fasta.gz: device 40 / 41 / 43 ms, eight host threads 12 / 37 / 77; four
 // .fastq.gz files of 64 MB of text: 38 against 224 (four files keep four threads busy).  PSK_GZ_DEVICE_MIN_MB replaces the
 // estimate by a threshold on the compressed megabytes.
-bool gz_group_on_device(int n, const size_t *sizes, bool host_only, int host_threads)
+int gz_group_on_device(psk_ctx *ctx, int n, const size_t *sizes, bool host_only, int host_threads, bool *on)
 {
-    if (host_only || n <= 0) return false;
-    size_t comp_bytes = 0;
+    *on = false;
+    if (host_only || n <= 0) return PSK_OK;
+    size_t comp_bytes = 0, min_mb = 0;
     for (int i = 0; i < n; i++) comp_bytes += sizes[i];
-    const char *fixed = std::getenv("PSK_GZ_DEVICE_MIN_MB");
-    if (fixed && *fixed) return comp_bytes >= (gz_env("PSK_GZ_DEVICE_MIN_MB", 48) << 20);
+    bool fixed = false;
+    PSK_TRY(env_int(ctx, "PSK_GZ_DEVICE_MIN_MB", 0, 1 << 30, &min_mb, &fixed));
     const int threads = std::max(1, std::min(n, std::min(host_threads < 1 ? 1 : host_threads, 32)));
     const double host_ms = 4.0 * (double)comp_bytes / (0.45e6 * threads), device_ms = 40.0 + (double)comp_bytes / 10e6;
-    return device_ms < host_ms;
+    *on = fixed ? comp_bytes >= (min_mb << 20) : device_ms < host_ms;
+    return PSK_OK;
 }
 
 // Inflates n gzip images.  The text of file i is out_dev[res[i].off, + res[i].len) when res[i].on_device, else
@@ -1342,11 +1338,13 @@ int gz_inflate_group(psk_ctx *ctx, int n, const uint8_t *const *data, const size
                 if (!errs[(size_t)j].empty()) return psk_fail(ctx, PSK_EINVAL, "%s", errs[(size_t)j].c_str());
         return PSK_OK;
     };
-    if (!gz_group_on_device(n, sizes, host_only, host_threads)) {
+    bool on_device = false;
+    PSK_TRY(gz_group_on_device(ctx, n, sizes, host_only, host_threads, &on_device));
+    if (!on_device) {
         std::vector<int> all((size_t)n);
         for (int i = 0; i < n; i++) all[(size_t)i] = i;
         PSK_TRY(host_route(all));
-        if (std::getenv("PSK_TRACE"))
+        if (env_flag("PSK_TRACE"))
             std::fprintf(stderr, "[psk] gz inflate: %d files, %.1f MB compressed: zlib on at most %d host threads\n", n, comp_bytes / 1e6, host_threads < 1 ? 1 : host_threads);
         return PSK_OK;
     }
@@ -1363,8 +1361,9 @@ int gz_inflate_group(psk_ctx *ctx, int n, const uint8_t *const *data, const size
     // ---- the chunks --------------------------------------------------------------------------------------------
     size_t deflate_bytes = 0;
     for (int i = 0; i < n; i++) deflate_bytes += sizes[i];
-    const size_t want_lanes = gz_env("PSK_GZ_LANES", 65536);   // four waves on each of 256 CUs
-    size_t chunk = gz_env("PSK_GZ_CHUNK", 0);
+    size_t want_lanes = 65536, chunk = 0;   // lanes: four waves on each of 256 CUs; chunk 0: from the lanes
+    PSK_TRY(env_int(ctx, "PSK_GZ_LANES", 1, 1 << 30, &want_lanes));
+    PSK_TRY(env_int(ctx, "PSK_GZ_CHUNK", 0, 1ll << 40, &chunk));
     if (!chunk) chunk = std::min<size_t>(std::max<size_t>(deflate_bytes / want_lanes, 16 << 10), 4 << 20);   // (16 KB: less than a block of most encoders -- two cuts in one block find the same start and one of the two lanes idles, but a group that cannot fill the part anyway is cut at every block: 1.15 GB of FASTQ text 69 -> 51 ms)
     chunk = (chunk + 3) & ~(size_t)3;
     std::vector<GzChunk> ch;
@@ -1417,7 +1416,7 @@ int gz_inflate_group(psk_ctx *ctx, int n, const uint8_t *const *data, const size
         file_chunks[i].second = (int)ch.size();
     }
     const auto t_begin = std::chrono::steady_clock::now();
-    const bool trace = std::getenv("PSK_TRACE") != nullptr;
+    const bool trace = env_flag("PSK_TRACE");
     auto t_last = t_begin;
     std::string phases;
     auto lap = [&](const char *what) {
@@ -1450,7 +1449,8 @@ int gz_inflate_group(psk_ctx *ctx, int n, const uint8_t *const *data, const size
     for (size_t c = 0; c < ch.size(); c++) todo.push_back((int)c);
     std::vector<uint8_t> stage;
     int rounds = 0;
-    const int max_rounds = (int)gz_env("PSK_GZ_ROUNDS", 24);
+    int max_rounds = 24;
+    PSK_TRY(env_int(ctx, "PSK_GZ_ROUNDS", 0, 1 << 20, &max_rounds));
     // ---- step 1: the starts ---------------------------------------------------------------------------------------
     {
         std::vector<int> seek;
@@ -1507,7 +1507,9 @@ int gz_inflate_group(psk_ctx *ctx, int n, const uint8_t *const *data, const size
     // 1.9 GB in 21 ms), so this is the bound on what a file with no dynamic block headers -- stored or fixed-code blocks only, or one
     // crafted to look so -- can cost the call before zlib gets it: 1 MiB = 0.75 s (r05: 8 MiB = 6 s, and again in every round of a
     // file of several such members).  Blocks of the usual encoders end far sooner (zlib: tens of KB; pigz 128 KB; libdeflate <= ~300 KB).
-    const uint64_t max_span_bits = (uint64_t)std::max<size_t>(chunk * 8, gz_env("PSK_GZ_MAX_SPAN", 1 << 20)) * 8;
+    size_t max_span = 1 << 20;
+    PSK_TRY(env_int(ctx, "PSK_GZ_MAX_SPAN", 0, 1ll << 40, &max_span));
+    const uint64_t max_span_bits = (uint64_t)std::max<size_t>(chunk * 8, max_span) * 8;
     std::vector<int> next_chunk((size_t)n, -1);   // per file: the chunk its chain follows next (-1: the chain has reached the end)
     for (int i = 0; i < n; i++) next_chunk[(size_t)i] = files[(size_t)i].device_ok && file_chunks[(size_t)i].second > file_chunks[(size_t)i].first ? file_chunks[(size_t)i].first : -1;
     while (!todo.empty()) {
@@ -1706,7 +1708,7 @@ int gz_inflate_group(psk_ctx *ctx, int n, const uint8_t *const *data, const size
     total = (total + 63) & ~63ull;
     const size_t m = order.size();
     std::vector<unsigned long long> nul_at;   // per file of the writing pass: where its text has its first NUL (in out_buf), ~0: nowhere
-    const size_t guard = std::getenv("PSK_GZ_GUARD") ? GZ_GUARD : 0;
+    const size_t guard = env_flag("PSK_GZ_GUARD") ? GZ_GUARD : 0;
     uint32_t guard_damage = 0;
     if (m) {
         PSK_TRY(dev_reserve(ctx, sym_buf, total * 2 + 64 + 2 * guard));
@@ -1783,7 +1785,7 @@ int gz_inflate_group(psk_ctx *ctx, int n, const uint8_t *const *data, const size
         PSK_HIP(ctx, hipGetLastError());
         const uint64_t *d_off = reinterpret_cast<const uint64_t *>(t + o_off), *d_len = reinterpret_cast<const uint64_t *>(t + o_want);
         unsigned long long *d_stats = nullptr;
-        if (std::getenv("PSK_GZ_STATS")) {
+        if (env_flag("PSK_GZ_STATS")) {
             PSK_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&d_stats), 64));
             PSK_HIP(ctx, hipMemsetAsync(d_stats, 0, 64, st));
         }
@@ -1812,7 +1814,7 @@ int gz_inflate_group(psk_ctx *ctx, int n, const uint8_t *const *data, const size
         std::vector<uint32_t> crc_got(m_begin.size(), 0);
         if (m_begin.size() != m_len.size() || m_len.size() != m_crc.size())
             return psk_fail(ctx, PSK_ESTATE, "gz inflate: %zu member starts, %zu member ends (internal error)", m_begin.size(), m_len.size());
-        const bool check_crc = !m_begin.empty() && !std::getenv("PSK_GZ_NO_CRC");
+        const bool check_crc = !m_begin.empty() && !env_flag("PSK_GZ_NO_CRC");
         if (check_crc) {
             const size_t nm = m_begin.size();
             uint8_t *mt = tab_buf.as<uint8_t>() + o_members;
@@ -1883,14 +1885,14 @@ void gz_release_device(psk_ctx *ctx)
         dev_bytes += b->cap;
         dev_release(*b);
     }
-    if (dev_bytes && std::getenv("PSK_TRACE"))
+    if (dev_bytes && env_flag("PSK_TRACE"))
         std::fprintf(stderr, "[psk] gz release: %.1f GB of device buffers in %.1f ms\n", dev_bytes / 1e9,
                      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
 }
 
 void gz_release_host(psk_ctx *ctx, bool wait)
 {
-    const bool trace = std::getenv("PSK_TRACE") != nullptr;
+    const bool trace = env_flag("PSK_TRACE");
     {
         const auto m0 = std::chrono::steady_clock::now();
         size_t bytes = 0;

@@ -531,17 +531,8 @@ static int frame_into(uint8_t *stage, size_t stage_cap, const uint8_t *bytes, si
 //     are uploaded and framed ahead on their own streams;
 //   groups of G = 8 genomes per chain (k <= 16, r03): 3 G buffer sets, a group's uploads and framing run ahead, one
 //     launch chain counts the group (dense_group_enqueue / bucket_group_enqueue), the group before it is finalised meanwhile.
-// uploads rotate over two copy streams (PSK_COPY_STREAMS = 1..4): with one, the next copy is only queued when the
-// previous one has gone -- 256 genomes took 38-40 ms, with two 33-36 (r03; a stream per buffer set: set index mod streams)
-static int copy_stream_count()
-{
-    static const int n_cs = [] {
-        const char *e = getenv("PSK_COPY_STREAMS");
-        const int v = e ? atoi(e) : 2;
-        return v < 1 ? 1 : (v > 4 ? 4 : v);
-    }();
-    return n_cs;
-}
+// uploads rotate over two copy streams (ctx->copy_streams, PSK_COPY_STREAMS = 1..4): with one, the next copy is only queued
+// when the previous one has gone -- 256 genomes took 38-40 ms, with two 33-36 (r03; a stream per buffer set: set index mod streams)
 
 static int lane_prepare(psk_ctx *ctx, CountLane &L)
 {
@@ -558,7 +549,7 @@ static int lane_prepare(psk_ctx *ctx, CountLane &L)
         // the 55 ms of a process's first counting call (r04, PSK_TRACE).  Only the copy streams in use now, and together
         std::vector<hipStream_t *> want;
         if (!ctx->copy_stream) want.push_back(&ctx->copy_stream);
-        for (int c = 0; c + 1 < copy_stream_count() && c < 3; c++) if (!ctx->copy_more[c]) want.push_back(&ctx->copy_more[c]);
+        for (int c = 0; c + 1 < ctx->copy_streams && c < 3; c++) if (!ctx->copy_more[c]) want.push_back(&ctx->copy_more[c]);
         if (!ctx->frame_stream) want.push_back(&ctx->frame_stream);
         std::vector<hipError_t> err(want.size(), hipSuccess);
         std::vector<std::thread> th;
@@ -667,7 +658,7 @@ static int chain_upload(psk_ctx *ctx, CountLane &L, const uint8_t *src, uint64_t
     PSK_TRY(lane_prepare(ctx, L));
     if (bytes == 0) return PSK_OK;
     if (bytes >= (1ull << 32)) return psk_fail(ctx, PSK_ERANGE, "sample larger than 4 GB");
-    const int which = (int)((&L - ctx->lane) % copy_stream_count());
+    const int which = (int)((&L - ctx->lane) % ctx->copy_streams);
     hipStream_t cs = which ? ctx->copy_more[which - 1] : ctx->copy_stream;
     // after the last reader of this set's clean stream (the sample before last)
     if (L.raw_used) PSK_HIP(ctx, hipStreamWaitEvent(cs, L.raw_free, 0));
@@ -999,8 +990,9 @@ static int count_batch_core(psk_ctx *ctx, int first_sample_idx, int n, const uin
     // pinned ring: at most ~4 GiB of it (read-scale FASTQ samples are hundreds of MB each)
     while (n_threads > 1 && (size_t)(n_threads + 4) * max_len > (4ull << 30)) n_threads--;
     // genomes at k <= 13 (dense counting) go through the counting kernels in groups of G: one launch chain per group
-    const bool bucket_run = !ctx->dense_mode && ctx->k >= 14 && ctx->k <= 32 && !getenv("PSK_NO_BUCKET_SORT");
-    int G = (!consumer && (ctx->dense_mode || bucket_run) && n > 1 && max_len < (64u << 20)) ? dense_group_size() : 1;
+    const bool bucket_run = !ctx->dense_mode && ctx->k >= 14 && ctx->k <= 32 && !env_flag("PSK_NO_BUCKET_SORT");
+    int G = 1;
+    if (!consumer && (ctx->dense_mode || bucket_run) && n > 1 && max_len < (64u << 20)) PSK_TRY(dense_group_size(ctx, &G));
     if (G > 1) {
         // The 3 G buffer sets of a grouped batch are one slab sized for the batch's longest sample: ~16 bytes per base on the
         // bucketed route -- 1.8 GB for 5-Mbp genomes, but 23 GB for samples just under the 64-MB grouping limit.
@@ -1032,7 +1024,7 @@ static int count_batch_core(psk_ctx *ctx, int first_sample_idx, int n, const uin
     const size_t slot_need = any_host ? max_host_len + 2 * EX_SEG : 0;
     // FASTA and four-line FASTQ are framed on the GPU (frame_gpu.hip): the worker threads then only move file bytes
     // into pinned memory.  PSK_HOST_FRAMING=1 keeps the host state machine for everything (A/B runs, tests).
-    const bool gpu_framing = getenv("PSK_HOST_FRAMING") == nullptr;
+    const bool gpu_framing = !env_flag("PSK_HOST_FRAMING");
 
     std::mutex mu;
     std::condition_variable cv;
@@ -1045,7 +1037,7 @@ static int count_batch_core(psk_ctx *ctx, int first_sample_idx, int n, const uin
     std::atomic<int> next(0);
     const int k = consumer ? k_window : ctx->k;
     // PSK_TRACE: where the calling thread waits (stderr, one line per call)
-    const bool trace = getenv("PSK_TRACE") != nullptr;
+    const bool trace = env_flag("PSK_TRACE");
     double t_worker = 0, t_frame = 0, t_final = 0;
     std::atomic<long long> t_fill_us(0);
     const auto t_call = std::chrono::steady_clock::now();
@@ -1171,7 +1163,7 @@ static int count_batch_core(psk_ctx *ctx, int first_sample_idx, int n, const uin
             PSK_HIP(ctx, hipEventSynchronize(L.raw_ready));   // the GPU is busy with the chain of sample i - 1 meanwhile
             t_frame += since(t0);
             const uint64_t *res = lane_frame_result(L);
-            if (fmt[i] == 2 && res[1] && getenv("PSK_HOST_WRAPPED_FASTQ")) {
+            if (fmt[i] == 2 && res[1] && env_flag("PSK_HOST_WRAPPED_FASTQ")) {
                 // (r05's route, kept as the A/B knob: the host state machine frames a FASTQ sample that is not four-line FASTQ)
                 PSK_TRY(ensure_pinned(ctx, &ctx->pinned, &ctx->pinned_cap, rlen[i] + 2 * EX_SEG));
                 uint64_t c = 0, p = 0, w = 0;
@@ -1193,7 +1185,7 @@ static int count_batch_core(psk_ctx *ctx, int first_sample_idx, int n, const uin
                 // not four-line FASTQ (records over several lines, blank lines between them): framed again, on the device, by the
                 // scan of line kinds (frame_gpu.hip, format 3; r06 -- until then the host's state machine took such a sample); the
                 // raw bytes are still in the lane's input buffer
-                if (getenv("PSK_TRACE"))
+                if (env_flag("PSK_TRACE"))
                     fprintf(stderr, "[psk] sample %d: FASTQ, but not four lines a record: framed on the device by the scan of line kinds\n", first_sample_idx + i);
                 PSK_TRY(frame_gpu_enqueue(ctx, ctx->frame_stream, 3, L.rawin.as<uint8_t>(), rlen[i], L.raw.as<uint8_t>(), L.fr_scratch.p, lane_frame_result(L)));
                 PSK_HIP(ctx, hipEventRecord(L.raw_ready, ctx->frame_stream));
@@ -1352,7 +1344,7 @@ static int count_batch_impl(psk_ctx *ctx, int first_sample_idx, int n, const uin
                                 n_threads, sketch_k, sketch_size, sketch_seed, hashes_out ? hashes_out + (size_t)lo * sketch_size : nullptr,
                                 n_hashes_out ? n_hashes_out + lo : nullptr, k_window, consumer, g);
     };
-    if (!ctx || n <= 0 || (!bytes && !paths) || !lens || getenv("PSK_NO_GPU_GZ")) return core(0, n, bytes, paths, lens, nullptr);
+    if (!ctx || n <= 0 || (!bytes && !paths) || !lens || env_flag("PSK_NO_GPU_GZ")) return core(0, n, bytes, paths, lens, nullptr);
     std::vector<char> is_gz((size_t)n, 0);
     bool any = false;
     for (int i = 0; i < n; i++) {
@@ -1375,10 +1367,10 @@ static int count_batch_impl(psk_ctx *ctx, int first_sample_idx, int n, const uin
     PSK_HIP(ctx, hipSetDevice(ctx->device));
     if (!ctx->gz_stream) PSK_HIP(ctx, hipStreamCreateWithFlags(&ctx->gz_stream, hipStreamNonBlocking));
     if (!ctx->gz_up_stream) PSK_HIP(ctx, hipStreamCreateWithFlags(&ctx->gz_up_stream, hipStreamNonBlocking));
-    const char *gm = getenv("PSK_GZ_GROUP_MB");
-    const size_t budget = (size_t)(gm && *gm ? strtoull(gm, nullptr, 10) : 8192) << 20;
-    const bool host_only = getenv("PSK_HOST_FRAMING") != nullptr;   // (the A/B knob of the host's state machine: the host's inflate with it)
-    const bool trace = getenv("PSK_TRACE") != nullptr;
+    size_t budget_mb = 8192;
+    PSK_TRY(env_int(ctx, "PSK_GZ_GROUP_MB", 0, 1 << 30, &budget_mb));
+    const bool host_only = env_flag("PSK_HOST_FRAMING");   // (the A/B knob of the host's state machine: the host's inflate with it)
+    const bool trace = env_flag("PSK_TRACE");
     std::vector<uint8_t *> held((size_t)n, nullptr);   // where the compressed image of a .gz FILE is (a slice of ctx->gz_host[set])
     std::vector<const uint8_t *> eb((size_t)n, nullptr);
     std::vector<const char *> ep((size_t)n, nullptr);
@@ -1422,7 +1414,7 @@ static int count_batch_impl(psk_ctx *ctx, int first_sample_idx, int n, const uin
                 e = isize_of(r.hi);
                 if (e < 3 * lens[r.hi]) e = 3 * lens[r.hi];
             }
-            if (r.hi > lo && est + e > budget) break;
+            if (r.hi > lo && est + e > (budget_mb << 20)) break;
             est += e;
             if (is_gz[(size_t)r.hi]) r.idx.push_back(r.hi);
             r.hi++;
@@ -1437,7 +1429,7 @@ static int count_batch_impl(psk_ctx *ctx, int first_sample_idx, int n, const uin
         // of such buffers back cost psk_build_presence 0.5 s of cfg5gz's 2.3 s (on a helper thread the same half second was spent by
         // whoever next touched the address space); an unmapped file gives no page back.  PSK_GZ_READ=1: r05's buffers (and what a
         // file that cannot be mapped gets).
-        const bool map_files = !getenv("PSK_GZ_READ");
+        const bool map_files = !env_flag("PSK_GZ_READ");
         std::vector<std::pair<void *, size_t>> &maps = ctx->gz_maps[r.set];
         for (auto &m : maps) munmap(m.first, m.second);   // (the run before last of this set: inflated and counted)
         maps.clear();
@@ -1527,7 +1519,7 @@ static int count_batch_impl(psk_ctx *ctx, int first_sample_idx, int n, const uin
         PSK_HIP(ctx, hipSetDevice(ctx->device));
         r.t0 = std::chrono::steady_clock::now();
         for (int i : r.idx) r.sizes.push_back(lens[i]);
-        r.on_device = gz_group_on_device((int)r.idx.size(), r.sizes.data(), host_only, n_threads);
+        PSK_TRY(gz_group_on_device(ctx, (int)r.idx.size(), r.sizes.data(), host_only, n_threads, &r.on_device));
         r.at.resize(r.idx.size());
         if (r.on_device) {
             const uint64_t total = gz_image_layout((int)r.idx.size(), r.sizes.data(), r.at.data());
@@ -1613,7 +1605,7 @@ static int count_batch_impl(psk_ctx *ctx, int first_sample_idx, int n, const uin
     }
     const int R = (int)runs.size();
     const auto t_all = std::chrono::steady_clock::now();
-    if (R == 1 || getenv("PSK_GZ_NO_LOOKAHEAD")) {
+    if (R == 1 || env_flag("PSK_GZ_NO_LOOKAHEAD")) {
         for (Run &r : runs) {
             PSK_TRY(stage_read(r));
             PSK_TRY(stage_inflate(r));

@@ -798,26 +798,20 @@ extern "C" int psk_nj_merges(psk_ctx *ctx, const double *dist, int n, int32_t *m
     int32_t *mi = reinterpret_cast<int32_t *>(last + 1), *mj = mi + n;
     PSK_HIP(ctx, hipMemcpyAsync(D, dist, nn * 8, hipMemcpyHostToDevice, ctx->stream));
     // (PSK_NJ_ONE_WG=1: the one-workgroup kernel, the A/B and the cross-check of the tests)
-    const char *one = getenv("PSK_NJ_ONE_WG");
+    const bool one_wg = env_flag("PSK_NJ_ONE_WG"), grid_knob = env_flag("PSK_NJ_GRID");
     bool grid_done = false;
     // (below 512 leaves the one workgroup is the faster one: 4 ms against 7 at 256 -- a join costs the grid ~25 us of
     // exchanges whatever its size; 1,024 leaves: 67 against 92 ms, 2,048: 240 against 645)
     // (r04) the matrix in LDS, a workgroup per C columns: from PSK_NJ_LDS_MIN leaves on (default 288: below, the one workgroup is as fast -- 256 leaves 4.1 ms either way) while a workgroup per
     // slice fits the compute units; PSK_NJ_LDS=0 switches it off
-    const bool one_wg = one && *one && strcmp(one, "0") != 0;
-    const char *lds_knob = getenv("PSK_NJ_LDS"), *lds_min = getenv("PSK_NJ_LDS_MIN");
-    int lds_from = 288;
-    if (lds_min && *lds_min) {   // (a knob of the tests: a whole number of leaves, 3 ... NJ_MAX)
-        char *end = nullptr;
-        const long v = strtol(lds_min, &end, 10);
-        if (*end || v < 3 || v > NJ_MAX) return psk_fail(ctx, PSK_EINVAL, "PSK_NJ_LDS_MIN=%s: expected a number of leaves, 3 ... %d", lds_min, NJ_MAX);
-        lds_from = (int)v;
-    }
+    int lds_on = 1, lds_from = 288;
+    PSK_TRY(env_choice(ctx, "PSK_NJ_LDS", {0, 1}, &lds_on));
+    PSK_TRY(env_int(ctx, "PSK_NJ_LDS_MIN", 3, NJ_MAX, &lds_from));   // (a knob of the tests: a number of leaves)
     const int n_pad = (n + 31) & ~31;
     int lgC = 6;
     while (lgC > 3 && (size_t)n_pad * 8 * (1u << lgC) > NJL_SLICE_BYTES) lgC--;
     const int nwg_l = (n + (1 << lgC) - 1) >> lgC;
-    if (!one_wg && !(lds_knob && strcmp(lds_knob, "0") == 0) && !getenv("PSK_NJ_GRID") && n >= lds_from &&
+    if (!one_wg && lds_on && !grid_knob && n >= lds_from &&
         n <= NJL_MAXN && nwg_l <= NJL_T && nwg_l <= (ctx->n_cu > 0 ? ctx->n_cu : 256)) {
         const size_t xbytes = sizeof(NjlShared) + 2 * (size_t)n * sizeof(NjlX) + (size_t)nwg_l * sizeof(NjlCandX);
         PSK_TRY(dev_reserve(ctx, ctx->keysB, xbytes));
@@ -842,9 +836,9 @@ extern "C" int psk_nj_merges(psk_ctx *ctx, const double *dist, int n, int32_t *m
         PSK_HIP(ctx, hipMemcpyAsync(&fail, &sh->fail, 4, hipMemcpyDeviceToHost, ctx->stream));
         PSK_HIP(ctx, hipStreamSynchronize(ctx->stream));
         grid_done = fail == 0;   // (the matrix itself is untouched: the slices live in LDS)
-        if (getenv("PSK_TRACE")) fprintf(stderr, "psk_nj_merges: %d leaves in LDS, %d workgroups of %d columns: %s\n", n, nwg_l, 1 << lgC, grid_done ? "done" : "gave up (a workgroup never arrived)");
+        if (env_flag("PSK_TRACE")) fprintf(stderr, "psk_nj_merges: %d leaves in LDS, %d workgroups of %d columns: %s\n", n, nwg_l, 1 << lgC, grid_done ? "done" : "gave up (a workgroup never arrived)");
     }
-    if (!grid_done && !one_wg && (n >= 512 || getenv("PSK_NJ_GRID"))) {
+    if (!grid_done && !one_wg && (n >= 512 || grid_knob)) {
         const int nwg = (n + NJG_T - 1) / NJG_T;
         PSK_TRY(dev_reserve(ctx, ctx->keysB, sizeof(NjgShared)));
         NjgShared *sh = ctx->keysB.as<NjgShared>();
@@ -855,7 +849,7 @@ extern "C" int psk_nj_merges(psk_ctx *ctx, const double *dist, int n, int32_t *m
         PSK_HIP(ctx, hipMemcpyAsync(&fail, &sh->fail, 4, hipMemcpyDeviceToHost, ctx->stream));
         PSK_HIP(ctx, hipStreamSynchronize(ctx->stream));
         grid_done = fail == 0;
-        if (getenv("PSK_TRACE")) fprintf(stderr, "psk_nj_merges: %d leaves on %d workgroups: %s\n", n, nwg, grid_done ? "done" : "gave up (a workgroup never arrived): one workgroup");
+        if (env_flag("PSK_TRACE")) fprintf(stderr, "psk_nj_merges: %d leaves on %d workgroups: %s\n", n, nwg, grid_done ? "done" : "gave up (a workgroup never arrived): one workgroup");
         // (one of its workgroups never arrived: the matrix may be half-joined -- again)
         if (!grid_done) PSK_HIP(ctx, hipMemcpyAsync(D, dist, nn * 8, hipMemcpyHostToDevice, ctx->stream));
     }

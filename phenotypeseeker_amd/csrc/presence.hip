@@ -16,7 +16,7 @@ struct PhaseTimer {
     bool on;
     hipStream_t st;
     std::chrono::steady_clock::time_point t0;
-    explicit PhaseTimer(hipStream_t s) : on(getenv("PSK_TRACE") != nullptr), st(s), t0(std::chrono::steady_clock::now()) {}
+    explicit PhaseTimer(hipStream_t s) : on(env_flag("PSK_TRACE")), st(s), t0(std::chrono::steady_clock::now()) {}
     void mark(const char *what)
     {
         if (!on) return;
@@ -308,7 +308,7 @@ static int build_presence_impl(psk_ctx *ctx, uint64_t *n_kmers)
     // a chunk of a sorted list is a contiguous range of it), each sorted on its own.  One chunk: one pass.  Several:
     // a first pass counts the rows of every chunk, the matrix is allocated once, a second pass fills it.
     uint64_t pair_chunk = 1ull << 30;
-    if (const char *e = getenv("PSK_PAIR_CHUNK")) { const uint64_t v = strtoull(e, nullptr, 10); if (v >= 1024) pair_chunk = v; }
+    PSK_TRY(env_int(ctx, "PSK_PAIR_CHUNK", 1024, INT64_MAX, &pair_chunk));
     if (pair_chunk >= (1ull << 32)) pair_chunk = (1ull << 32) - 1;
     const int ns = ctx->n_samples;
     std::vector<uint64_t> cut;  // cut[c * ns + i]: first entry of sample i's list that belongs to chunk c; n_chunks + 1 rows

@@ -105,7 +105,7 @@ int compact_encode(psk_ctx *ctx)
     ctx->cx_valid = false;
     const uint64_t M = ctx->n_kmers;
     const int n = ctx->n_samples, wpr = ctx->wpr;
-    const bool trace = getenv("PSK_TRACE") != nullptr;
+    const bool trace = env_flag("PSK_TRACE");
     if (n < CX_MIN_SAMPLES || n > CX_MAX_SAMPLES || M == 0 || M > 0xffffffffull || (wpr != 2 && wpr != 4)) {
         compact_release(ctx);
         return PSK_OK;

@@ -162,7 +162,7 @@ __global__ __launch_bounds__(PD_THREADS) void pd_transpose_kernel(const uint64_t
 int build_presence_dense(psk_ctx *ctx, uint64_t *n_kmers, int *done)
 {
     *done = 0;
-    if (!ctx->dense_mode || getenv("PSK_NO_DENSE_PRESENCE")) return PSK_OK;
+    if (!ctx->dense_mode || env_flag("PSK_NO_DENSE_PRESENCE")) return PSK_OK;
     const int n = ctx->n_samples;
     for (int i = 0; i < n; i++)
         if (!ctx->lists[i].dense || !ctx->lists[i].bitmap) return PSK_OK;   // installed lists (exchange): the list routes

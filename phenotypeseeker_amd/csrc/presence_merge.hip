@@ -667,14 +667,27 @@ __global__ void pm_pilot_kernel(const PmList *__restrict__ lists, const int32_t 
     out[g] = v;
 }
 
+// The knobs of both merge builds, read per build (tests cross them in one process).  0: the build's own choice; rec_div_set:
+// the knob asks for records explicitly; rec_region: chunks per pool region (tests: a region too small on purpose)
+struct MergeKnobs { uint64_t tile_pairs = 8192, ranges = 0, rec_div = 0, rec_region = 0; bool rec_div_set = false; };
+int merge_knobs(psk_ctx *ctx, MergeKnobs *kn)
+{
+    PSK_TRY(env_int(ctx, "PSK_MERGE_TILE_PAIRS", 64, INT64_MAX, &kn->tile_pairs));
+    PSK_TRY(env_int(ctx, "PSK_MERGE_RANGES", 1, INT64_MAX, &kn->ranges));
+    PSK_TRY(env_int(ctx, "PSK_MERGE_REC_DIV", 0, INT64_MAX, &kn->rec_div, &kn->rec_div_set));
+    PSK_TRY(env_int(ctx, "PSK_MERGE_REC_REGION", 1, (1 << 26) - 1, &kn->rec_region));
+    kn->rec_region = (kn->rec_region + PM_REC_BLOCK - 1) & ~(uint64_t)(PM_REC_BLOCK - 1);
+    return PSK_OK;
+}
+
 }  // namespace
 
 // Returns PSK_OK and sets *done = 1 when the merge build ran; *done = 0: not eligible, the caller takes the sort route.
 int build_presence_merge(psk_ctx *ctx, uint64_t total_pairs, uint64_t *n_kmers, int *done)
 {
     *done = 0;
-    if (getenv("PSK_NO_MERGE_PRESENCE")) return PSK_OK;
-    const bool trace = getenv("PSK_TRACE") != nullptr;
+    if (env_flag("PSK_NO_MERGE_PRESENCE")) return PSK_OK;
+    const bool trace = env_flag("PSK_TRACE");
     auto t_prev = std::chrono::steady_clock::now();
     auto mark = [&](const char *what) {   // PSK_TRACE: host-side phase times (each mark waits for the stream)
         if (!trace) return;
@@ -696,10 +709,10 @@ int build_presence_merge(psk_ctx *ctx, uint64_t total_pairs, uint64_t *n_kmers, 
     if (total_pairs >= (1ull << 32) && span / 2 + (1ull << k) >= (1ull << 32)) return PSK_OK;
     for (int i = 0; i < n; i++)
         if (ctx->lists[i].n_unique >= (1ull << 32)) return PSK_OK;
+    MergeKnobs kn;
+    PSK_TRY(merge_knobs(ctx, &kn));
     // ---- tile bounds: pair quantiles of a pilot, no tile wider than PM_BMW bitmap words ------------------------------
-    uint64_t pairs_per_tile = 8192;
-    if (const char *e = getenv("PSK_MERGE_TILE_PAIRS")) { const uint64_t v = strtoull(e, nullptr, 10); if (v >= 64) pairs_per_tile = v; }
-    uint64_t want = (total_pairs + pairs_per_tile - 1) / pairs_per_tile;
+    uint64_t want = (total_pairs + kn.tile_pairs - 1) / kn.tile_pairs;
     if (want < 1) want = 1;
     if (want > (1ull << 24)) want = 1ull << 24;
     const int n_pick = n < 64 ? n : 64;
@@ -758,7 +771,7 @@ int build_presence_merge(psk_ctx *ctx, uint64_t total_pairs, uint64_t *n_kmers, 
     const int n_groups = (n + PM_GROUP - 1) / PM_GROUP;
     const int threads = n >= PM_GROUP ? PM_GROUP : ((n + 63) / 64) * 64;
     uint64_t n_ranges = ((uint64_t)(ctx->n_cu > 0 ? ctx->n_cu : 256) * 8 * (PM_GROUP / threads)) / n_groups;
-    if (const char *e = getenv("PSK_MERGE_RANGES")) { const uint64_t v = strtoull(e, nullptr, 10); if (v >= 1) n_ranges = v; }
+    if (kn.ranges) n_ranges = kn.ranges;
     if (n_ranges > n_tiles) n_ranges = n_tiles;
     if (n_ranges < 1) n_ranges = 1;
     const uint32_t tiles_per_range = (uint32_t)((n_tiles + n_ranges - 1) / n_ranges);
@@ -789,25 +802,16 @@ int build_presence_merge(psk_ctx *ctx, uint64_t total_pairs, uint64_t *n_kmers, 
     // records of pass 1 for pass 2 (PmRec): a pool of pairs / PSK_MERGE_REC_DIV records (default 12; 0: none, pass 2 merges)
     PmRec rec = {nullptr, nullptr, nullptr, nullptr, 0};   // (region_chunks = 0: no records)
     {
-        uint64_t div = 12;
-        if (const char *e = getenv("PSK_MERGE_REC_DIV")) {
-            char *end = nullptr;
-            div = strtoull(e, &end, 10);
-            if (!*e || *end) return psk_fail(ctx, PSK_EINVAL, "PSK_MERGE_REC_DIV=%s: expected a whole number (0 = no records)", e);
-        }
         // The pool has a fixed part -- every wave's claims, whatever it holds -- of about a gigabyte: a build of a few million
         // pairs gains nothing from records (its merging pass 2 takes microseconds) and is spared that reservation, unless the
         // knob asks for records explicitly (tests of the replay on small sets)
-        if (div && total_pairs < (16ull << 20) && !getenv("PSK_MERGE_REC_DIV")) div = 0;
+        const uint64_t div = kn.rec_div_set ? kn.rec_div : total_pairs < (16ull << 20) ? 0 : 12;
         if (div) {
             // + every wave's claims under way (two) and the one it ends in; a region takes what the ranges that map to it need:
             // half as much again for their imbalance
             uint64_t chunks = total_pairs / div / 64 + 3 * PM_REC_BLOCK * (uint64_t)n_ranges * n_groups * (threads / 64);
             uint64_t region_chunks = ((chunks + chunks / 2) / PM_REC_REGIONS + PM_REC_BLOCK) & ~(uint64_t)(PM_REC_BLOCK - 1);
-            if (const char *e = getenv("PSK_MERGE_REC_REGION")) {   // (tests: a region too small on purpose)
-                const uint64_t v = strtoull(e, nullptr, 10);
-                if (v >= 1 && v < (1ull << 26)) region_chunks = (v + PM_REC_BLOCK - 1) & ~(uint64_t)(PM_REC_BLOCK - 1);
-            }
+            if (kn.rec_region) region_chunks = kn.rec_region;
             chunks = region_chunks * PM_REC_REGIONS;
             if (chunks < (1ull << 31)) {
                 const size_t wbytes = w32 ? 4 : 8, ctr_bytes = (size_t)(PM_REC_REGIONS + 1) * PM_REC_CTR_STRIDE * 4;
@@ -875,8 +879,10 @@ int build_presence_merge(psk_ctx *ctx, uint64_t total_pairs, uint64_t *n_kmers, 
         uint32_t r_cap = (uint32_t)((PM_LDS_MAX - head) / ((size_t)cols0 * 8));
         {   // two workgroups per CU (78 KB each) whenever the bulk of the tiles -- the 99.5th percentile of their row counts, or
             // PSK_MERGE_RCAP_PCT -- fits a block of that size; the few wider tiles are streamed in batches
-            double pct = 0.995;
-            if (const char *pe = getenv("PSK_MERGE_RCAP_PCT")) { const double v = atof(pe); if (v > 0 && v <= 1) pct = v; }
+            double pct = 0;
+            PSK_TRY(env_real(ctx, "PSK_MERGE_RCAP_PCT", 0, 1, &pct));
+            const bool pct_set = pct > 0;
+            if (!pct_set) pct = 0.995;
             std::vector<uint32_t> sorted_rows(rows);
             const size_t q = (size_t)((double)(n_tiles - 1) * pct);
             std::nth_element(sorted_rows.begin(), sorted_rows.begin() + q, sorted_rows.end());
@@ -885,7 +891,7 @@ int build_presence_merge(psk_ctx *ctx, uint64_t total_pairs, uint64_t *n_kmers, 
             // (only a build whose fill kernel fits two workgroups per CU by its registers asks for it -- EXTRA="-DPSK_PM_BLOCK=4
             // -DPSK_PM_FILL_WGS=8": 57 VGPRs, a 32-KB ring; measured no faster than one workgroup with 64-byte blocks: fill 13.0
             // against 13.6 ms, mark 6.2 against 5.3)
-            if ((PSK_PM_FILL_WGS >= 8 || getenv("PSK_MERGE_RCAP_PCT")) && head + (size_t)cols0 * 8 * bulk <= two_per_cu)
+            if ((PSK_PM_FILL_WGS >= 8 || pct_set) && head + (size_t)cols0 * 8 * bulk <= two_per_cu)
                 r_cap = std::min<uint32_t>(r_cap, (uint32_t)((two_per_cu - head) / ((size_t)cols0 * 8)));
         }
         const uint32_t rb_max = rows_max < r_cap ? rows_max : r_cap;
@@ -910,9 +916,9 @@ int build_presence_merge(psk_ctx *ctx, uint64_t total_pairs, uint64_t *n_kmers, 
         (void)hipMemcpyToSymbol(HIP_SYMBOL(pm_stats), z, sizeof(z));
     }
 #endif
-    if (getenv("PSK_TRACE"))
+    if (trace)
         fprintf(stderr, "[psk] merge build: %u tiles (%llu pairs each wanted), %llu ranges x %d groups of %d threads, widest tile %u bitmap words, most rows %u\n",
-                n_tiles, (unsigned long long)pairs_per_tile, (unsigned long long)n_ranges, n_groups, threads, bmw_max, rows_max);
+                n_tiles, (unsigned long long)kn.tile_pairs, (unsigned long long)n_ranges, n_groups, threads, bmw_max, rows_max);
     *n_kmers = M;
     *done = 1;
     return PSK_OK;
@@ -928,8 +934,8 @@ int build_presence_merge(psk_ctx *ctx, uint64_t total_pairs, uint64_t *n_kmers, 
 int build_presence_merge_wide(psk_ctx *ctx, uint64_t total_pairs, uint64_t *n_kmers, int *done)
 {
     *done = 0;
-    if (getenv("PSK_NO_MERGE_PRESENCE") || getenv("PSK_NO_WIDE_MERGE")) return PSK_OK;
-    const bool trace = getenv("PSK_TRACE") != nullptr;
+    if (env_flag("PSK_NO_MERGE_PRESENCE") || env_flag("PSK_NO_WIDE_MERGE")) return PSK_OK;
+    const bool trace = env_flag("PSK_TRACE");
     auto t_prev = std::chrono::steady_clock::now();
     auto mark = [&](const char *what) {
         if (!trace) return;
@@ -945,10 +951,10 @@ int build_presence_merge_wide(psk_ctx *ctx, uint64_t total_pairs, uint64_t *n_km
     const uint64_t lo = ctx->slab_lo;
     const uint64_t hi = ctx->slab_hi ? ctx->slab_hi : (k == 32 ? ~0ull : (1ull << (2 * k)));   // exclusive; no canonical word is all ones
     if (hi <= lo) return PSK_OK;
+    MergeKnobs kn;
+    PSK_TRY(merge_knobs(ctx, &kn));
     // ---- tile bounds: pair quantiles of a pilot (they only cut the stream into ranges of work: no bitmap depends on them) ----
-    uint64_t pairs_per_tile = 8192;
-    if (const char *e = getenv("PSK_MERGE_TILE_PAIRS")) { const uint64_t v = strtoull(e, nullptr, 10); if (v >= 64) pairs_per_tile = v; }
-    uint64_t want = (total_pairs + pairs_per_tile - 1) / pairs_per_tile;
+    uint64_t want = (total_pairs + kn.tile_pairs - 1) / kn.tile_pairs;
     if (want < 1) want = 1;
     if (want > (1ull << 24)) want = 1ull << 24;
     const int n_pick = n < 64 ? n : 64;
@@ -994,7 +1000,7 @@ int build_presence_merge_wide(psk_ctx *ctx, uint64_t total_pairs, uint64_t *n_km
         n_groups = (n + gsz - 1) / gsz;
         threads = n >= gsz ? gsz : ((n + 63) / 64) * 64;
         n_ranges = ((uint64_t)(ctx->n_cu > 0 ? ctx->n_cu : 256) * 8 * (PM_GROUP / threads)) / n_groups;
-        if (const char *e = getenv("PSK_MERGE_RANGES")) { const uint64_t v = strtoull(e, nullptr, 10); if (v >= 1) n_ranges = v; }
+        if (kn.ranges) n_ranges = kn.ranges;
         if (n_ranges > n_tiles) n_ranges = n_tiles;
         if (n_ranges < 1) n_ranges = 1;
         tiles_per_range = (uint32_t)((n_tiles + n_ranges - 1) / n_ranges);
@@ -1006,7 +1012,7 @@ int build_presence_merge_wide(psk_ctx *ctx, uint64_t total_pairs, uint64_t *n_km
     // 64 KB of it per workgroup leave room for two workgroups on a CU.  Tiles are cut at pair quantiles of a pilot, so a few come out
     // many times wider than the rest: a tile wider than its share of a range's 2^32 is cut further, by value (a bound may be any
     // word value) -- unless that would more than double the tiles (a space as sparse as k = 31's: the 64-bit cursors are for it)
-    bool narrow = !getenv("PSK_WIDE_MERGE_64");
+    bool narrow = !env_flag("PSK_WIDE_MERGE_64");
     const uint64_t limit = 0xfffffffdull;
     uint64_t widest = 0;
     for (int round = 0; narrow && round < 4; round++) {
@@ -1034,7 +1040,7 @@ int build_presence_merge_wide(psk_ctx *ctx, uint64_t total_pairs, uint64_t *n_km
     if (trace) fprintf(stderr, "[psk]   wide merge: %u tiles, %u per range, widest range %llu word values\n", n_tiles, tiles_per_range, (unsigned long long)widest);
     if (!narrow) {
         int gsz = 512;
-        if (const char *e = getenv("PSK_WIDE_GROUP")) { const int v = atoi(e); if (v == 256 || v == 512 || v == 1024) gsz = v; }
+        PSK_TRY(env_choice(ctx, "PSK_WIDE_GROUP", {256, 512, 1024}, &gsz));
         shape(gsz);
     }
     PSK_TRY(dev_reserve(ctx, ctx->flags, 64 + (size_t)(n_tiles + 1) * 8 + 64));
@@ -1043,22 +1049,14 @@ int build_presence_merge_wide(psk_ctx *ctx, uint64_t total_pairs, uint64_t *n_km
     PSK_HIP(ctx, hipMemcpyAsync(d_bounds, bounds.data(), (size_t)(n_tiles + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
     // ---- the record pool: pairs / PSK_MERGE_REC_DIV records (default 12) + every wave's claims under way ------------------------
     // (a record stands for the samples of one wave that share a word: a few dozen samples cannot share twelve-fold)
-    uint64_t div = std::min<uint64_t>(12, std::max<uint64_t>(2, (uint64_t)n / 8));
-    if (const char *e = getenv("PSK_MERGE_REC_DIV")) {
-        char *end = nullptr;
-        div = strtoull(e, &end, 10);
-        if (!*e || *end) return psk_fail(ctx, PSK_EINVAL, "PSK_MERGE_REC_DIV=%s: expected a whole number (0 = no records)", e);
-    }
+    const uint64_t div = kn.rec_div_set ? kn.rec_div : std::min<uint64_t>(12, std::max<uint64_t>(2, (uint64_t)n / 8));
     if (div == 0) return PSK_OK;   // no records, no wide merge: the sort route
     uint64_t chunks = total_pairs / div / 64 + 3 * PM_REC_BLOCK * (uint64_t)n_ranges * n_groups * (threads / 64);
     // a workgroup's records all go to ONE region ((range + group) mod 16): with fewer workgroups than regions only that many
     // regions are ever used, and here -- unlike in the bitmap build, whose pass 2 can merge again -- an overflow costs the route
     const uint64_t regions_used = std::min<uint64_t>(PM_REC_REGIONS, n_ranges * (uint64_t)n_groups);
     uint64_t region_chunks = ((chunks + chunks / 2) / regions_used + PM_REC_BLOCK) & ~(uint64_t)(PM_REC_BLOCK - 1);
-    if (const char *e = getenv("PSK_MERGE_REC_REGION")) {
-        const uint64_t v = strtoull(e, nullptr, 10);
-        if (v >= 1 && v < (1ull << 26)) region_chunks = (v + PM_REC_BLOCK - 1) & ~(uint64_t)(PM_REC_BLOCK - 1);
-    }
+    if (kn.rec_region) region_chunks = kn.rec_region;
     chunks = region_chunks * PM_REC_REGIONS;
     if (chunks >= (1ull << 26)) return PSK_OK;          // records are numbered in u32: 64 x chunks < 2^32
     const size_t ctr_bytes = (size_t)(PM_REC_REGIONS + 1) * PM_REC_CTR_STRIDE * 4;

@@ -168,7 +168,7 @@ __global__ __launch_bounds__(PT_THREADS) void tile_fill_kernel(const ListRef *__
 int build_presence_tiled(psk_ctx *ctx, uint64_t total_pairs, uint64_t *n_kmers, int *done)
 {
     *done = 0;
-    if (getenv("PSK_NO_TILED_PRESENCE")) return PSK_OK;
+    if (env_flag("PSK_NO_TILED_PRESENCE")) return PSK_OK;
     const int k = ctx->k, n = ctx->n_samples, wpr = ctx->wpr;
     if (2 * k > 40) return PSK_OK;
     const uint64_t space = 1ull << (2 * k);
@@ -182,8 +182,9 @@ int build_presence_tiled(psk_ctx *ctx, uint64_t total_pairs, uint64_t *n_kmers, 
     // row is hundreds of bytes and a tile holds fewer rows than the workgroup has threads (down to 64)
     uint32_t R = 0;
     uint64_t n_tiles64 = 0;
-    const size_t forced = getenv("PSK_TILE_LDS_KB") ? (size_t)atoi(getenv("PSK_TILE_LDS_KB")) * 1024 : 0;
-    for (size_t lds_try = forced ? forced : PT_LDS_MAX; lds_try <= PT_LDS_MAX; lds_try *= 2) {
+    size_t forced = 0;   // KB
+    PSK_TRY(env_int(ctx, "PSK_TILE_LDS_KB", 1, PT_LDS_MAX / 1024, &forced));
+    for (size_t lds_try = forced ? forced * 1024 : PT_LDS_MAX; lds_try <= PT_LDS_MAX; lds_try *= 2) {
         uint32_t r = (uint32_t)(lds_try / ((size_t)wpr * 8 + 4));  // bit block + the 4-byte entry of the occupied-row list
         if (r < 64) { if (forced) break; continue; }  // not even 64 rows fit: too many samples for this block size
         uint32_t p2 = 64;

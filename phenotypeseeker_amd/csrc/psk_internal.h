@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <thread>
 #include <utility>
@@ -119,6 +120,9 @@ struct psk_ctx {
     uint64_t scan_seq = 0;
     std::string err;
     int n_cu = 0;
+    // knobs psk_init reads once per context: PSK_GRID_MULT (0: the build's PSK_SC_GRID_MULT), PSK_COPY_STREAMS, PSK_PINNED_CACHE_MB
+    int grid_mult = 0, copy_streams = 2;
+    size_t pinned_cache_mb = 1024;
 
     // run configuration
     int k = 0;
@@ -163,7 +167,7 @@ struct psk_ctx {
     CountLane lane[LANES];   // sample i runs on set i % 3: i + 1 and i + 2 are uploaded / framed ahead while chain i runs; in groups
                              // of G genomes (dense counting) on set i % (3 G): two groups ahead, one in flight
     hipStream_t copy_stream = nullptr;  // uploads of the batch counter overlap the previous sample's kernels
-    hipStream_t copy_more[3] = {nullptr, nullptr, nullptr};   // ... and rotate over up to four streams (PSK_COPY_STREAMS, default 2): a copy is queued while one runs
+    hipStream_t copy_more[3] = {nullptr, nullptr, nullptr};   // ... and rotate over up to four streams (copy_streams): a copy is queued while one runs
     hipStream_t frame_stream = nullptr; // the GPU framing of sample i + 1 runs beside upload i + 2 and chain i
     hipStream_t sketch_stream = nullptr;  // the one-workgroup sketch select runs beside the next sample's chain
 
@@ -214,6 +218,22 @@ void psk_forget_lane_slices(psk_ctx *ctx);   // kmer_count.hip
         if (rc_ != PSK_OK) return rc_; \
     } while (0)
 
+// ---- PSK_* environment knobs (api.hip; docs/KNOBS.md): the library's only reader of the environment -----------------
+// A flag is on when set to anything but "" or "0".  A value knob that is unset or "" leaves *out at the caller's default
+// (*set = false); any other value must parse whole and lie in range, else PSK_EINVAL with a message naming the variable.
+bool env_flag(const char *name);
+const char *env_str(const char *name);   // nullptr when unset or ""
+int env_int(psk_ctx *ctx, const char *name, int64_t lo, int64_t hi, int64_t *out, bool *set = nullptr);
+int env_choice(psk_ctx *ctx, const char *name, std::initializer_list<int> allowed, int *out);
+int env_real(psk_ctx *ctx, const char *name, double lo, double hi, double *out);   // in (lo, hi]
+template <class T> int env_int(psk_ctx *ctx, const char *name, int64_t lo, int64_t hi, T *out, bool *set = nullptr)
+{
+    int64_t v = (int64_t)*out;
+    PSK_TRY(env_int(ctx, name, lo, hi, &v, set));
+    *out = (T)v;
+    return PSK_OK;
+}
+
 // ---- exception-coded rows (presence_compact.hip) ----------------------------------------------------------------------
 // Slot of a row (u64, little endian): byte 0 = header -- bits 0..2 e, bit 3 "the exceptions are the ABSENT samples",
 // bit 4 overflow (e > CX_MAX_E: the row is in the side matrix) --, bytes 1..e = the exceptions' sample indices, ascending.
@@ -256,7 +276,7 @@ int gz_inflate_group(psk_ctx *ctx, int n, const uint8_t *const *data, const size
                      DevBuf &tab_buf, std::vector<GzInflated> &res, double *device_ms, bool host_only = false, int host_threads = 8,
                      hipStream_t on_stream = nullptr, bool images_uploaded = false);
 uint64_t gz_image_layout(int n, const size_t *sizes, uint64_t *at);
-bool gz_group_on_device(int n, const size_t *sizes, bool host_only, int host_threads);
+int gz_group_on_device(psk_ctx *ctx, int n, const size_t *sizes, bool host_only, int host_threads, bool *on);
 
 // r06: pinned host buffers outlive their context in a process-wide cache (api.hip).  Unpinning is slow -- the 20 slots of the batch
 // counter's ring cost psk_free 28 ms of a 0.59-s `phenotypeseeker modeling` process, and a second context of the process (bench.py's
@@ -307,7 +327,7 @@ void dense_configure(psk_ctx *ctx);        // psk_begin: decides dense_mode / de
 // n = its window count.  dense_chain_finalize (one sample later) places the multi-count entries in the arena.
 int dense_chain_enqueue(psk_ctx *ctx, CountLane &L, int sample_idx, uint64_t clean_len, uint64_t n);
 int dense_chain_finalize(psk_ctx *ctx, CountLane &L, uint64_t *n_kept, uint64_t *n_unique);
-int dense_group_size();   // samples per launch chain (PSK_DC_GROUP, default and at most 8)
+int dense_group_size(psk_ctx *ctx, int *G);   // samples per launch chain (PSK_DC_GROUP, default and at most 8)
 bool dense_group_ok(const psk_ctx *ctx, uint64_t n);
 int dense_group_enqueue(psk_ctx *ctx, CountLane *const *lanes, const int *sample_idx, const uint64_t *clean_len, const uint64_t *n,
                         int count);

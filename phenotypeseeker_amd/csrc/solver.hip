@@ -16,7 +16,6 @@
 // (DESIGN.md).  The host removes duplicated columns first (model.GridSearch): k-mers of one gene share
 // one presence pattern, and an L1 optimum may put a pattern's weight on any one of its copies.
 #include <algorithm>
-#include <cerrno>
 
 #include "solver_common.h"
 
@@ -584,29 +583,6 @@ int check_fit_args(psk_ctx *ctx, const void *X, const void *y, int n, int p, con
     return PSK_OK;
 }
 
-// The PSK_* variables that pick kernel forms (docs/KNOBS.md: A/B runs and tests): a flag counts when it is set to
-// anything but "" or "0"; an integer must parse completely and lie in its range -- atoi() made 0 of garbage and took any
-// number, and a forced register form narrower than the design or a negative CG count are reachable from a user's shell.
-bool env_flag(const char *name)
-{
-    const char *v = getenv(name);
-    return v && *v && strcmp(v, "0") != 0;
-}
-int env_int(psk_ctx *ctx, const char *name, long lo, long hi, bool *set, int *out)
-{
-    const char *v = getenv(name);
-    *set = false;
-    if (!v || !*v) return PSK_OK;
-    char *end = nullptr;
-    errno = 0;
-    const long x = strtol(v, &end, 10);
-    if (errno || end == v || *end != '\0' || x < lo || x > hi)
-        return psk_fail(ctx, PSK_EINVAL, "%s=%s: expected an integer in [%ld, %ld]", name, v, lo, hi);
-    *set = true;
-    *out = (int)x;
-    return PSK_OK;
-}
-
 }  // namespace
 
 #define SV_ALLOC(ptr, bytes) PSK_HIP(ctx, hipMalloc(&(ptr), (bytes) ? (bytes) : 8))
@@ -619,15 +595,14 @@ extern "C" int psk_logreg_l1_fit(psk_ctx *ctx, const float *X, const int32_t *y0
     // form knobs, validated before anything is allocated
     const bool knob_no_cd_regs = env_flag("PSK_NO_CD_REGS"), knob_no_gram = env_flag("PSK_NO_GRAM"),
                knob_no_gram_global = env_flag("PSK_NO_GRAM_GLOBAL");
-    bool set_min_p1 = false, set_wmreg = false, set_cg = false, set_reps = false, set_from = false;
+    bool set_min_p1 = false, set_reps = false;
     int knob_min_p1 = 0, knob_wmreg = 0, knob_cg_max = 16, knob_polish_reps = 0, knob_polish_from = 32;
-    PSK_TRY(env_int(ctx, "PSK_GG_MIN_P1", 1, 1 << 20, &set_min_p1, &knob_min_p1));
-    PSK_TRY(env_int(ctx, "PSK_FORCE_WMREG", 16, 64, &set_wmreg, &knob_wmreg));
-    PSK_TRY(env_int(ctx, "PSK_CG_MAX", 0, 256, &set_cg, &knob_cg_max));
-    PSK_TRY(env_int(ctx, "PSK_POLISH_REPS", -4096, 4096, &set_reps, &knob_polish_reps));
-    PSK_TRY(env_int(ctx, "PSK_GG_POLISH_FROM", 1, 1000, &set_from, &knob_polish_from));
-    if (set_wmreg && (knob_wmreg != 16 && knob_wmreg != 32 && knob_wmreg != 64))
-        return psk_fail(ctx, PSK_EINVAL, "PSK_FORCE_WMREG=%d: the register forms hold 16, 32 or 64 sample words", knob_wmreg);
+    PSK_TRY(env_int(ctx, "PSK_GG_MIN_P1", 1, 1 << 20, &knob_min_p1, &set_min_p1));
+    PSK_TRY(env_choice(ctx, "PSK_FORCE_WMREG", {16, 32, 64}, &knob_wmreg));   // (0: n picks the register form)
+    PSK_TRY(env_int(ctx, "PSK_CG_MAX", 0, 256, &knob_cg_max));
+    PSK_TRY(env_int(ctx, "PSK_POLISH_REPS", -4096, 4096, &knob_polish_reps, &set_reps));
+    PSK_TRY(env_int(ctx, "PSK_GG_POLISH_FROM", 1, 1000, &knob_polish_from));
+    const bool set_wmreg = knob_wmreg != 0;
     if (set_wmreg && knob_wmreg * 64 < n)
         return psk_fail(ctx, PSK_EINVAL, "PSK_FORCE_WMREG=%d holds %d samples, the design has %d", knob_wmreg, knob_wmreg * 64, n);
     PSK_HIP(ctx, hipSetDevice(ctx->device));

@@ -27,6 +27,7 @@ import time
 
 import numpy as np
 
+from ._lib import env_flag
 from .engine import PskContext
 
 
@@ -511,9 +512,9 @@ class HostFileTransport:
 def host_files_allowed():
     """The host-file fallback is OPT-IN: PSK_DIST_ALLOW_HOST_FILES=1, or PSK_SHARE_GPU=1 (ranks share GPUs, where RCCL
     cannot work at all).  PSK_DIST_STRICT=1 wins over both."""
-    if os.environ.get("PSK_DIST_STRICT") == "1":
+    if env_flag("PSK_DIST_STRICT"):
         return False
-    return os.environ.get("PSK_DIST_ALLOW_HOST_FILES") == "1" or os.environ.get("PSK_SHARE_GPU") == "1"
+    return env_flag("PSK_DIST_ALLOW_HOST_FILES") or env_flag("PSK_SHARE_GPU")
 
 
 def _exchange_status(d, prefix, rank, world, text, timeout=600.0, nonce=""):
@@ -627,7 +628,7 @@ class Group:
         if transport is None and spec:
             mod, _, name = spec.partition(":")
             cls = getattr(importlib.import_module(mod), name)      # before libpsk.so is opened (see the module's note)
-        if os.environ.get("PSK_SHARE_GPU") == "1":
+        if env_flag("PSK_SHARE_GPU"):
             from . import _lib
             self.device = self.local_rank % max(_lib.load().psk_device_count(), 1)
         if transport is None:

@@ -31,7 +31,7 @@ class PskContext:
         h = ctypes.c_void_p()
         rc = self._lib.psk_init(int(device), ctypes.byref(h))
         if rc != 0:
-            raise PskError("psk_init(%d) failed: %s" % (device, self._lib.psk_last_error(None).decode()))
+            raise PskError("psk_init(%d) failed: %s" % (device, self._lib.psk_last_error(None).decode()), code=rc)
         self._h = h
         self.device = device
         self.k = None

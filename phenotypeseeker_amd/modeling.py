@@ -116,7 +116,7 @@ class Samples:
         inflaters = max(n_threads, min(int(getattr(Input, "num_threads", n_threads) or n_threads), os.cpu_count() or n_threads))
         with ThreadPoolExecutor(max_workers=inflaters) as pool:
             # (two bytes per file, read here: through the pool the 1,024 futures of a 1,024-genome run cost 45 ms, the reads 10)
-            host_inflate = bool(os.environ.get("PSK_NO_GPU_GZ"))
+            host_inflate = _lib.env_flag("PSK_NO_GPU_GZ")
             zipped = [host_inflate and (s.address.endswith(".gz") or formats.is_gzip(s.address)) for s in samples]
             # (plain files never sit in this process's memory -- the library streams them through its pinned ring --, so
             # their calls grow to 512 samples: a call ends with its pipeline drained, ~3 ms each at 64 samples per call, 60 ms
@@ -736,7 +736,7 @@ class phenotypes:
         # (scikit-learn-free) classes, which is also what is written when scikit-learn is missing.
         package.update({"pca": self.pca, "pred_scale": self.pred_scale})
         blob = None
-        if os.environ.get("PSK_NATIVE_PKL") != "1":
+        if not _lib.env_flag("PSK_NATIVE_PKL"):
             from . import skpickle
             shell = self.model_fitted.to_sklearn_shell()          # no scikit-learn import (skpickle.py)
             if shell is not None:

@@ -2,7 +2,6 @@
 prediction.py; line numbers cite it).  The `gmer_counter -db` subprocess per sample (:72-80) is
 replaced by psk_count_dict; the k-mer text database and the per-sample count files are never
 written.  The model file is the reference's joblib dict {'model', 'kmers', 'pca', 'pred_scale'}."""
-import os
 import sys
 import time
 from collections import OrderedDict
@@ -10,7 +9,7 @@ from collections import OrderedDict
 import numpy as np
 
 from . import formats
-from ._lib import PSK_EGZIP, PskError
+from ._lib import PSK_EGZIP, PskError, env_flag
 from .engine import PskContext
 
 
@@ -45,7 +44,7 @@ class Samples:
         counts = None
         # .gz files go to the library as they are (r05: it inflates them, on the GPU when there is enough of them); with
         # PSK_NO_GPU_GZ=1 they are recognised here by their magic bytes (the suffix alone is not trusted) and inflated here
-        zipped = bool(os.environ.get("PSK_NO_GPU_GZ")) and any(p.endswith(".gz") or formats.is_gzip(p) for p in paths)
+        zipped = env_flag("PSK_NO_GPU_GZ") and any(p.endswith(".gz") or formats.is_gzip(p) for p in paths)
         if not zipped:
             try:
                 counts = ctx.count_dict_files(paths, pheno.k, pheno.words, n_threads)
@@ -79,7 +78,7 @@ class Phenotypes:
         name, path = line.split()[0], line.split()[1]
         # a plain pickle of a linear model (what `modeling` writes) is read without importing joblib / scikit-learn
         # (0.5-2 s of a run that otherwise takes half a second); anything else goes through joblib.load as in the reference
-        pkg = None if os.environ.get("PSK_JOBLIB_LOAD") else skpickle.load_linear_package(path)
+        pkg = None if env_flag("PSK_JOBLIB_LOAD") else skpickle.load_linear_package(path)
         if pkg is None:
             import joblib
             pkg = joblib.load(path)

@@ -1396,16 +1396,18 @@ def test_sort_route_in_word_range_chunks(ctx, oracle, k, n, length, chunk, monke
 @pytest.mark.parametrize("k,n,length,env", [
     (16, 40, 30_000, {}),                                                    # one wave, default tiles
     (16, 70, 20_000, {"PSK_MERGE_TILE_PAIRS": "64"}),                        # two waves, thousands of tiny tiles
-    (14, 130, 9_000, {"PSK_MERGE_RCAP": "7", "PSK_MERGE_TILE_PAIRS": "500"}),  # padded column; tiles streamed in batches of 7 rows
+    (14, 130, 9_000, {"PSK_MERGE_RCAP_PCT": "0.5", "PSK_MERGE_TILE_PAIRS": "500"}),  # padded column; block sized for two workgroups a CU
     (15, 1100, 3_000, {"PSK_MERGE_TILE_PAIRS": "3000"}),                     # two sample groups (global bitmap by atomics)
-    (16, 1100, 2_000, {"PSK_MERGE_RCAP": "40", "PSK_MERGE_RANGES": "3"}),    # two groups, batches, three long ranges
+    (16, 1100, 2_000, {"PSK_MERGE_RCAP_PCT": "0.5", "PSK_MERGE_RANGES": "3"}),  # two groups, three long ranges
     (17, 24, 50_000, {"PSK_MERGE_RANGES": "1"}),                             # k = 17, the widest eligible space; one range
 ])
 def test_merge_presence_build_equals_the_oracle_and_the_sort_route(ctx, oracle, k, n, length, env, monkeypatch):
     """r03: the presence build for k >= 14 is a streaming 64-way merge of the sorted lists per wave (presence_merge.hip)
     instead of a sort of all (word, sample) pairs.  Union and every row equal the oracle's and the sort route's, with
-    empty samples, identical samples, a slab filter, tiles of every size, tiles streamed in several batches of rows,
-    and more than 1,024 samples (two workgroups per tile range)."""
+    empty samples, identical samples, a slab filter, tiles of every size, and more than 1,024 samples (two workgroups
+    per tile range).  (No tile here outgrows the fill's LDS block, whatever PSK_MERGE_RCAP_PCT says: a tile spans at
+    most 2,048 bitmap words of the word space, and at these sizes that holds far fewer rows than a block; the batched
+    fill is not reached.)"""
     from phenotypeseeker_amd.synth import GenomeSet
     gs = GenomeSet(n, length, seed=3 * k + n, gene_len=150, sub_rate=0.01)
     datas = [gs.sample(i)[1] for i in range(n)]

@@ -419,6 +419,101 @@ def test_form_knobs_of_neighbour_joining_and_of_the_merge_build_are_validated(mo
         assert ctx.build_presence() > 0
 
 
+def _refused(monkeypatch, var, bads, call):
+    """Each of `bads` in `var` makes `call` raise PskError with PSK_EINVAL and the variable's name."""
+    from phenotypeseeker_amd._lib import PskError
+    for bad in bads:
+        monkeypatch.setenv(var, bad)
+        with pytest.raises(PskError) as e:
+            call()
+        assert e.value.code == -1 and var in str(e.value), (var, bad, str(e.value))
+    monkeypatch.delenv(var)
+
+
+@pytest.mark.gpu
+def test_integer_and_set_knobs_are_refused_where_they_are_read(monkeypatch):
+    """Every value knob parses whole and lies in its range or set, in the call that reads it (docs/KNOBS.md): a non-number
+    and a value out of range are PSK_EINVAL naming the variable, where atoi / strtoull once made 0 of them, clamped them
+    or ignored them.  Afterwards the same context works on."""
+    from phenotypeseeker_amd.engine import PskContext
+    from phenotypeseeker_amd.synth import GenomeSet
+    for var, bads in (("PSK_GRID_MULT", ["x", "0"]), ("PSK_COPY_STREAMS", ["two", "5"]), ("PSK_PINNED_CACHE_MB", ["1G", "-1"])):
+        _refused(monkeypatch, var, bads, lambda: PskContext(0).close())          # read once per context, by psk_init
+    gs = GenomeSet(4, 5000, seed=1, gene_len=100)
+    datas = [gs.sample(i)[1] for i in range(4)]
+    with PskContext(0) as ctx:
+        # the scan
+        ctx.synth_presence(4096, 96, seed=2)
+        pheno = np.array([i % 2 for i in range(96)], dtype=np.int8)
+        scan = lambda: ctx.chi2_scan(pheno, None, 2, 94, 0.05, 0, 4096)
+        _refused(monkeypatch, "PSK_CHI2_MODE", ["abc", "1"], scan)
+        assert scan() >= 0
+        # the counting: genomes per launch chain of the dense kernels (k = 13)
+        ctx.begin(13, 4)
+        _refused(monkeypatch, "PSK_DC_GROUP", ["abc", "0", "9"], lambda: ctx.count_kmers_batch(0, datas, 2))
+        ctx.count_kmers_batch(0, datas, 2)
+        # the presence builds (k = 16): tiled, sort, merge
+        ctx.begin(16, 4)
+        ctx.count_kmers_batch(0, datas, 2)
+        _refused(monkeypatch, "PSK_TILE_LDS_KB", ["abc", "0", "157"], ctx.build_presence)
+        m = ctx.build_presence()
+        monkeypatch.setenv("PSK_NO_TILED_PRESENCE", "1")
+        for var, bads in (("PSK_MERGE_TILE_PAIRS", ["x", "63"]), ("PSK_MERGE_RANGES", ["x", "0"]),
+                          ("PSK_MERGE_REC_REGION", ["8k", "0", str(1 << 26)]), ("PSK_MERGE_RCAP_PCT", ["x", "0", "1.5"])):
+            _refused(monkeypatch, var, bads, ctx.build_presence)
+        monkeypatch.setenv("PSK_NO_MERGE_PRESENCE", "1")
+        _refused(monkeypatch, "PSK_PAIR_CHUNK", ["abc", "1023"], ctx.build_presence)
+        assert ctx.build_presence() == m
+        monkeypatch.delenv("PSK_NO_MERGE_PRESENCE")
+        monkeypatch.delenv("PSK_NO_TILED_PRESENCE")
+        # .gz: the route's threshold, then the device inflate's own knobs (PSK_GZ_LANES=0 once divided by zero)
+        text = b"".join(datas)
+        gz = gzip.compress(text)
+        inflate = lambda: ctx.gz_inflate([gz])
+        _refused(monkeypatch, "PSK_GZ_DEVICE_MIN_MB", ["abc", "-1"], inflate)
+        monkeypatch.setenv("PSK_GZ_DEVICE_MIN_MB", "0")
+        for var, bads in (("PSK_GZ_LANES", ["abc", "0"]), ("PSK_GZ_CHUNK", ["16k", "-1"]), ("PSK_GZ_ROUNDS", ["x", "-1"]),
+                          ("PSK_GZ_MAX_SPAN", ["1MiB", "-1"])):
+            _refused(monkeypatch, var, bads, inflate)
+        texts, _, routes, _ = inflate()
+        assert texts[0] == text and routes[0] in (1, 2)
+        ctx.begin(16, 1)
+        _refused(monkeypatch, "PSK_GZ_GROUP_MB", ["abc", "-1"], lambda: ctx.count_kmers_batch(0, [gz], 1))
+        ctx.count_kmers_batch(0, [gz], 1)
+        # neighbour joining
+        mat = np.ones((5, 5)) - np.eye(5)
+        _refused(monkeypatch, "PSK_NJ_LDS", ["abc", "2"], lambda: ctx.nj_merges(mat))
+        assert len(ctx.nj_merges(mat)[0]) == 3
+
+
+@pytest.mark.gpu
+def test_a_flag_set_to_0_is_off(monkeypatch, capfd):
+    """Flags follow the documented rule: "0" is off, as unset is (a bare getenv once switched them on).  Seen in the phase
+    names PSK_TRACE prints: the tiled and the merge presence builds still run with PSK_NO_TILED_PRESENCE=0 /
+    PSK_NO_MERGE_PRESENCE=0, and PSK_TRACE=0 prints nothing."""
+    from phenotypeseeker_amd.engine import PskContext
+    from phenotypeseeker_amd.synth import GenomeSet
+    gs = GenomeSet(4, 5000, seed=1, gene_len=100)
+    with PskContext(0) as ctx:
+        ctx.begin(14, 4)                                   # (k = 14: the tiled build's word space)
+        ctx.count_kmers_batch(0, [gs.sample(i)[1] for i in range(4)], 2)
+
+        def trace_of_a_build(**env):
+            for name, val in env.items():
+                monkeypatch.setenv(name, val)
+            capfd.readouterr()
+            ctx.build_presence()
+            for name in env:
+                monkeypatch.delenv(name)
+            return capfd.readouterr().err
+        assert "tiled build" in trace_of_a_build(PSK_TRACE="1")
+        assert "tiled build" in trace_of_a_build(PSK_TRACE="1", PSK_NO_TILED_PRESENCE="0")
+        assert "tiled build" not in trace_of_a_build(PSK_TRACE="1", PSK_NO_TILED_PRESENCE="1")
+        assert "merge build" in trace_of_a_build(PSK_TRACE="1", PSK_NO_TILED_PRESENCE="1", PSK_NO_MERGE_PRESENCE="0")
+        assert "merge build" not in trace_of_a_build(PSK_TRACE="1", PSK_NO_TILED_PRESENCE="1", PSK_NO_MERGE_PRESENCE="1")
+        assert trace_of_a_build(PSK_TRACE="0") == ""
+
+
 def test_oracle_neighbour_joining_on_the_textbook_example():
     """orc_nj (the checker of the GPU neighbour joining) on the five-taxon example of the neighbour-joining literature
     (Saitou & Nei's method as tabulated in the Wikipedia article: a, b joined first with branches 2 and 3 -- although (d, e) ties
