@@ -224,6 +224,10 @@ int psk_export_survivors_async(psk_ctx *ctx, void *device_dst, uint64_t cap_reco
  * rows mostly within 7 samples of all-absent or all-present), and how many of its rows sit in the side matrix of dense
  * rows (*overflow_rows).  Measurement and tests only: the scan picks its form by itself (PSK_SCAN_DENSE=1 forces the dense one). */
 int psk_compact_info(const psk_ctx *ctx, int *encoded, uint64_t *overflow_rows);
+/* 1 when the division-free pre-test of the unit-weight chi2 scan lets the 2 x 2 table (A, B | C, D) through to the exact
+ * evaluation against the statistic threshold thr = -2 log(cut), else 0: the host's evaluation of the function the dense
+ * kernel and the exception-coded scan's candidate table share.  Tests only (no context, no device). */
+int psk_chi2_pretest(double A, double B, double C, double D, double thr);
 /* HIP-event duration of the last scan kernel launch in milliseconds (for bench.py). */
 double psk_last_scan_ms(const psk_ctx *ctx);
 /* Re-launches the last chi2 scan `reps` times back to back on the context's stream and

@@ -407,6 +407,56 @@ double orc_t_two_sided_p(double t, double df)
     return orc_betainc(0.5 * df, 0.5, x);
 }
 
+/* numpy's pairwise_sum (numpy/_core/src/umath/loops_utils.h.src): sequential from -0.0 below 8 elements, eight
+ * interleaved accumulators up to 128, else the two halves with the split rounded down to a multiple of 8 */
+static double pairwise_sum(const double *a, long n)
+{
+    if (n < 8) {
+        double r = -0.0;
+        for (long i = 0; i < n; i++) r += a[i];
+        return r;
+    }
+    if (n <= 128) {
+        double r[8];
+        long i;
+        for (i = 0; i < 8; i++) r[i] = a[i];
+        for (i = 8; i < n - (n % 8); i += 8)
+            for (int j = 0; j < 8; j++) r[j] += a[i + j];
+        double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+        for (; i < n; i++) res += a[i];
+        return res;
+    }
+    long n2 = n / 2;
+    n2 -= n2 % 8;
+    return pairwise_sum(a, n2) + pairwise_sum(a + n2, n - n2);
+}
+
+/* np.add.reduce of a float64 array: from 0.0, the pairwise sums of its 8,192-element buffers in turn */
+static double numpy_sum(const double *a, long n)
+{
+    double r = 0.0;
+    for (long i = 0; i < n; i += 8192) r += pairwise_sum(a + i, n - i < 8192 ? n - i : 8192);
+    return r;
+}
+
+/* the group means as the reference prints them: np.average(x, weights=x_weights) (modeling.py:735-736) =
+ * numpy_sum(x * w) / numpy_sum(w) over the group's samples in sample order */
+static void numpy_group_means(const uint8_t *presence, const double *pheno, const uint8_t *valid, const double *weight,
+                              int n_samples, double *mean_x, double *mean_y)
+{
+    double *buf = (double *)malloc(sizeof(double) * 4 * (size_t)(n_samples > 0 ? n_samples : 1));
+    double *xw = buf, *xs = buf + n_samples, *yw = buf + 2 * (size_t)n_samples, *ys = buf + 3 * (size_t)n_samples;
+    long cx = 0, cy = 0;
+    for (int i = 0; i < n_samples; i++) {
+        if (!valid[i]) continue;
+        if (presence[i] == 0) { yw[cy] = pheno[i] * weight[i]; ys[cy++] = weight[i]; }
+        else { xw[cx] = pheno[i] * weight[i]; xs[cx++] = weight[i]; }
+    }
+    *mean_x = numpy_sum(xw, cx) / numpy_sum(xs, cx);
+    *mean_y = numpy_sum(yw, cy) / numpy_sum(ys, cy);
+    free(buf);
+}
+
 int orc_ttest_row(const uint8_t *presence, const double *pheno, const uint8_t *valid, const double *weight,
                   int n_samples, int min_samples, int max_samples, double *t_out, double *p_out,
                   double *mean_x_out, double *mean_y_out, int *n_with_out)
@@ -436,8 +486,9 @@ int orc_ttest_row(const uint8_t *presence, const double *pheno, const uint8_t *v
     double df = 1.0 / (z1 + z2);
     *t_out = t;
     *p_out = orc_t_two_sided_p(t, df);
-    *mean_x_out = mx;
-    *mean_y_out = my;
+    /* t follows DescrStatsW's sample-order sums above; the printed means are np.average's (numpy's pairwise order): at a
+     * two-decimal tie the one ulp between the two decides round(mean, 2) */
+    numpy_group_means(presence, pheno, valid, weight, n_samples, mean_x_out, mean_y_out);
     return 1;
 }
 

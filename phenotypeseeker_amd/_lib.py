@@ -65,6 +65,7 @@ _SIGNATURES = {
     "psk_get_results": (c.c_int, [c.c_void_p] + [c.c_void_p] * 7 + [c.c_uint64]),
     "psk_export_survivors": (c.c_int, [c.c_void_p, c.c_void_p, c.c_uint64, _u64p]),
     "psk_compact_info": (c.c_int, [c.c_void_p, c.POINTER(c.c_int), c.POINTER(c.c_uint64)]),
+    "psk_chi2_pretest": (c.c_int, [c.c_double] * 5),
     "psk_last_scan_ms": (c.c_double, [c.c_void_p]),
     "psk_rescan_timed": (c.c_int, [c.c_void_p, c.c_int, c.POINTER(c.c_double)]),
     "psk_rescan_times": (c.c_int, [c.c_void_p, c.c_int, c.c_void_p]),

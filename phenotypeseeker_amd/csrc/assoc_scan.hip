@@ -1177,6 +1177,103 @@ __global__ __launch_bounds__(SC_FIN_THREADS) void ttest_finalize_kernel(const Sc
     }
 }
 
+// np.add.reduce of a float64 stream of n values, fed in order: from 0.0, the pairwise sums (numpy's pairwise_sum:
+// sequential from -0.0 below 8 elements, eight interleaved accumulators up to 128, else the two halves with the split
+// rounded down to a multiple of 8) of its 8,192-element buffers in turn.  The tree of a buffer is walked leaf by leaf: a
+// frame per level holds the size of the right half still to come (0 once it is under way) and the left half's sum.
+struct NpSum {
+    double tot, acc, r[8], left[8];
+    int right[8], depth, leaf, k, rest;
+};
+__device__ int np_descend(NpSum &s, int sz)
+{
+    while (sz > 128) {
+        int n2 = sz / 2;
+        n2 -= n2 % 8;
+        s.right[s.depth++] = sz - n2;
+        sz = n2;
+    }
+    return sz;
+}
+__device__ void np_next_buffer(NpSum &s)
+{
+    const int c = s.rest < 8192 ? s.rest : 8192;
+    s.rest -= c;
+    s.depth = 0;
+    s.leaf = np_descend(s, c);
+    s.k = 0;
+}
+__device__ void np_begin(NpSum &s, int n)
+{
+    s.tot = 0.0;
+    s.rest = n;
+    if (n > 0) np_next_buffer(s);
+}
+__device__ double np_fold8(const double *r) { return ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7])); }
+__device__ void np_add(NpSum &s, double v)
+{
+    const int L = s.leaf, body = L - L % 8;
+    if (L < 8) s.acc = (s.k == 0 ? -0.0 : s.acc) + v;
+    else if (s.k < 8) s.r[s.k] = v;
+    else if (s.k < body) s.r[s.k & 7] += v;
+    else {
+        if (s.k == body) s.acc = np_fold8(s.r);
+        s.acc += v;
+    }
+    if (++s.k < L) return;
+    double sum = (L >= 8 && body == L) ? np_fold8(s.r) : s.acc;   // the leaf is done
+    while (s.depth > 0) {
+        const int t = s.depth - 1;
+        if (s.right[t] > 0) {   // its left half: the right half comes next
+            s.left[t] = sum;
+            const int rs = s.right[t];
+            s.right[t] = 0;
+            s.leaf = np_descend(s, rs);
+            s.k = 0;
+            return;
+        }
+        sum = s.left[t] + sum;
+        s.depth = t;
+    }
+    s.tot += sum;
+    if (s.rest > 0) np_next_buffer(s);
+}
+
+// The two means of every Welch survivor as the reference prints them: np.average(x, weights=x_weights)
+// (modeling.py:735-736) = the numpy sums of w v and of w over the group's samples in sample order.  ttest_finalize_kernel's
+// t follows DescrStatsW's sums, which it adds in sample order; the two orders differ by an ulp now and then, and at a
+// two-decimal tie that ulp decides round(mean, 2).  One thread per survivor (they are few), after the finalize kernel has
+// compacted its segment.
+template <bool WT>
+__global__ __launch_bounds__(256) void ttest_means_kernel(const ScanArgs P)
+{
+    const uint32_t seg = blockIdx.x;
+    const uint32_t c = min(P.final_counts[seg], P.seg_cap);   // (an overflowed segment is refused by fetch_counts)
+    const uint64_t base = (uint64_t)seg * P.seg_cap;
+    const double2 *raw = reinterpret_cast<const double2 *>(P.raw);   // {weight, value}; NA: {0, 0}
+    const int words = P.half ? 1 : 2 * P.cpr;
+    for (uint32_t i = threadIdx.x; i < c; i += blockDim.x) {
+        const uint64_t row = P.res_row[base + i];
+        const int nw = P.res_nw[base + i];
+        const uint64_t *rp = reinterpret_cast<const uint64_t *>(P.bits) + row * (uint64_t)words;
+        NpSum sx, sy, wx, wy;
+        np_begin(sx, nw);
+        np_begin(sy, P.nvalid - nw);
+        if (WT) { np_begin(wx, nw); np_begin(wy, P.nvalid - nw); }
+        for (int wd = 0; wd < words; wd++) {
+            const uint64_t pres = rp[wd];
+            for (uint64_t m = P.mvalid[wd]; m; m &= m - 1) {
+                const int b = __ffsll((long long)m) - 1;
+                const double2 t = raw[wd * 64 + b];
+                if ((pres >> b) & 1) { np_add(sx, t.y * t.x); if (WT) np_add(wx, t.x); }
+                else { np_add(sy, t.y * t.x); if (WT) np_add(wy, t.x); }
+            }
+        }
+        P.res_mx[base + i] = sx.tot / (WT ? wx.tot : (double)nw);
+        P.res_my[base + i] = sy.tot / (WT ? wy.tot : (double)(P.nvalid - nw));
+    }
+}
+
 template <bool WT>
 void launch_ttest_w(int G, dim3 grid, hipStream_t st, const ScanArgs &a, double mu)
 {
@@ -1232,8 +1329,13 @@ void launch_ttest(int G, dim3 grid, hipStream_t st, const ScanArgs &a, double mu
         else launch_ttest_lut<false>(G, grid, st, a, mu);
     } else if (weighted) launch_ttest_w<true>(G, grid, st, a, mu);
     else launch_ttest_w<false>(G, grid, st, a, mu);
-    if (weighted) ttest_finalize_kernel<true><<<SC_NSEG, SC_FIN_THREADS, 0, st>>>(a);
-    else ttest_finalize_kernel<false><<<SC_NSEG, SC_FIN_THREADS, 0, st>>>(a);
+    if (weighted) {
+        ttest_finalize_kernel<true><<<SC_NSEG, SC_FIN_THREADS, 0, st>>>(a);
+        ttest_means_kernel<true><<<SC_NSEG, 256, 0, st>>>(a);
+    } else {
+        ttest_finalize_kernel<false><<<SC_NSEG, SC_FIN_THREADS, 0, st>>>(a);
+        ttest_means_kernel<false><<<SC_NSEG, 256, 0, st>>>(a);
+    }
 }
 
 // builds the nibble table of `tab` (cpr * 128 samples x nm moments, already on the device) into ctx->lut
@@ -1978,3 +2080,5 @@ extern "C" int psk_export_survivors_async(psk_ctx *ctx, void *device_dst, uint64
 }
 
 extern "C" double psk_last_scan_ms(const psk_ctx *ctx) { return ctx ? ctx->last_scan_ms : 0.0; }
+
+extern "C" int psk_chi2_pretest(double A, double B, double C, double D, double thr) { return chi2_pretest(A, B, C, D, thr) ? 1 : 0; }

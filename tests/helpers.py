@@ -101,3 +101,80 @@ def mask_numbers(line):
     """Every numeric token of a line replaced by '#': what is left of a summary line when liblinear's unseeded,
     unconverged coefficients decide its numbers."""
     return " ".join("#" if _num(t) is not None else t for t in line.split())
+
+
+# ---- the chi2 scan's reference arithmetic (the GPU tests of the scans compare with this, not with the C oracle) ----------
+SCAN_KNOBS = ("PSK_CHI2_MODE", "PSK_SCAN_DENSE", "PSK_LUT_F64", "PSK_NO_LUT")
+
+
+class scan_knobs:
+    """with scan_knobs({"PSK_SCAN_DENSE": "1"}): ...  -- the scan knobs of SCAN_KNOBS set as given and the others unset for
+    the block, restored after it (the library reads them on every scan)."""
+
+    def __init__(self, env):
+        self.env = env
+
+    def __enter__(self):
+        self.saved = {k: os.environ.get(k) for k in SCAN_KNOBS}
+        for k in SCAN_KNOBS:
+            os.environ.pop(k, None)
+        os.environ.update(self.env)
+
+    def __exit__(self, *exc):
+        for k, v in self.saved.items():
+            os.environ.pop(k, None)
+            if v is not None:
+                os.environ[k] = v
+
+
+def chi2_restated(A, B, C, D):
+    """conduct_chi_squared_test (modeling.py:773-792) in float64 and in its operation order, elementwise over arrays of the
+    four cells: totals, expected counts (w_pheno * w_kmer) / total ..., then scipy's Pearson terms (O - E)**2 / E summed left
+    to right (numpy sums four terms in order).  E = 0 gives NaN, as in the reference."""
+    import numpy as np
+    A, B, C, D = (np.asarray(x, dtype=np.float64) for x in (A, B, C, D))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        w_pheno, wo_pheno, w_kmer, wo_kmer = A + B, C + D, A + C, B + D
+        total = w_pheno + wo_pheno
+        stat = np.zeros(np.broadcast(A, B, C, D).shape)
+        for o, e in ((A, (w_pheno * w_kmer) / total), (B, (w_pheno * wo_kmer) / total), (C, (wo_pheno * w_kmer) / total),
+                     (D, (wo_pheno * wo_kmer) / total)):
+            d = o - e
+            stat = stat + (d * d) / e
+    return stat
+
+
+def chi2_every_table(n1, n0):
+    """(stat, p) of every unit-weight table (a, c), 0 <= a <= n1, 0 <= c <= n0, as [n1 + 1][n0 + 1] arrays; p is
+    scipy.stats.chi2.sf(stat, 2), what stats.chisquare(f_obs, f_exp, 1) returns."""
+    import numpy as np
+    import scipy.stats
+    a = np.arange(n1 + 1, dtype=np.float64)[:, None]
+    c = np.arange(n0 + 1, dtype=np.float64)[None, :]
+    stat = chi2_restated(a, n1 - a, c, n0 - c)
+    return stat, scipy.stats.chi2.sf(stat, 2)
+
+
+def chi2_reference_keep(n_w, n_wo, p, min_samples, max_samples, pvalue_cutoff, omit_B, n_kmers):
+    """The frequency filter (modeling.py:770-772) and the keep rule (:795), elementwise"""
+    import numpy as np
+    with np.errstate(invalid="ignore"):
+        freq_ok = ~((n_w < min_samples) | (n_wo < 2) | (n_w > max_samples))
+        return freq_ok & ((omit_B & (p < pvalue_cutoff)) | (p < pvalue_cutoff / n_kmers))
+
+
+def round2(x):
+    """round(np.float64, 2) as the reference prints it"""
+    import numpy as np
+    return float(np.round(np.float64(x), 2))
+
+
+def pack_presence(pres):
+    """bool [m][n] -> the library's bit rows: sample i is bit (i & 63) of word (i >> 6), words_per_row(n) words"""
+    import numpy as np
+    from phenotypeseeker_amd.engine import words_per_row
+    m, n = pres.shape
+    wpr = words_per_row(n)
+    padded = np.zeros((m, wpr * 64), dtype=bool)
+    padded[:, :n] = pres
+    return np.ascontiguousarray(np.packbits(padded, axis=1, bitorder="little").view("<u8").astype(np.uint64))

@@ -28,6 +28,29 @@ def test_library_exports_every_declared_symbol():
     assert lib.psk_version() >> 16 == 1
 
 
+def test_chi2_pretest_is_sound_and_tight():
+    """The division-free pre-test (chi2_pretest) decides which unit-weight tables the dense kernel and the exception-coded
+    scan evaluate exactly.  Over every table of three phenotypes and four cuts: every table whose restated statistic reaches
+    the threshold (less 1e-10) is let through, and every table more than 2e-9 below it is ruled out -- the slack covers
+    the rounding of the two forms of the statistic and no more."""
+    from phenotypeseeker_amd import _lib
+    from helpers import chi2_restated
+    pretest = _lib.load().psk_chi2_pretest
+    in_band = 0
+    for n1, n0 in ((20, 24), (50, 43), (140, 150)):
+        a = np.repeat(np.arange(n1 + 1, dtype=np.float64), n0 + 1)
+        c = np.tile(np.arange(n0 + 1, dtype=np.float64), n1 + 1)
+        stat = chi2_restated(a, n1 - a, c, n0 - c)
+        for cut in (0.5, 0.05, 0.05 / 1e4, 1e-30):
+            thr = -2.0 * np.log(cut)
+            got = np.array([pretest(*t, thr) for t in zip(a, n1 - a, c, n0 - c)], dtype=bool)
+            fin = np.isfinite(stat)
+            assert got[fin & (stat >= thr * (1 - 1e-10))].all(), (n1, n0, cut)
+            assert not got[fin & (stat < thr * (1 - 2e-9))].any(), (n1, n0, cut)
+            in_band += int((fin & (stat < thr * (1 - 2e-9)) & (stat >= thr * (1 - 1e-3))).sum())
+    assert in_band > 10
+
+
 def test_no_cpu_fallback_without_gpu():
     import torch  # only to learn whether this box has a GPU
     if torch.cuda.is_available():

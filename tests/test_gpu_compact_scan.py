@@ -1,13 +1,17 @@
 """The unweighted chi2 scan over the exception-coded copy of the matrix (presence_compact.hip, chi2_scan_kernel_cx)
 against the dense kernel (PSK_SCAN_DENSE=1, in a child process): the same survivors, bit for bit (row, stat, p,
 n_with); and against the C oracle: the same rows and n_with, stat and p as test_gpu_parity.py compares them.
-Also: which matrices are encoded and which are declined."""
+Also: which matrices are encoded and which are declined; and, against the dense kernel and the reference restatement
+(helpers.chi2_restated, scipy's chi2.sf): the kernel at 2.1 M rows under a capped grid (several grid-stride passes per
+wave, the slot / side-matrix split of cx_grid, 0 ... 500 side-matrix rows), at 1 ... 257 rows, and after intersect_db."""
 import os
 import subprocess
 import sys
 
 import numpy as np
 import pytest
+
+from helpers import chi2_every_table, chi2_reference_keep, pack_presence, scan_knobs
 
 pytestmark = pytest.mark.gpu
 
@@ -176,16 +180,143 @@ def test_which_matrices_are_encoded(ctx):
     rng = np.random.default_rng(3)
     ctx.set_presence(_bits_from_presence(rng.random((4000, 150)) < 0.3, 4), 150)
     assert ctx.compact_info() == (False, 0)
-    # intersect_db re-encodes what is left
+    # intersect_db re-encodes what is left: the survivors are the dense kernel's and the reference's on the kept rows
     bits = _core_or_rare(256, 20_000, 9)
     ctx.set_presence(bits, 256)
     assert ctx.compact_info()[0]
-    ctx.intersect_db(np.arange(0, 20_000, 3, dtype=np.uint64))
+    assert ctx.intersect_db(np.arange(0, 20_000, 3, dtype=np.uint64)) == len(bits[::3])
     enc, n_ov = ctx.compact_info()
     assert enc and n_ov > 0
-    ph = _phenotypes(256, 9)[0]
-    c = ctx.chi2_scan(ph, None, 2, 254, 1.5, True, 10)
-    assert c > 0
+    for ph in _phenotypes(256, 9)[:2]:
+        _compact_dense_and_reference(ctx, bits[::3], ph, _sweeps(ph, len(bits[::3])), "intersect")
+    # an intersection that keeps no row: no copy, an empty scan
+    assert ctx.intersect_db(np.array([1 << 40], dtype=np.uint64)) == 0
+    assert ctx.compact_info() == (False, 0)
+    assert ctx.chi2_scan(_phenotypes(256, 9)[0], None, 1, 256, 1.5, True, 10) == 0
+    # a declined matrix (half its rows random) that the intersection turns into an encoded one (its core-or-rare rows)
+    core = _core_or_rare(256, 6000, 10)
+    mixed = np.empty((12_000, 4), np.uint64)
+    mixed[0::2] = core
+    mixed[1::2] = _bits_from_presence(rng.random((6000, 256)) < 0.3, 4)
+    ctx.set_presence(mixed, 256)
+    assert ctx.compact_info() == (False, 0)
+    assert ctx.intersect_db(np.arange(0, 12_000, 2, dtype=np.uint64)) == 6000
+    assert ctx.compact_info()[0]
+    for ph in _phenotypes(256, 10)[:2]:
+        _compact_dense_and_reference(ctx, core, ph, _sweeps(ph, 6000), "declined then encoded")
+
+
+# ---- the exception-coded kernel against the dense kernel and the reference restatement, at scale and at the edges ----------
+def _scan(ctx, env, ph8, mn, mx, cut, omit, nk):
+    with scan_knobs(env):
+        return ctx.get_results(ctx.chi2_scan(ph8, None, mn, mx, cut, omit, nk))
+
+
+def _sweeps(ph8, m):
+    """the usual cut with omit_B, and a cut >= 1: every row the frequency filter passes survives"""
+    n_valid = int((ph8 >= 0).sum())
+    return [(2, n_valid - 2, 0.05, True, m), (1, n_valid, 1.5, True, 1)]
+
+
+def _compact_dense_and_reference(ctx, bits, ph8, sweeps, what):
+    """Each sweep on the encoded copy (asserted) and on the dense kernel: the same survivors bit for bit, and the
+    reference's -- keep set, the restated statistic bit for bit, p within 1e-13 of chi2.sf.  Returns the survivor counts."""
+    assert ctx.compact_info()[0], what
+    n1, n0 = int((ph8 == 1).sum()), int((ph8 == 0).sum())
+    m1, m0 = (pack_presence((ph8 == v)[None, :])[0] for v in (1, 0))
+    a = np.bitwise_count(bits & m1).sum(axis=1).astype(np.int64)
+    c = np.bitwise_count(bits & m0).sum(axis=1).astype(np.int64)
+    stat_t, p_t = chi2_every_table(n1, n0)
+    counts = []
+    for sw in sweeps:
+        got = _scan(ctx, {}, ph8, *sw)
+        dense = _scan(ctx, {"PSK_SCAN_DENSE": "1"}, ph8, *sw)
+        for f in FIELDS:
+            assert np.array_equal(got[f], dense[f]), (what, sw, f)
+        keep = np.nonzero(chi2_reference_keep(a + c, n1 + n0 - a - c, p_t[a, c], *sw))[0]
+        rows = got["row"].astype(np.int64)
+        assert np.array_equal(rows, keep), (what, sw, len(rows), len(keep))
+        assert np.array_equal(got["n_with"], (a + c)[rows]), (what, sw)
+        assert np.array_equal(got["stat"], stat_t[a[rows], c[rows]]), (what, sw)
+        p_ref = p_t[a[rows], c[rows]]
+        assert np.all(np.abs(got["p"] - p_ref) <= 1e-13 * p_ref), (what, sw)
+        counts.append(len(rows))
+    return counts
+
+
+def _slot_rows(rng, m, n):
+    """m rows of 1 ... 7 exceptions (an index drawn twice counts once), present or absent samples alike"""
+    from phenotypeseeker_amd.engine import words_per_row
+    e = rng.integers(1, 8, m)
+    idx = rng.integers(0, n, (m, 7))
+    bits = np.zeros((m, words_per_row(n)), np.uint64)
+    for j in range(7):
+        on = j < e
+        for wd in range(bits.shape[1]):
+            sel = on & (idx[:, j] >> 6 == wd)
+            bits[sel, wd] |= np.uint64(1) << (idx[sel, j] & 63).astype(np.uint64)
+    flip = rng.random(m) < 0.5
+    bits[flip] ^= pack_presence(np.ones((1, n), bool))[0]
+    return bits
+
+
+def _ov_rows(rng, k, ph8):
+    """k rows of many exceptions (the side matrix), associated with the phenotype: present in most cases, few controls"""
+    return pack_presence(np.where(ph8 == 1, rng.random((k, len(ph8))) < 0.8, rng.random((k, len(ph8))) < 0.2))
+
+
+@pytest.fixture(scope="module")
+def big_matrix():
+    """2.1 M slot rows at 256 samples, 500 side-matrix rows, a phenotype with NA samples"""
+    rng = np.random.default_rng(21)
+    n = 256
+    ph8 = np.where(rng.random(n) < 0.04, -1, np.arange(n) % 2 == 0).astype(np.int8)
+    return n, _slot_rows(rng, 2_100_000, n), _ov_rows(rng, 500, ph8), ph8
+
+
+@pytest.mark.parametrize("grid_mult", [1, 2])
+def test_compact_scan_grid_stride_passes_and_split(big_matrix, grid_mult):
+    """A context whose scan grid is capped at 1 or 2 workgroups per CU (PSK_GRID_MULT, read by psk_init): each wave makes
+    several passes of its grid-stride loop, and cx_grid splits the capped grid between slots and side matrix in proportion
+    to their bytes -- with 1, 64, 65 side-matrix rows the side matrix gets the one workgroup of the n_ov && bo == 0
+    branch; with none, no workgroup.  A cut >= 1 keeps nearly every row: no result segment may overflow (PSK_ERANGE)."""
+    from phenotypeseeker_amd.engine import PskContext
+    n, base, ov, ph8 = big_matrix
+    saved = os.environ.get("PSK_GRID_MULT")
+    os.environ["PSK_GRID_MULT"] = str(grid_mult)
+    try:
+        ctx = PskContext(0)
+    finally:
+        os.environ.pop("PSK_GRID_MULT", None)
+        if saved is not None:
+            os.environ["PSK_GRID_MULT"] = saved
+    try:
+        for k in ((0, 1, 64, 65, 500) if grid_mult == 1 else (500,)):
+            rng = np.random.default_rng(k)
+            m = len(base) + k
+            at = np.zeros(m, bool)
+            at[rng.choice(m, k, replace=False)] = True
+            bits = np.empty((m, base.shape[1]), np.uint64)
+            bits[~at] = base
+            bits[at] = ov[:k]
+            ctx.set_presence(bits, n)
+            assert ctx.compact_info() == (True, k)
+            counts = _compact_dense_and_reference(ctx, bits, ph8, _sweeps(ph8, m), ("grid_mult", grid_mult, k))
+            assert counts[1] > 0.75 * m
+    finally:
+        ctx.close()
+
+
+@pytest.mark.parametrize("m", [1, 2, 3, 255, 256, 257])
+def test_compact_scan_small_row_counts(ctx, m):
+    """Row counts around one slot pair and one wave step, on the encoded path (no side matrix)"""
+    for n in (100, 200):
+        rng = np.random.default_rng(m * 1000 + n)
+        ph8 = np.where(rng.random(n) < 0.05, -1, rng.random(n) < 0.5).astype(np.int8)
+        bits = _slot_rows(rng, m, n)
+        ctx.set_presence(bits, n)
+        assert ctx.compact_info() == (True, 0)
+        _compact_dense_and_reference(ctx, bits, ph8, _sweeps(ph8, m) + [(0, n, 0.9, False, 1)], ("rows", m, n))
 
 
 if __name__ == "__main__":      # the dense side of test_compact_scan_equals_dense_kernel_and_oracle (PSK_SCAN_DENSE=1)

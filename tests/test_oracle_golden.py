@@ -128,6 +128,24 @@ def test_welch_kats(oracle):
         assert nw == sum(c["presence"])
 
 
+def test_welch_means_are_np_average(oracle):
+    """The means the reference prints are round(np.average(x, weights=x_weights), 2) (modeling.py:735-736): numpy's
+    pairwise sums within 8,192-element buffers.  The oracle's, bit for bit, at group sizes on both sides of 8, 128 and 8,192
+    (the GPU's equal the oracle's: tests/test_gpu_parity.py)."""
+    rng = np.random.default_rng(11)
+    for n in (6, 9, 17, 130, 131, 300, 1025, 8200, 17000):
+        for wt in (False, True):
+            vals = np.round(rng.normal(3.0, 1.5, n), 4)
+            valid = rng.random(n) > 0.05
+            pres = rng.random(n) < 0.5
+            valid[:4] = True
+            pres[:4] = [True, True, False, False]   # two samples in each group at least: the row passes the filter
+            w = rng.integers(1, 5, n).astype(np.float64) if wt else np.ones(n)
+            r = oracle.ttest_row(pres, [float(v) if ok else "NA" for v, ok in zip(vals, valid)], w, 1, n)
+            x, y = pres & valid, ~pres & valid
+            assert (r[2], r[3]) == (np.average(vals[x], weights=w[x]), np.average(vals[y], weights=w[y])), (n, wt)
+
+
 def test_gmer_counter_outputs(oracle):
     import base64
     import gzip
