@@ -201,7 +201,7 @@ int build_presence_merge_wide(psk_ctx *ctx, uint64_t total_pairs, uint64_t *n_km
 static int padded_wpr(int n_samples)
 {
     int w = (n_samples + 63) / 64;
-    if (w == 1) return 1;  // up to 64 samples: 8-byte rows, two per 16-byte load of the scans (assoc_scan.hip, G = 0)
+    if (w == 1) return 1;  // up to 64 samples: 8-byte rows, two per 16-byte load of the scans (scan_common.h stream_rows, G = 0)
     return (w + 1) & ~1;   // even: rows are 16-byte aligned
 }
 

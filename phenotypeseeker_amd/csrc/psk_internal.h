@@ -184,8 +184,8 @@ struct psk_ctx {
 
     // scan state
     DevBuf mask1, phe, res_count, res_sorted;
-    DevBuf lut;                          // nibble table of the moment scans (assoc_scan.hip row_moments_lut)
-    bool lut_valid = false;              // ... holds the table of the last weighted chi2 scan
+    DevBuf lut;                          // nibble table of the moment scans (scan_common.h row_moments_lut)
+    bool lut_valid = false;              // ... holds the table of the last moment scan (setup_table_scan)
     bool lut6_valid = false;             // ... in its six-bit f32 form (row_moments_f32)
     uint64_t n_pass = 0;
     uint64_t res_seg_cap = 0;            // entries per result segment of the last scan

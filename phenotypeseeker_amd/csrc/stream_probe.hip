@@ -13,7 +13,7 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // Shape 0: grid-stride, four loads 1/4 of the grid's span apart per lane.
 // Shape 1: the scan's own shape -- a wave owns UNR consecutive 1-KiB pieces per step (64 lanes x 16 B each), the waves of the
-// grid take consecutive steps and stride by the whole grid (assoc_scan.hip chi2_scan_kernel: SC_UNROLL = 4 pieces in flight).
+// grid take consecutive steps and stride by the whole grid (scan_common.h stream_rows: SC_UNROLL = 4 pieces in flight).
 // NT: non-temporal loads (no allocation in L2 / the Infinity Cache) or plain ones.
 template <int SHAPE, bool NT>
 __global__ __launch_bounds__(256) void stream_read_kernel(const u32x4 *__restrict__ p, uint64_t n_vec, uint32_t *__restrict__ sink, const uint32_t magic)
