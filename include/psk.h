@@ -286,6 +286,28 @@ int psk_logreg_l2_fit(psk_ctx *ctx, const float *X, const int32_t *y01, int n, i
                       const double *fit_param, const int32_t *fit_fold, int n_fits, double tol, int max_iter,
                       int penalise_intercept, double *coef_out, double *icpt_out, int32_t *iters_out);
 
+/* ---- f5: the `-bc SVM` estimator ------------------------------------------------------------------
+ * Replaces GridSearchCV over SVC(kernel='linear' | 'rbf', probability=True, max_iter, tol) (set_model,
+ * modeling.py:1025-1029, :1050-1056, :1086-1090).  Same batching and the same meaning of X, y01, n, p, fold,
+ * fit_fold, n_fits as psk_logreg_l1_fit; fit_C[j] (and fit_gamma[j] for the rbf kernel) are fit j's parameters.
+ * Per fit, libsvm's C-SVC dual  min 1/2 a'Qa - e'a, 0 <= a_i <= C, y'a = 0, Q_ij = y_i y_j K_ij  with class 0 as
+ * libsvm's +1 (scikit-learn sorts the labels) and no class weights, walked by libsvm's Solver::Solve without
+ * shrinking, step for step (WSS2 working sets with libsvm's tie rules, float Q entries, f64 elsewhere): a fit that
+ * stops at max_iter returns that iterate, as scikit-learn does, so the PATH is part of the contract
+ * (csrc/solver_svc.hip).  K: linear x_i . x_j, rbf exp(-gamma |x_i - x_j|^2).  max_iter = -1: no limit.
+ *   dual_out[n_fits][n]  y_i alpha_i in libsvm's sign (class 0 positive), 0 for samples the fit did not train on
+ *   rho_out[n_fits]
+ *   dec_out[n_fits][n]   sum_j dual_j K(x_j, x_i) - rho for EVERY sample, held-out ones included (libsvm's sign:
+ *                        scikit-learn's decision_function is its negative)
+ *   iters_out[n_fits]    iterations taken (== max_iter: stopped at the limit); may be NULL
+ * The sample x sample dot products are built once per call and shared by the fits (popcounts of bit-packed rows for
+ * a 0/1 design, f64 dot products otherwise): at most 4096 samples (PSK_ERANGE beyond).  A fit whose training
+ * samples are of one class is refused (PSK_EINVAL).
+ */
+int psk_svc_fit(psk_ctx *ctx, const float *X, const int32_t *y01, int n, int p, const int32_t *fold,
+                const double *fit_C, const double *fit_gamma, const int32_t *fit_fold, int n_fits, int kernel,
+                double tol, int max_iter, double *dual_out, double *rho_out, double *dec_out, int32_t *iters_out);
+
 /* ---- f1: fixed-dictionary counting (prediction) ---------------------------------------------
  * Replaces `gmer_counter -db <txt> <addr>` (prediction.Samples.map_samples, prediction.py:72-80):
  * occurrences, both strands with multiplicity, of each dictionary k-mer (canonical words) in

@@ -79,6 +79,9 @@ _SIGNATURES = {
     "psk_logreg_l2_fit": (c.c_int, [c.c_void_p, c.c_void_p, c.c_void_p, c.c_int, c.c_int, c.c_void_p, c.c_void_p,
                                     c.c_void_p, c.c_int, c.c_double, c.c_int, c.c_int, c.c_void_p, c.c_void_p,
                                     c.c_void_p]),
+    "psk_svc_fit": (c.c_int, [c.c_void_p, c.c_void_p, c.c_void_p, c.c_int, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p,
+                              c.c_void_p, c.c_int, c.c_int, c.c_double, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p,
+                              c.c_void_p]),
     "psk_count_dict": (c.c_int, [c.c_void_p, c.c_char_p, c.c_size_t, c.c_int, c.c_void_p, c.c_uint64, c.c_void_p]),
     "psk_count_dict_batch": (c.c_int, [c.c_void_p, c.c_int, c.POINTER(c.c_char_p), c.POINTER(c.c_size_t), c.c_int, c.c_void_p,
                                        c.c_uint64, c.c_void_p, c.c_int]),

@@ -1,0 +1,428 @@
+// C-SVC fits of the reference's `-bc SVM` branch: GridSearchCV(SVC(kernel, probability=True, max_iter, tol), {'C': 1/alphas})
+// (set_model / fit_model, modeling.py:1025-1029, :1050-1056, :1086-1090).  scikit-learn's SVC is libsvm; at the reference's
+// default --max_iter 1000 a fit on a non-separable design stops at the cap, and what GridSearchCV then scores is the 1000th
+// iterate of libsvm's solver, not the optimum.  So this is libsvm's Solver::Solve WITHOUT shrinking restated step for step:
+//   min 1/2 a'Qa - e'a,  0 <= a_i <= C,  y'a = 0,  Q_ij = y_i y_j K_ij,  class 0 is +1, no class weights
+//   * solver index order = the fit's training samples, class 0 first, then class 1, input order kept within a class;
+//     alpha = 0, G = -1
+//   * working set by WSS2 (Fan, Chen, Lin 2005): i = arg max of -y_t G_t over I_up, the LAST maximal index; j = arg min of
+//     -(Gmax + y_j G_j)^2 / max(QD_i + QD_j - 2 y_i y_j Q_ij, 1e-12) over I_low with a positive numerator, the LAST
+//     minimal index; stop when Gmax + Gmax2 < tol (not counted as an iteration) or after max_iter iterations
+//   * the two-variable update with libsvm's clipping, then G_k += Q_ik d_alpha_i + Q_jk d_alpha_j in that operation order,
+//     f64 throughout, no FMA fusion (the translation unit is compiled -ffp-contract=off)
+//   * Q entries are float (libsvm's Qfloat): K evaluated in double, times y_i y_j, rounded; QD is double
+//   * rho: mean of y_i G_i over the free variables, else the midpoint of the bounds (calculate_rho)
+// Two kernels: svc_gram_kernel builds the sample x sample dot products once per call (popcounts of bit-packed rows for a
+// 0/1 design, which are exact in float; f64 dot products otherwise); svc_smo_kernel runs one workgroup of four waves per
+// fit with alpha, G, QD, the index list, the current row Q_i and the labels in LDS (33 B per training sample, 135 KB at
+// 4096 samples).
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "dev_utils.h"
+#include "psk_internal.h"
+
+namespace {
+
+constexpr int SVC_THREADS = 256;
+constexpr int SVC_MAX_N = 4096;
+constexpr int SVC_TILE = 16;
+constexpr double SVC_TAU = 1e-12;
+constexpr int SVC_RED_BYTES = 28 * 8 + 12 * 4;   // 28 doubles and 12 ints of reduction slots: 272 B, a multiple of 16
+
+// ---- Gram matrix -------------------------------------------------------------------------------------------------------
+// D[i][j] = popc(r_i & r_j) over the W u64 words of the bit-packed rows: a 16 x 16 tile per workgroup, the rows of the
+// tile staged in LDS 16 words at a time.
+__global__ __launch_bounds__(SVC_TILE * SVC_TILE) void svc_gram_bits_kernel(const uint64_t *__restrict__ bits, int n, int W,
+                                                                            float *__restrict__ D)
+{
+    __shared__ uint64_t ra[SVC_TILE][SVC_TILE + 1], rb[SVC_TILE][SVC_TILE + 1];
+    const int tx = threadIdx.x & (SVC_TILE - 1), ty = threadIdx.x / SVC_TILE;
+    const int i0 = blockIdx.y * SVC_TILE, j0 = blockIdx.x * SVC_TILE;
+    uint32_t s = 0;
+    for (int w0 = 0; w0 < W; w0 += SVC_TILE) {
+        const int w = w0 + tx;
+        ra[ty][tx] = (i0 + ty < n && w < W) ? bits[(size_t)(i0 + ty) * W + w] : 0;
+        rb[ty][tx] = (j0 + ty < n && w < W) ? bits[(size_t)(j0 + ty) * W + w] : 0;
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < SVC_TILE; q++) s += (uint32_t)__popcll(ra[ty][q] & rb[tx][q]);
+        __syncthreads();
+    }
+    if (i0 + ty < n && j0 + tx < n) D[(size_t)(i0 + ty) * n + j0 + tx] = (float)s;
+}
+
+// D[i][j] = sum_k x_ik x_jk in f64, k ascending (libsvm's dot() order), for designs that are not 0/1.
+__global__ __launch_bounds__(SVC_TILE * SVC_TILE) void svc_gram_dense_kernel(const float *__restrict__ X, int n, int p,
+                                                                             double *__restrict__ D)
+{
+    __shared__ float ra[SVC_TILE][SVC_TILE + 1], rb[SVC_TILE][SVC_TILE + 1];
+    const int tx = threadIdx.x & (SVC_TILE - 1), ty = threadIdx.x / SVC_TILE;
+    const int i0 = blockIdx.y * SVC_TILE, j0 = blockIdx.x * SVC_TILE;
+    double s = 0.0;
+    for (int k0 = 0; k0 < p; k0 += SVC_TILE) {
+        const int k = k0 + tx;
+        ra[ty][tx] = (i0 + ty < n && k < p) ? X[(size_t)(i0 + ty) * p + k] : 0.0f;
+        rb[ty][tx] = (j0 + ty < n && k < p) ? X[(size_t)(j0 + ty) * p + k] : 0.0f;
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < SVC_TILE; q++) s += (double)ra[ty][q] * (double)rb[tx][q];
+        __syncthreads();
+    }
+    if (i0 + ty < n && j0 + tx < n) D[(size_t)(i0 + ty) * n + j0 + tx] = s;
+}
+
+template <typename T> __global__ void svc_diag_kernel(const T *__restrict__ D, int n, double *__restrict__ diag)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) diag[i] = (double)D[(size_t)i * n + i];
+}
+
+// ---- SMO ---------------------------------------------------------------------------------------------------------------
+// (value, index) maximum with the LAST index winning among equal values: a total order, so the result does not depend on
+// the order in which lanes and waves are combined.
+__device__ __forceinline__ bool svc_better(double v, int i, double bv, int bi) { return v > bv || (v == bv && i > bi); }
+
+__device__ __forceinline__ void svc_wave_argmax(double &v, int &i)
+{
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        const double ov = psk_shfl_xor_f64(v, d);
+        const int oi = __shfl_xor(i, d, 64);
+        if (svc_better(ov, oi, v, i)) { v = ov; i = oi; }
+    }
+}
+
+__device__ __forceinline__ double svc_wave_max(double v)
+{
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v = fmax(v, psk_shfl_xor_f64(v, d));
+    return v;
+}
+
+// K(a, b) in double from the dot product d_ab and the squared norms (rbf: libsvm's exp(-gamma (|a|^2 + |b|^2 - 2 a.b)))
+template <int KERN> __device__ __forceinline__ double svc_kval(double dab, double sa, double sb, double gamma)
+{
+    if (KERN == 0) return dab;
+    return exp(-gamma * (sa + sb - 2 * dab));
+}
+
+template <typename T, int KERN>
+__global__ __launch_bounds__(SVC_THREADS) void svc_smo_kernel(
+    const T *__restrict__ D, const double *__restrict__ diag, const int32_t *__restrict__ y01, const int32_t *__restrict__ fold,
+    int n, int l_cap, const double *__restrict__ fit_C, const double *__restrict__ fit_gamma,
+    const int32_t *__restrict__ fit_fold, double tol, int max_iter, double *__restrict__ dual, double *__restrict__ rho_out,
+    double *__restrict__ dec, int32_t *__restrict__ iters)
+{
+    // all LDS in the dynamic region, every carve a multiple of 16 bytes (l_cap is a multiple of 8): the reductions' slots
+    // first (SVC_RED_BYTES), then the per-sample arrays
+    extern __shared__ __attribute__((aligned(16))) double svc_lds[];
+    double *r1v = svc_lds, *r1g = r1v + 4, *r2v = r1g + 4;
+    double(*rr)[4] = reinterpret_cast<double(*)[4]>(r2v + 4);
+    int *r1i = reinterpret_cast<int *>(svc_lds + 28), *r2i = r1i + 4;
+    uint32_t *scan_lds = reinterpret_cast<uint32_t *>(r2i + 4);
+    double *alpha = svc_lds + SVC_RED_BYTES / 8, *G = alpha + l_cap, *SQ = G + l_cap;   // SQ: x_k . x_k (QD of the linear kernel)
+    int32_t *idx = reinterpret_cast<int32_t *>(SQ + l_cap);
+    float *Qi = reinterpret_cast<float *>(idx + l_cap);
+    int8_t *ys = reinterpret_cast<int8_t *>(Qi + l_cap);
+
+    const int fit = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const double C = fit_C[fit], gamma = KERN ? fit_gamma[fit] : 0.0;
+    const int tf = fit_fold[fit];
+
+    // index list: training samples of class 0 in input order, then those of class 1 (svm_group_classes)
+    int l = 0;
+    for (int cls = 0; cls < 2; cls++)
+        for (int s0 = 0; s0 < n; s0 += SVC_THREADS) {
+            const int s = s0 + tid;
+            const uint32_t take = (s < n && fold[s] != tf && (y01[s] != 0) == (cls != 0)) ? 1u : 0u;
+            uint32_t total;
+            const uint32_t off = psk_block_excl_scan_u32<SVC_THREADS>(take, &total, scan_lds);
+            if (take) {
+                const int k = l + (int)off;
+                idx[k] = s;
+                ys[k] = cls ? -1 : 1;
+                alpha[k] = 0.0;
+                G[k] = -1.0;
+                SQ[k] = diag[s];
+            }
+            l += (int)total;
+        }
+    __syncthreads();
+
+    int iter = 0;
+    while (max_iter == -1 || iter < max_iter) {
+        // i and Gmax over I_up; Gmax2 over I_low (it does not depend on i)
+        double bv = -INFINITY, g2 = -INFINITY;
+        int bi = -1;
+        for (int k = tid; k < l; k += SVC_THREADS) {
+            const double a = alpha[k], g = G[k];
+            if (ys[k] > 0) {
+                if (a < C && -g >= bv) { bv = -g; bi = k; }
+                if (a > 0.0) g2 = fmax(g2, g);
+            } else {
+                if (a > 0.0 && g >= bv) { bv = g; bi = k; }
+                if (a < C) g2 = fmax(g2, -g);
+            }
+        }
+        svc_wave_argmax(bv, bi);
+        g2 = svc_wave_max(g2);
+        if (lane == 0) { r1v[wave] = bv; r1i[wave] = bi; r1g[wave] = g2; }
+        __syncthreads();
+        double Gmax = r1v[0], Gmax2 = r1g[0];
+        int i = r1i[0];
+#pragma unroll
+        for (int w = 1; w < 4; w++) {
+            if (svc_better(r1v[w], r1i[w], Gmax, i)) { Gmax = r1v[w]; i = r1i[w]; }
+            Gmax2 = fmax(Gmax2, r1g[w]);
+        }
+        if (i < 0 || Gmax + Gmax2 < tol) break;
+
+        // row i of Q, kept in LDS for the update; j over I_low
+        const int yi = ys[i], si = idx[i];
+        const double sqi = SQ[i], QDi = KERN ? 1.0 : sqi;
+        const T *Di = D + (size_t)si * n;
+        bv = -INFINITY;
+        bi = -1;
+        for (int k = tid; k < l; k += SVC_THREADS) {
+            const int yk = ys[k];
+            const double sqk = SQ[k], QDk = KERN ? 1.0 : sqk;
+            const float q = (float)((double)(yi * yk) * svc_kval<KERN>((double)Di[idx[k]], sqi, sqk, gamma));
+            Qi[k] = q;
+            const double a = alpha[k], g = G[k];
+            double gd, qc;
+            bool in_low;
+            if (yk > 0) {
+                in_low = a > 0.0;
+                gd = Gmax + g;
+                qc = QDi + QDk - 2.0 * yi * (double)q;
+            } else {
+                in_low = a < C;
+                gd = Gmax - g;
+                qc = QDi + QDk + 2.0 * yi * (double)q;
+            }
+            if (in_low && gd > 0.0) {
+                const double o = (gd * gd) / (qc > 0.0 ? qc : SVC_TAU);   // -obj_diff: its maximum is obj_diff's minimum
+                if (o >= bv) { bv = o; bi = k; }
+            }
+        }
+        svc_wave_argmax(bv, bi);
+        if (lane == 0) { r2v[wave] = bv; r2i[wave] = bi; }
+        __syncthreads();
+        double ov = r2v[0];
+        int j = r2i[0];
+#pragma unroll
+        for (int w = 1; w < 4; w++)
+            if (svc_better(r2v[w], r2i[w], ov, j)) { ov = r2v[w]; j = r2i[w]; }
+        if (j < 0) break;
+        iter++;
+
+        // the two-variable update, by every thread for itself from the same LDS words
+        const int yj = ys[j], sj = idx[j];
+        const double sqj = SQ[j], QDj = KERN ? 1.0 : sqj;
+        const double oai = alpha[i], oaj = alpha[j], Gi = G[i], Gj = G[j], Qij = (double)Qi[j];
+        double ai = oai, aj = oaj;
+        if (yi != yj) {
+            double qc = QDi + QDj + 2 * Qij;
+            if (qc <= 0.0) qc = SVC_TAU;
+            const double delta = (-Gi - Gj) / qc, diff = ai - aj;
+            ai += delta;
+            aj += delta;
+            if (diff > 0.0) {
+                if (aj < 0.0) { aj = 0.0; ai = diff; }
+            } else {
+                if (ai < 0.0) { ai = 0.0; aj = -diff; }
+            }
+            if (diff > 0.0) {   // C_i - C_j = 0: no class weights
+                if (ai > C) { ai = C; aj = C - diff; }
+            } else {
+                if (aj > C) { aj = C; ai = C + diff; }
+            }
+        } else {
+            double qc = QDi + QDj - 2 * Qij;
+            if (qc <= 0.0) qc = SVC_TAU;
+            const double delta = (Gi - Gj) / qc, sum = ai + aj;
+            ai -= delta;
+            aj += delta;
+            if (sum > C) {
+                if (ai > C) { ai = C; aj = sum - C; }
+            } else {
+                if (aj < 0.0) { aj = 0.0; ai = sum; }
+            }
+            if (sum > C) {
+                if (aj > C) { aj = C; ai = sum - C; }
+            } else {
+                if (ai < 0.0) { ai = 0.0; aj = sum; }
+            }
+        }
+        const double dai = ai - oai, daj = aj - oaj;
+        __syncthreads();   // every thread has read alpha and G of i and j
+        const T *Dj = D + (size_t)sj * n;
+        for (int k = tid; k < l; k += SVC_THREADS) {
+            const double sqk = SQ[k];
+            const float qj = (float)((double)(yj * ys[k]) * svc_kval<KERN>((double)Dj[idx[k]], sqj, sqk, gamma));
+            G[k] += (double)Qi[k] * dai + (double)qj * daj;
+        }
+        if (tid == (i & (SVC_THREADS - 1))) alpha[i] = ai;
+        if (tid == (j & (SVC_THREADS - 1))) alpha[j] = aj;
+        // the next pass reads only the thread's own k; the reductions' barriers order everything else
+    }
+    __syncthreads();
+
+    // rho (calculate_rho)
+    double nfree = 0.0, sfree = 0.0, ub = INFINITY, lb = -INFINITY;
+    for (int k = tid; k < l; k += SVC_THREADS) {
+        const double a = alpha[k], yG = (double)ys[k] * G[k];
+        if (a >= C) {
+            if (ys[k] < 0) ub = fmin(ub, yG); else lb = fmax(lb, yG);
+        } else if (a <= 0.0) {
+            if (ys[k] > 0) ub = fmin(ub, yG); else lb = fmax(lb, yG);
+        } else {
+            nfree += 1.0;
+            sfree += yG;
+        }
+    }
+    nfree = psk_wave_sum_f64_dpp(nfree);
+    sfree = psk_wave_sum_f64_dpp(sfree);
+    ub = -svc_wave_max(-ub);
+    lb = svc_wave_max(lb);
+    if (lane == 0) { rr[0][wave] = nfree; rr[1][wave] = sfree; rr[2][wave] = ub; rr[3][wave] = lb; }
+    __syncthreads();
+    nfree = (rr[0][0] + rr[0][1]) + (rr[0][2] + rr[0][3]);
+    sfree = (rr[1][0] + rr[1][1]) + (rr[1][2] + rr[1][3]);
+    ub = fmin(fmin(rr[2][0], rr[2][1]), fmin(rr[2][2], rr[2][3]));
+    lb = fmax(fmax(rr[3][0], rr[3][1]), fmax(rr[3][2], rr[3][3]));
+    const double rho = nfree > 0.0 ? sfree / nfree : (ub + lb) / 2;
+
+    for (int k = tid; k < l; k += SVC_THREADS) dual[(size_t)fit * n + idx[k]] = (double)ys[k] * alpha[k];
+    if (tid == 0) { rho_out[fit] = rho; iters[fit] = iter; }
+    // decision values of every sample, support vectors in solver order (svm_predict_values)
+    for (int s = tid; s < n; s += SVC_THREADS) {
+        const double sqs = KERN ? diag[s] : 0.0;
+        double sum = 0.0;
+        for (int k = 0; k < l; k++) {
+            const double a = alpha[k];
+            if (a != 0.0)
+                sum += ((double)ys[k] * a) * svc_kval<KERN>((double)D[(size_t)idx[k] * n + s], SQ[k], sqs, gamma);
+        }
+        dec[(size_t)fit * n + s] = sum - rho;
+    }
+}
+
+struct SvcBufs {
+    void *x = nullptr, *D = nullptr, *diag = nullptr, *y = nullptr, *fold = nullptr, *C = nullptr, *gamma = nullptr,
+         *ffold = nullptr, *dual = nullptr, *rho = nullptr, *dec = nullptr, *iters = nullptr;
+    ~SvcBufs()
+    {
+        void *ps[] = {x, D, diag, y, fold, C, gamma, ffold, dual, rho, dec, iters};
+        for (void *q : ps) if (q) (void)hipFree(q);
+    }
+};
+
+#define SVC_ALLOC(ptr, bytes) PSK_HIP(ctx, hipMalloc(&(ptr), (bytes) ? (bytes) : 8))
+
+template <typename T, int KERN>
+int svc_launch_smo(psk_ctx *ctx, SvcBufs &b, int n, int n_fits, double tol, int max_iter)
+{
+    const int l_cap = (n + 7) & ~7;
+    const size_t lds = SVC_RED_BYTES + (size_t)l_cap * (3 * 8 + 4 + 4 + 1);
+    auto kern = svc_smo_kernel<T, KERN>;
+    if (lds > 64 * 1024)
+        PSK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    kern<<<n_fits, SVC_THREADS, lds, ctx->stream>>>((const T *)b.D, (const double *)b.diag, (const int32_t *)b.y,
+                                                    (const int32_t *)b.fold, n, l_cap, (const double *)b.C,
+                                                    (const double *)b.gamma, (const int32_t *)b.ffold, tol, max_iter,
+                                                    (double *)b.dual, (double *)b.rho, (double *)b.dec, (int32_t *)b.iters);
+    PSK_HIP(ctx, hipGetLastError());
+    return PSK_OK;
+}
+
+}  // namespace
+
+extern "C" int psk_svc_fit(psk_ctx *ctx, const float *X, const int32_t *y01, int n, int p, const int32_t *fold,
+                           const double *fit_C, const double *fit_gamma, const int32_t *fit_fold, int n_fits, int kernel,
+                           double tol, int max_iter, double *dual_out, double *rho_out, double *dec_out, int32_t *iters_out)
+{
+    if (!ctx) return PSK_EINVAL;
+    if (!X || !y01 || !fold || !fit_C || !fit_fold || !dual_out || !rho_out || !dec_out)
+        return psk_fail(ctx, PSK_EINVAL, "null buffer");
+    if (n < 2 || p < 1 || n_fits < 1) return psk_fail(ctx, PSK_EINVAL, "bad problem shape n=%d p=%d fits=%d", n, p, n_fits);
+    if (kernel != 0 && kernel != 1) return psk_fail(ctx, PSK_EINVAL, "kernel must be 0 (linear) or 1 (rbf), got %d", kernel);
+    if (kernel == 1 && !fit_gamma) return psk_fail(ctx, PSK_EINVAL, "the rbf kernel needs fit_gamma");
+    if (!(tol > 0.0) || (max_iter < 1 && max_iter != -1))
+        return psk_fail(ctx, PSK_EINVAL, "tol must be > 0 and max_iter >= 1 or -1 (no limit)");
+    if (n > SVC_MAX_N)
+        return psk_fail(ctx, PSK_ERANGE, "psk_svc_fit holds the sample x sample kernel matrix on the device: at most %d samples, got %d",
+                        SVC_MAX_N, n);
+    for (int f = 0; f < n_fits; f++) {
+        if (!(fit_C[f] > 0.0)) return psk_fail(ctx, PSK_EINVAL, "fit %d: C must be > 0", f);
+        if (kernel == 1 && !(fit_gamma[f] >= 0.0)) return psk_fail(ctx, PSK_EINVAL, "fit %d: gamma must be >= 0", f);
+        int c0 = 0, c1 = 0;
+        for (int i = 0; i < n; i++)
+            if (fold[i] != fit_fold[f]) { if (y01[i]) c1++; else c0++; }
+        if (!c0 || !c1) return psk_fail(ctx, PSK_EINVAL, "fit %d trains on one class only (%d of class 0, %d of class 1)", f, c0, c1);
+    }
+    bool binary = true;
+    for (size_t t = 0; t < (size_t)n * p && binary; t++) binary = X[t] == 0.0f || X[t] == 1.0f;
+
+    PSK_HIP(ctx, hipSetDevice(ctx->device));
+    SvcBufs b;
+    const dim3 tiles(div_up(n, SVC_TILE), div_up(n, SVC_TILE));
+    SVC_ALLOC(b.diag, (size_t)n * 8);
+    if (binary) {
+        const int W = (p + 63) / 64;
+        std::vector<uint64_t> bits((size_t)n * W, 0);
+        for (int i = 0; i < n; i++)
+            for (int j = 0; j < p; j++)
+                if (X[(size_t)i * p + j] != 0.0f) bits[(size_t)i * W + (j >> 6)] |= 1ull << (j & 63);
+        SVC_ALLOC(b.x, bits.size() * 8);
+        SVC_ALLOC(b.D, (size_t)n * n * 4);
+        PSK_HIP(ctx, hipMemcpyAsync(b.x, bits.data(), bits.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+        PSK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // `bits` leaves scope
+        svc_gram_bits_kernel<<<tiles, SVC_TILE * SVC_TILE, 0, ctx->stream>>>((const uint64_t *)b.x, n, W, (float *)b.D);
+        svc_diag_kernel<float><<<div_up(n, 256), 256, 0, ctx->stream>>>((const float *)b.D, n, (double *)b.diag);
+    } else {
+        SVC_ALLOC(b.x, (size_t)n * p * 4);
+        SVC_ALLOC(b.D, (size_t)n * n * 8);
+        PSK_HIP(ctx, hipMemcpyAsync(b.x, X, (size_t)n * p * 4, hipMemcpyHostToDevice, ctx->stream));
+        svc_gram_dense_kernel<<<tiles, SVC_TILE * SVC_TILE, 0, ctx->stream>>>((const float *)b.x, n, p, (double *)b.D);
+        svc_diag_kernel<double><<<div_up(n, 256), 256, 0, ctx->stream>>>((const double *)b.D, n, (double *)b.diag);
+    }
+    PSK_HIP(ctx, hipGetLastError());
+
+    std::vector<double> gam(n_fits, 0.0);
+    if (kernel == 1) memcpy(gam.data(), fit_gamma, (size_t)n_fits * 8);
+    SVC_ALLOC(b.y, (size_t)n * 4);
+    SVC_ALLOC(b.fold, (size_t)n * 4);
+    SVC_ALLOC(b.C, (size_t)n_fits * 8);
+    SVC_ALLOC(b.gamma, (size_t)n_fits * 8);
+    SVC_ALLOC(b.ffold, (size_t)n_fits * 4);
+    SVC_ALLOC(b.dual, (size_t)n_fits * n * 8);
+    SVC_ALLOC(b.rho, (size_t)n_fits * 8);
+    SVC_ALLOC(b.dec, (size_t)n_fits * n * 8);
+    SVC_ALLOC(b.iters, (size_t)n_fits * 4);
+    PSK_HIP(ctx, hipMemcpyAsync(b.y, y01, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    PSK_HIP(ctx, hipMemcpyAsync(b.fold, fold, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    PSK_HIP(ctx, hipMemcpyAsync(b.C, fit_C, (size_t)n_fits * 8, hipMemcpyHostToDevice, ctx->stream));
+    PSK_HIP(ctx, hipMemcpyAsync(b.gamma, gam.data(), (size_t)n_fits * 8, hipMemcpyHostToDevice, ctx->stream));
+    PSK_HIP(ctx, hipMemcpyAsync(b.ffold, fit_fold, (size_t)n_fits * 4, hipMemcpyHostToDevice, ctx->stream));
+    PSK_HIP(ctx, hipMemsetAsync(b.dual, 0, (size_t)n_fits * n * 8, ctx->stream));   // samples a fit did not train on
+    if (binary) {
+        if (kernel == 0) PSK_TRY((svc_launch_smo<float, 0>(ctx, b, n, n_fits, tol, max_iter)));
+        else PSK_TRY((svc_launch_smo<float, 1>(ctx, b, n, n_fits, tol, max_iter)));
+    } else {
+        if (kernel == 0) PSK_TRY((svc_launch_smo<double, 0>(ctx, b, n, n_fits, tol, max_iter)));
+        else PSK_TRY((svc_launch_smo<double, 1>(ctx, b, n, n_fits, tol, max_iter)));
+    }
+    std::vector<int32_t> it(n_fits);
+    PSK_HIP(ctx, hipMemcpyAsync(dual_out, b.dual, (size_t)n_fits * n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    PSK_HIP(ctx, hipMemcpyAsync(rho_out, b.rho, (size_t)n_fits * 8, hipMemcpyDeviceToHost, ctx->stream));
+    PSK_HIP(ctx, hipMemcpyAsync(dec_out, b.dec, (size_t)n_fits * n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    PSK_HIP(ctx, hipMemcpyAsync(it.data(), b.iters, (size_t)n_fits * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PSK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (iters_out) memcpy(iters_out, it.data(), (size_t)n_fits * 4);
+    return PSK_OK;
+}

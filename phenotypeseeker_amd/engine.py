@@ -436,6 +436,28 @@ class PskContext:
                                                 _ptr(coef), _ptr(icpt), _ptr(iters)), "psk_logreg_l2_fit")
         return coef, icpt, iters
 
+    def svc_fit(self, X, y01, fold, fit_C, fit_fold, kernel="linear", fit_gamma=None, tol=1e-3, max_iter=-1):
+        """C-SVC fits (psk_svc_fit): libsvm's solver without shrinking, one workgroup per fit.  Returns
+        (dual[n_fits][n], rho[n_fits], dec[n_fits][n], iters[n_fits]) in libsvm's sign: class 0 is positive."""
+        if kernel not in ("linear", "rbf"):
+            raise ValueError("kernel must be 'linear' or 'rbf', got %r" % (kernel,))
+        X = np.ascontiguousarray(X, dtype=np.float32)
+        n, p = X.shape
+        y = np.ascontiguousarray(y01, dtype=np.int32)
+        fold = np.ascontiguousarray(fold, dtype=np.int32)
+        fit_C = np.ascontiguousarray(fit_C, dtype=np.float64)
+        fit_fold = np.ascontiguousarray(fit_fold, dtype=np.int32)
+        nf = len(fit_C)
+        if kernel == "rbf":
+            fit_gamma = np.ascontiguousarray(np.broadcast_to(np.asarray(fit_gamma, dtype=np.float64), (nf,)))
+        dual, rho, dec = np.zeros((nf, n)), np.zeros(nf), np.zeros((nf, n))
+        iters = np.zeros(nf, dtype=np.int32)
+        self._check(self._lib.psk_svc_fit(self._h, _ptr(X), _ptr(y), n, p, _ptr(fold), _ptr(fit_C),
+                                          _ptr(fit_gamma) if kernel == "rbf" else None, _ptr(fit_fold), nf,
+                                          1 if kernel == "rbf" else 0, float(tol), int(max_iter), _ptr(dual), _ptr(rho),
+                                          _ptr(dec), _ptr(iters)), "psk_svc_fit")
+        return dual, rho, dec, iters
+
     # -- population-structure weights --------------------------------------------------------------
     def minhash_sketch(self, data, k=21, sketch_size=1000, seed=42):
         data = bytes(data)

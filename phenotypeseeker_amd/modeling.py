@@ -29,7 +29,7 @@ from . import formats, metrics, _stats
 from .engine import PskContext
 from . import _lib
 from ._lib import PSK_EGZIP, PskError
-from .model import GridSearch, L1LogisticRegression, L2LogisticRegression, LassoRegression, RidgeRegression
+from .model import SVC, GridSearch, L1LogisticRegression, L2LogisticRegression, LassoRegression, RidgeRegression
 
 RED_BANNER = "\x1b[1;1;101m%s\x1b[0m\n"
 GREEN = "\x1b[1;32m%s\x1b[0m"
@@ -371,18 +371,28 @@ class Input:
                 raise SystemExit("Only the linear (Lasso) regressor runs on the GPU engine, got %r." % regressor)
             phenotypes.model_name_long, phenotypes.model_name_short = "linear regression", "linreg"
         else:
-            if binary_classifier != "log":
+            phenotypes.binary_classifier = "log"
+            if binary_classifier == "SVM" and _lib.env_flag("PSK_SVM"):
+                # set_model (:1025-1029): SVC(kernel, probability=True) over C = 1 / alphas.  The reference searches the rbf
+                # kernel with an unseeded RandomizedSearchCV (:1091-1095): not offered from the command line
+                if kernel != "linear":
+                    raise SystemExit("The support vector machine on the GPU engine takes --kernel linear only, got %r." % kernel)
+                phenotypes.binary_classifier, phenotypes.kernel = "SVM", kernel
+                phenotypes.model_name_long, phenotypes.model_name_short = "support vector machine", "SVM"
+            elif binary_classifier != "log":
                 raise SystemExit("Only the logistic-regression classifier runs on the GPU engine, got %r "
                                  "(SVM/RF/DT/NB are outside the accelerated path)." % binary_classifier)
-            phenotypes.model_name_long, phenotypes.model_name_short = "logistic regression", "log_reg"
+            else:
+                phenotypes.model_name_long, phenotypes.model_name_short = "logistic regression", "log_reg"
             # get_logreg_solver (:245-264): L1 -> liblinear (saga's objective leaves the intercept free and
             # is not implemented); L2 -> lbfgs by default, all five names share one strictly convex optimum
-            if phenotypes.penalty == "L1":
+            is_log = phenotypes.binary_classifier == "log"
+            if is_log and phenotypes.penalty == "L1":
                 if logreg_solver not in (None, "liblinear"):
                     raise SystemExit("Logistic Regression with L1 penalty on the GPU engine implements the "
                                      "liblinear objective only, got {}.".format(logreg_solver))
                 phenotypes.logreg_solver = "liblinear"
-            elif phenotypes.penalty == "L2":
+            elif is_log and phenotypes.penalty == "L2":
                 if logreg_solver is None:
                     logreg_solver = "lbfgs"
                 if logreg_solver not in ("liblinear", "newton-cg", "lbfgs", "sag", "saga"):
@@ -408,6 +418,8 @@ class phenotypes:
     kmer_limit = None
     omit_B = None
     penalty = None
+    binary_classifier = "log"
+    kernel = None
     logreg_solver = None
     max_iter = None
     tol = None
@@ -657,6 +669,8 @@ class phenotypes:
     def _new_estimator(self):
         if self.pred_scale == "binary":
             grid = [1.0 / a for a in self.alphas]
+            if self.binary_classifier == "SVM":
+                return SVC(kernel=self.kernel, probability=True, max_iter=self.max_iter, tol=self.tol), "C", grid
             if self.penalty == "L2":
                 return L2LogisticRegression(tol=self.tol, max_iter=self.max_iter, solver=self.logreg_solver), "C", grid
             return L1LogisticRegression(tol=self.tol, max_iter=self.max_iter), "C", grid
@@ -669,6 +683,10 @@ class phenotypes:
         est, pname, grid = self._new_estimator()
         self.model = est
         self.model_fitted = GridSearch(est, pname, grid, self.n_splits_cv_inner).fit(X, y, ctx)
+        if isinstance(est, SVC) and int(est.max_iter) != -1 and np.any(self.model_fitted.n_iter_ >= int(est.max_iter)):
+            # scikit-learn's ConvergenceWarning (svm/_base.py, _warn_from_fit_status), once per grid search
+            _err("ConvergenceWarning: Solver terminated early (max_iter=%i).  Consider pre-processing your data with "
+                 "StandardScaler or MinMaxScaler.\n" % int(est.max_iter))
 
     def machine_learning_modelling(self, ctx):
         _err("\x1b[1;32m\t" + self.name + ".\x1b[0m\n")

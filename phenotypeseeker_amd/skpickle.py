@@ -156,11 +156,34 @@ class LinearModel:
         return np.vstack([1.0 - p, p]).T
 
 
+def _svc_from_state(est):
+    """model.SVC from the attribute dictionary of a fitted two-class dense sklearn.svm.SVC with a linear or rbf kernel and a
+    Platt pair: the same decision values, libsvm's vote on a zero and its probability iteration, not the logistic.  None
+    for anything else (more classes, sparse fits, other kernels, probability=False, class weights)."""
+    import numpy as np
+    from .model import SVC
+    d = est.__dict__
+    classes = d.get("classes_")
+    if (classes is None or list(classes) != [0, 1] or d.get("_sparse") or d.get("kernel") not in ("linear", "rbf")
+            or len(d.get("_probA", ())) != 1 or len(d.get("_probB", ())) != 1 or d.get("class_weight") is not None):
+        return None
+    m = SVC(C=d["C"], kernel=d["kernel"], gamma=d["gamma"], tol=d["tol"], max_iter=d["max_iter"], probability=True)
+    m.support_ = np.asarray(d["support_"])
+    m.support_vectors_ = np.asarray(d["support_vectors_"], dtype=np.float64)
+    m.n_support_ = np.asarray(d["_n_support"])
+    m.dual_coef_, m.intercept_ = np.asarray(d["dual_coef_"], dtype=np.float64), np.asarray(d["intercept_"], dtype=np.float64)
+    m._gamma = float(d["_gamma"])
+    m.probA_, m.probB_ = np.asarray(d["_probA"], dtype=np.float64), np.asarray(d["_probB"], dtype=np.float64)
+    m.n_features_in_ = int(m.support_vectors_.shape[1])
+    return m
+
+
 def load_linear_package(path):
     """The model package of `path` ({'model', 'kmers', 'pca', 'pred_scale'}) with 'model' as a LinearModel -- for files
     that are plain pickles of a (grid search over a) binary linear classifier or a linear regressor, which is what
-    `modeling` writes.  None for anything else (joblib-wrapped arrays, multi-class models, other estimators, a PCA
-    pipeline): the caller then takes joblib.load and scikit-learn itself."""
+    `modeling` writes; a two-class SVC with a Platt pair comes back as model.SVC (_svc_from_state).  None for anything else
+    (joblib-wrapped arrays, multi-class models, other estimators, a PCA pipeline): the caller then takes joblib.load and
+    scikit-learn itself."""
     try:
         with open(path, "rb") as f:
             pkg = _StubUnpickler(f).load()
@@ -170,7 +193,7 @@ def load_linear_package(path):
         est = getattr(m, "best_estimator_", m)
         kind = type(est).__name__
         coef, icpt = getattr(est, "coef_", None), getattr(est, "intercept_", None)
-        if coef is None or icpt is None:
+        if kind != "SVC" and (coef is None or icpt is None):   # (an SVC keeps its support vectors, coef_ is derived)
             return None
         if kind in ("LogisticRegression",):
             classes = getattr(est, "classes_", None)
@@ -183,6 +206,10 @@ def load_linear_package(path):
             model = LinearModel(coef, icpt, classes)
         elif kind in ("Lasso", "Ridge"):
             model = LinearModel(coef, icpt, None)
+        elif kind == "SVC":
+            model = _svc_from_state(est)
+            if model is None:
+                return None
         else:
             return None
         out = dict(pkg)
