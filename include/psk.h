@@ -308,6 +308,29 @@ int psk_svc_fit(psk_ctx *ctx, const float *X, const int32_t *y01, int n, int p, 
                 const double *fit_C, const double *fit_gamma, const int32_t *fit_fold, int n_fits, int kernel,
                 double tol, int max_iter, double *dual_out, double *rho_out, double *dec_out, int32_t *iters_out);
 
+/* ---- f6: the `-bc DT` estimator -------------------------------------------------------------------
+ * Replaces GridSearchCV over DecisionTreeClassifier() with {'max_depth': 1..10, 'criterion': ['gini', 'entropy']}
+ * (set_model, modeling.py:1032-1033, :1069-1073, :1100-1103).  Same batching and the same meaning of X, y01, n, p,
+ * fold, fit_fold, n_fits as psk_logreg_l1_fit; fit_max_depth[j] (1..10) and fit_criterion[j] (0 gini, 1 entropy)
+ * are fit j's parameters.  Per fit, scikit-learn's depth-first best-split builder with its default settings on
+ * the fit's training samples, nodes in pre-order (left subtree first; a clear bit goes left, the threshold is
+ * 0.5), the proxy improvement in f64 with scikit-learn's expressions.  Among columns whose proxy is bit-equal the
+ * LOWEST column index is taken (scikit-learn: the first in an unseeded random order); csrc/solver_tree.hip.
+ *   node_count_out[n_fits], max_depth_out[n_fits]   nodes made, deepest level reached
+ *   nodes_out[n_fits][PSK_TREE_NODE_CAP][6]          feature (-2: leaf), left, right (-1: leaf), n_node_samples,
+ *                                                    n0, n1 (training samples of class 0 / 1 in the node)
+ *   impurity_out[n_fits][PSK_TREE_NODE_CAP]          (of both, only the first node_count_out[j] slots of fit j are written)
+ *   leaf_out[n_fits][n], frac_out[n_fits][n]         for EVERY sample, held-out ones included: the leaf it lands
+ *                                                    in and that leaf's class-1 fraction n1 / n_node_samples
+ * The design must be 0/1 (PSK_EINVAL otherwise); at most 4096 samples (PSK_ERANGE beyond).  A fit whose training
+ * samples are of one class returns a single leaf.
+ */
+#define PSK_TREE_NODE_CAP 2047
+int psk_tree_fit(psk_ctx *ctx, const float *X, const int32_t *y01, int n, int p, const int32_t *fold,
+                 const int32_t *fit_max_depth, const int32_t *fit_criterion, const int32_t *fit_fold, int n_fits,
+                 int32_t *node_count_out, int32_t *max_depth_out, int32_t *nodes_out, double *impurity_out,
+                 int32_t *leaf_out, double *frac_out);
+
 /* ---- f1: fixed-dictionary counting (prediction) ---------------------------------------------
  * Replaces `gmer_counter -db <txt> <addr>` (prediction.Samples.map_samples, prediction.py:72-80):
  * occurrences, both strands with multiplicity, of each dictionary k-mer (canonical words) in

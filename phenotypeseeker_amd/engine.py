@@ -458,6 +458,37 @@ class PskContext:
                                           _ptr(dec), _ptr(iters)), "psk_svc_fit")
         return dual, rho, dec, iters
 
+    TREE_NODE_CAP = 2047      # PSK_TREE_NODE_CAP of include/psk.h
+
+    def tree_fit(self, X, y01, fold, fit_max_depth, fit_criterion, fit_fold):
+        """Decision-tree fits (psk_tree_fit): scikit-learn's depth-first best-split builder on a 0/1 design, one workgroup
+        per fit, the lowest column index among equally good splits.  fit_criterion: 0 / 'gini', 1 / 'entropy'.  Returns a
+        list with one dict per fit: node_count, max_depth, feature / left / right / n_node_samples / counts[:, 2] /
+        impurity by node (pre-order), and leaf[n], frac[n]: every sample's leaf and that leaf's class-1 fraction."""
+        X = np.ascontiguousarray(X, dtype=np.float32)
+        n, p = X.shape
+        y = np.ascontiguousarray(y01, dtype=np.int32)
+        fold = np.ascontiguousarray(fold, dtype=np.int32)
+        depth = np.ascontiguousarray(fit_max_depth, dtype=np.int32)
+        crit = np.ascontiguousarray([{"gini": 0, "entropy": 1}.get(c, c) for c in fit_criterion], dtype=np.int32)
+        fit_fold = np.ascontiguousarray(fit_fold, dtype=np.int32)
+        nf, cap = len(depth), self.TREE_NODE_CAP
+        count, deepest = np.zeros(nf, dtype=np.int32), np.zeros(nf, dtype=np.int32)
+        nodes, imp = np.zeros((nf, cap, 6), dtype=np.int32), np.zeros((nf, cap))
+        leaf, frac = np.zeros((nf, n), dtype=np.int32), np.zeros((nf, n))
+        self._check(self._lib.psk_tree_fit(self._h, _ptr(X), _ptr(y), n, p, _ptr(fold), _ptr(depth), _ptr(crit), _ptr(fit_fold),
+                                           nf, _ptr(count), _ptr(deepest), _ptr(nodes), _ptr(imp), _ptr(leaf), _ptr(frac)),
+                    "psk_tree_fit")
+        out = []
+        for j in range(nf):
+            k = int(count[j])
+            nd = nodes[j, :k]
+            out.append(dict(node_count=k, max_depth=int(deepest[j]), feature=nd[:, 0].astype(np.int64), left=nd[:, 1].astype(np.int64),
+                            right=nd[:, 2].astype(np.int64), n_node_samples=nd[:, 3].astype(np.int64),
+                            counts=nd[:, 4:6].astype(np.int64), impurity=imp[j, :k].copy(), leaf=leaf[j].astype(np.int64),
+                            frac=frac[j].copy()))
+        return out
+
     # -- population-structure weights --------------------------------------------------------------
     def minhash_sketch(self, data, k=21, sketch_size=1000, seed=42):
         data = bytes(data)

@@ -7,7 +7,8 @@ reference reads: predict / predict_proba / score, cv_results_['mean_test_score' 
 refit) are solved on the GPU in one psk_logreg_l1_fit / psk_lasso_fit launch.  `--penalty L2`
 (modeling.py:1001-1002, :1015-1019) maps to RidgeRegression / L2LogisticRegression over
 psk_ridge_fit / psk_logreg_l2_fit in the same way, `-bc SVM` (modeling.py:1025-1029) to SVC over
-psk_svc_fit, whose folds are scored from the decision values the engine returns.
+psk_svc_fit, whose folds are scored from the decision values the engine returns, and `-bc DT` (modeling.py:1032-1033) to
+DecisionTree over psk_tree_fit under a two-key grid, scored from the leaves the engine returns for every sample.
 """
 import numpy as np
 
@@ -329,6 +330,155 @@ class SVC:
         return platt_predict_proba(self._libsvm_decision(X), self.probA_[0], self.probB_[0])
 
 
+class Tree:
+    """The attributes of scikit-learn's tree_ (sklearn.tree._tree.Tree) for a two-class tree on a 0/1 design: nodes in
+    pre-order, threshold 0.5 at a split and -2 at a leaf, value the class fractions ([node_count][1][2], scikit-learn >= 1.3)."""
+    n_outputs, max_n_classes = 1, 2
+
+    def __init__(self, n_features, feature, left, right, n_node_samples, counts, impurity, max_depth):
+        self.n_features = int(n_features)
+        self.n_classes = np.array([2], dtype=np.int64)
+        self.feature = np.asarray(feature, dtype=np.int64)
+        self.children_left, self.children_right = np.asarray(left, dtype=np.int64), np.asarray(right, dtype=np.int64)
+        self.n_node_samples = np.asarray(n_node_samples, dtype=np.int64)
+        self.weighted_n_node_samples = self.n_node_samples.astype(np.float64)
+        self.impurity = np.asarray(impurity, dtype=np.float64)
+        self.threshold = np.where(self.feature >= 0, 0.5, -2.0)
+        self.value = (np.asarray(counts, dtype=np.float64) / self.weighted_n_node_samples[:, None]).reshape(-1, 1, 2)
+        self.missing_go_to_left = np.zeros(len(self.feature), dtype=np.uint8)
+        self.node_count, self.max_depth = len(self.feature), int(max_depth)
+        self.capacity = self.node_count
+
+    def apply(self, X):
+        """The leaf of every row: x <= threshold goes left."""
+        X = np.asarray(X, dtype=np.float64)
+        node = np.zeros(X.shape[0], dtype=np.int64)
+        rows = np.arange(X.shape[0])
+        for _ in range(self.max_depth):
+            f = self.feature[node]
+            inner = f >= 0
+            go_left = X[rows, np.where(inner, f, 0)] <= self.threshold[node]
+            node = np.where(inner, np.where(go_left, self.children_left[node], self.children_right[node]), node)
+        return node
+
+    def predict(self, X):
+        return self.value[self.apply(X), 0, :]
+
+    def compute_feature_importances(self, normalize=True):
+        """Tree.compute_feature_importances: the weighted impurity decrease of every split, added per feature in node order,
+        divided by the root's weight and, normalised, by their sum (f64 on the host)."""
+        imp = np.zeros(self.n_features)
+        w, I, L, R = self.weighted_n_node_samples, self.impurity, self.children_left, self.children_right
+        for k in range(self.node_count):
+            if L[k] != -1:
+                imp[self.feature[k]] += w[k] * I[k] - w[L[k]] * I[L[k]] - w[R[k]] * I[R[k]]
+        imp /= w[0]
+        if normalize:
+            total = np.sum(imp)
+            if total > 0.0:
+                imp /= total
+        return imp
+
+    def _sklearn_state(self):
+        """Tree.__getstate__ of scikit-learn 1.7: the structured node array (64 bytes a node) and the value array."""
+        dt = np.dtype({"names": ["left_child", "right_child", "feature", "threshold", "impurity", "n_node_samples",
+                                 "weighted_n_node_samples", "missing_go_to_left"],
+                       "formats": ["<i8", "<i8", "<i8", "<f8", "<f8", "<i8", "<f8", "u1"],
+                       "offsets": [0, 8, 16, 24, 32, 40, 48, 56], "itemsize": 64})
+        nodes = np.zeros(self.node_count, dtype=dt)
+        for name, v in (("left_child", self.children_left), ("right_child", self.children_right), ("feature", self.feature),
+                        ("threshold", self.threshold), ("impurity", self.impurity), ("n_node_samples", self.n_node_samples),
+                        ("weighted_n_node_samples", self.weighted_n_node_samples), ("missing_go_to_left", self.missing_go_to_left)):
+            nodes[name] = v
+        return dict(max_depth=int(self.max_depth), node_count=int(self.node_count), nodes=nodes,
+                    values=np.ascontiguousarray(self.value, dtype=np.float64))
+
+    @classmethod
+    def _from_sklearn_state(cls, n_features, state):
+        nd, val = state["nodes"], np.asarray(state["values"], dtype=np.float64)
+        t = cls(n_features, nd["feature"], nd["left_child"], nd["right_child"], nd["n_node_samples"],
+                val[:, 0, :] * np.asarray(nd["weighted_n_node_samples"], dtype=np.float64)[:, None], nd["impurity"], state["max_depth"])
+        t.threshold, t.value = np.asarray(nd["threshold"], dtype=np.float64), val.reshape(-1, 1, val.shape[-1])
+        return t
+
+
+class DecisionTree:
+    """sklearn.tree.DecisionTreeClassifier for two classes on a 0/1 design (set_model, modeling.py:1032-1033:
+    DecisionTreeClassifier() under {'max_depth': 1..10, 'criterion': ['gini', 'entropy']}) over psk_tree_fit:
+    scikit-learn's depth-first best-split builder with its default settings.  scikit-learn breaks ties between equally good
+    splits by an unseeded random feature order; here the lowest column index wins."""
+    _is_classifier = True
+    _fits_trees = True       # GridSearch scores the folds from the leaves psk_tree_fit returns for every sample
+    MAX_DEPTH = 10
+
+    def __init__(self, criterion="gini", max_depth=None):
+        if criterion not in ("gini", "entropy"):
+            raise ValueError("DecisionTree: criterion must be 'gini' or 'entropy', got %r" % (criterion,))
+        self.criterion, self.max_depth = criterion, max_depth
+        self.classes_ = np.array([0, 1])
+        self.tree_ = None
+
+    def __repr__(self):
+        parts = []
+        if self.criterion != "gini":
+            parts.append("criterion=%r" % self.criterion)
+        if self.max_depth is not None:
+            parts.append("max_depth=%r" % self.max_depth)
+        return "DecisionTreeClassifier(%s)" % ", ".join(parts)
+
+    def _clone(self, **params):
+        kw = dict(criterion=self.criterion, max_depth=self.max_depth)
+        kw.update(params)
+        return type(self)(**kw)
+
+    def _engine_fit(self, ctx, X, y, folds, fit_param, fit_fold):
+        """fit_param: one dict per fit; keys it lacks come from this estimator."""
+        y = np.asarray(y)
+        if not set(y.tolist()) <= {0, 1}:
+            raise ValueError("DecisionTree: the two classes must be labelled 0 and 1")
+        depth = [q.get("max_depth", self.max_depth) for q in fit_param]
+        crit = [q.get("criterion", self.criterion) for q in fit_param]
+        for dp in depth:
+            if dp is None or not 1 <= int(dp) <= self.MAX_DEPTH:
+                raise ValueError("DecisionTree: max_depth must be 1..%d on the GPU engine, got %r" % (self.MAX_DEPTH, dp))
+        for c in crit:
+            if c not in ("gini", "entropy"):
+                raise ValueError("DecisionTree: criterion must be 'gini' or 'entropy', got %r" % (c,))
+        return ctx.tree_fit(X, y.astype(np.int32), folds, [int(dp) for dp in depth], crit, fit_fold)
+
+    def fit(self, X, y, engine_ctx):
+        X = np.asarray(X, dtype=np.float64)
+        fits = self._engine_fit(engine_ctx, X, y, np.zeros(len(y), dtype=np.int32), [{}], [-1])
+        return self._set_fit(fits[0], X.shape[1])
+
+    def _set_fit(self, fit, n_features):
+        self.tree_ = Tree(n_features, fit["feature"], fit["left"], fit["right"], fit["n_node_samples"], fit["counts"],
+                          fit["impurity"], fit["max_depth"])
+        self.n_features_in_ = int(n_features)
+        self.n_outputs_, self.n_classes_, self.max_features_ = 1, np.int64(2), int(n_features)
+        return self
+
+    @property
+    def feature_importances_(self):
+        return self.tree_.compute_feature_importances()
+
+    def _sklearn_state(self):
+        """The fitted attributes of sklearn.tree.DecisionTreeClassifier (its __dict__ after fit, scikit-learn 1.7) without
+        tree_, which pickles by __reduce__ (skpickle.Reduced)."""
+        return dict(n_features_in_=self.n_features_in_, n_outputs_=1, classes_=np.array([0, 1]), n_classes_=np.int64(2),
+                    max_features_=self.n_features_in_)
+
+    def predict_proba(self, X):
+        return self.tree_.predict(X)
+
+    def predict(self, X):
+        # np.argmax: class 0 on equal fractions
+        return self.classes_[np.argmax(self.predict_proba(X), axis=1)]
+
+    def score(self, X, y):
+        return np.float64(np.mean(self.predict(X) == np.asarray(y)))
+
+
 def platt_sigmoid_train(dec, positive):
     """libsvm's sigmoid_train (Lin, Lin, Weng 2007): (A, B) of P(positive | f) = 1 / (1 + exp(A f + B)) by Newton's method
     with backtracking on the regularised likelihood, targets (N+ + 1)/(N+ + 2) and 1/(N- + 2).  f64, libsvm's constants."""
@@ -406,15 +556,68 @@ def platt_predict_proba(f, A, B):
 
 class GridSearch:
     """GridSearchCV(model, {'C' | 'alpha': grid}, cv=int) with refit.  `engine_ctx` is only needed
-    by fit(); the fitted object pickles without it."""
+    by fit(); the fitted object pickles without it.  GridSearch(model, {name: values, ...}, cv=int) searches several
+    parameters (DecisionTree) in ParameterGrid's order: keys sorted, the last key varying fastest."""
 
-    def __init__(self, estimator, param_name, grid, cv):
+    def __init__(self, estimator, param_name, grid=None, cv=None):
         self.estimator = estimator
-        self.param_name = param_name
-        self.param_grid = {param_name: list(grid)}
+        if isinstance(param_name, dict):
+            self.param_name = None
+            self.param_grid = {k: list(v) for k, v in param_name.items()}
+        else:
+            self.param_name = param_name
+            self.param_grid = {param_name: list(grid)}
         self.cv = int(cv)
 
+    def candidates(self):
+        """sklearn.model_selection.ParameterGrid(param_grid) as a list."""
+        import itertools
+        keys = sorted(self.param_grid)
+        return [dict(zip(keys, vals)) for vals in itertools.product(*(self.param_grid[k] for k in keys))]
+
+    def _fit_trees(self, X, y, engine_ctx):
+        """The search over an estimator whose engine call returns trees: every candidate x fold and every candidate's
+        refit in one launch; a fold is scored from the class-1 fractions the engine returns for its held-out samples."""
+        X = np.asarray(X, dtype=np.float64)
+        y = np.asarray(y)
+        if self.cv < 2:
+            raise ValueError("k-fold cross-validation requires at least one train/test split by setting "
+                             "n_splits=2 or more, got n_splits=%d." % self.cv)
+        cand = self.candidates()
+        folds = _cv.stratified_kfold(y, self.cv)
+        fit_param = [q for q in cand for _ in range(self.cv)] + list(cand)
+        fit_fold = [f for _ in cand for f in range(self.cv)] + [-1] * len(cand)
+        fits = self.estimator._engine_fit(engine_ctx, X, y, folds, fit_param, fit_fold)
+        scores = np.zeros((len(cand), self.cv))
+        for gi in range(len(cand)):
+            for f in range(self.cv):
+                te = folds == f
+                frac1 = fits[gi * self.cv + f]["frac"][te]
+                # argmax of (n0 / n, n1 / n): class 1 only when it is the strict majority of the leaf
+                scores[gi, f] = np.mean(self.estimator.classes_[(frac1 > 0.5).astype(int)] == y[te])
+        self._store(cand, scores)
+        best = self.estimator._clone(**cand[self.best_index_])
+        self.best_estimator_ = best._set_fit(fits[len(cand) * self.cv + self.best_index_], X.shape[1])
+        self.n_unique_columns_ = int(X.shape[1])
+        self.n_splits_ = self.cv
+        self.test_folds_ = folds
+        return self
+
+    def _store(self, cand, scores):
+        mean = scores.mean(axis=1)
+        self.cv_results_ = {"mean_test_score": mean, "std_test_score": scores.std(axis=1), "params": [dict(q) for q in cand],
+                            "rank_test_score": _rank_with_nan(mean)}
+        for f in range(self.cv):
+            self.cv_results_["split%d_test_score" % f] = scores[:, f]
+        self.best_index_ = int(np.argmin(self.cv_results_["rank_test_score"]))
+        self.best_params_ = dict(cand[self.best_index_])
+        self.best_score_ = float(mean[self.best_index_])
+
     def fit(self, X, y, engine_ctx):
+        if getattr(self.estimator, "_fits_trees", False):
+            return self._fit_trees(X, y, engine_ctx)
+        if self.param_name is None:
+            raise ValueError("a grid over several parameters is searched for tree estimators only")
         X_full = np.asarray(X, dtype=np.float64)
         y = np.asarray(y)
         n = len(y)
@@ -495,7 +698,13 @@ class GridSearch:
         the installed scikit-learn has no template."""
         from . import skpickle as sp
         be = self.best_estimator_
-        if isinstance(be, SVC):
+        if isinstance(be, DecisionTree):
+            est = sp.make("DecisionTreeClassifier", criterion=be.criterion, max_depth=be.max_depth, **be._sklearn_state())
+            if est is not None:
+                est.state["tree_"] = sp.Reduced("sklearn.tree._tree", "Tree", (be.n_features_in_, np.array([2], dtype=np.int64), 1),
+                                                be.tree_._sklearn_state())
+            proto = sp.make("DecisionTreeClassifier", criterion=self.estimator.criterion, max_depth=self.estimator.max_depth)
+        elif isinstance(be, SVC):
             kw = dict(kernel=be.kernel, gamma=be.gamma, tol=be.tol, max_iter=int(be.max_iter), probability=bool(be.probability))
             est = sp.make("SVC", C=be.C, **dict(kw, **be._sklearn_state()))
             proto = sp.make("SVC", **kw)
@@ -524,7 +733,15 @@ class GridSearch:
         from sklearn.linear_model import Lasso, LogisticRegression, Ridge
         from sklearn.model_selection import GridSearchCV
         be = self.best_estimator_
-        if isinstance(be, SVC):
+        if isinstance(be, DecisionTree):
+            from sklearn.tree import DecisionTreeClassifier
+            from sklearn.tree._tree import Tree as SkTree
+            est = DecisionTreeClassifier(criterion=be.criterion, max_depth=be.max_depth)
+            est.__dict__.update(be._sklearn_state())
+            est.tree_ = SkTree(be.n_features_in_, np.array([2], dtype=np.intp), 1)
+            est.tree_.__setstate__(be.tree_._sklearn_state())
+            proto = DecisionTreeClassifier(criterion=self.estimator.criterion, max_depth=self.estimator.max_depth)
+        elif isinstance(be, SVC):
             from sklearn.svm import SVC as SkSVC
             kw = dict(kernel=be.kernel, gamma=be.gamma, tol=be.tol, max_iter=int(be.max_iter), probability=bool(be.probability))
             est = SkSVC(C=be.C, **kw)
@@ -543,7 +760,7 @@ class GridSearch:
             est.coef_, est.intercept_ = be.coef_.copy(), be.intercept_
             est.n_iter_ = None if cls is Ridge else 0
             proto = cls(tol=be.tol, max_iter=int(be.max_iter))
-        if not isinstance(be, SVC):
+        if not isinstance(be, (SVC, DecisionTree)):
             est.n_features_in_ = be.n_features_in_
         gs = GridSearchCV(proto, self.param_grid, cv=self.cv)
         gs.best_estimator_, gs.best_params_ = est, dict(self.best_params_)

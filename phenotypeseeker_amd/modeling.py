@@ -29,7 +29,7 @@ from . import formats, metrics, _stats
 from .engine import PskContext
 from . import _lib
 from ._lib import PSK_EGZIP, PskError
-from .model import SVC, GridSearch, L1LogisticRegression, L2LogisticRegression, LassoRegression, RidgeRegression
+from .model import SVC, DecisionTree, GridSearch, L1LogisticRegression, L2LogisticRegression, LassoRegression, RidgeRegression
 
 RED_BANNER = "\x1b[1;1;101m%s\x1b[0m\n"
 GREEN = "\x1b[1;32m%s\x1b[0m"
@@ -279,6 +279,7 @@ class Input:
         phenotypes.no_results = []
         phenotypes.model_package = {}
         phenotypes._exchange = None
+        phenotypes.png_notice_given = False
         stderr_print.currentSampleNum = 0
         Samples.use_weights = False
         Samples.tree = None
@@ -341,7 +342,8 @@ class Input:
                    n_iter, n_splits_cv_inner, testset_size, train_on_whole, logreg_solver, jump_to, pca,
                    real_counts, omit_B, kmerDB):
         """Same positional signature as the reference (:141-183).  Options that select estimators
-        outside the hot path (SVM/RF/DT/NB, L2/elastic net, saga, PCA) are rejected here."""
+        outside the hot path (SVM/RF/DT/NB, L2/elastic net, saga, PCA) are rejected here; `-bc SVM` and `-bc DT` pass
+        with their knobs (PSK_SVM, PSK_DT)."""
         if alphas is None:
             phenotypes.alphas = np.logspace(math.log10(alpha_min), math.log10(alpha_max), num=n_alphas)
         else:
@@ -379,6 +381,17 @@ class Input:
                     raise SystemExit("The support vector machine on the GPU engine takes --kernel linear only, got %r." % kernel)
                 phenotypes.binary_classifier, phenotypes.kernel = "SVM", kernel
                 phenotypes.model_name_long, phenotypes.model_name_short = "support vector machine", "SVM"
+            elif binary_classifier == "DT" and _lib.env_flag("PSK_DT"):
+                # set_model (:1032-1033, :1069-1073): DecisionTreeClassifier() over max_depth 1..10 x {gini, entropy}.  The tree
+                # kernel works on the bit-packed presence matrix: k-mer counts and principal components are not 0/1
+                if real_counts:
+                    raise SystemExit("The decision tree on the GPU engine takes the 0/1 presence matrix only: "
+                                     "--real_counts is not supported with -bc DT.")
+                if pca:
+                    raise SystemExit("The decision tree on the GPU engine takes the 0/1 presence matrix only: "
+                                     "--pca is not supported with -bc DT.")
+                phenotypes.binary_classifier = "DT"
+                phenotypes.model_name_long, phenotypes.model_name_short = "decision tree", "DT"
             elif binary_classifier != "log":
                 raise SystemExit("Only the logistic-regression classifier runs on the GPU engine, got %r "
                                  "(SVM/RF/DT/NB are outside the accelerated path)." % binary_classifier)
@@ -432,6 +445,7 @@ class phenotypes:
     no_results = []
     model_package = {}
     _exchange = None
+    png_notice_given = False   # `-bc DT`: the one stderr line about the plot this package does not draw
 
     def __init__(self, name):
         self.name = name
@@ -669,6 +683,9 @@ class phenotypes:
     def _new_estimator(self):
         if self.pred_scale == "binary":
             grid = [1.0 / a for a in self.alphas]
+            if self.binary_classifier == "DT":
+                # (a grid of two parameters goes to GridSearch as a dictionary, in the reference's own spelling, :1069-1073)
+                return DecisionTree(), {"max_depth": [1, 2, 3, 4, 5, 6, 7, 8, 9, 10], "criterion": ["gini", "entropy"]}, None
             if self.binary_classifier == "SVM":
                 return SVC(kernel=self.kernel, probability=True, max_iter=self.max_iter, tol=self.tol), "C", grid
             if self.penalty == "L2":
@@ -773,6 +790,10 @@ class phenotypes:
                 import joblib
                 joblib.dump(package, fh)
         self._write_model_coefficients(coeff_path)
+        if short == "DT" and not phenotypes.png_notice_given:
+            # visualize_model (:1457-1463) draws the tree with matplotlib here; this package writes no plot
+            phenotypes.png_notice_given = True
+            _err("The decision tree's plot (DT_model_<phenotype>_plot.png) is not written by the GPU engine.\n")
         summary.close()
 
     def _cross_validation_results(self, out):
@@ -853,7 +874,10 @@ class phenotypes:
         with open(path, "w") as out:
             out.write("K-mer\tcoef._in_" + self.model_name_short + "_model\tNo._of_samples_with_k-mer\tSamples_with_k-mer\n")
         be = self.model_fitted.best_estimator_
-        coefs = be.coef_[0] if self.pred_scale == "binary" else be.coef_
+        if isinstance(be, DecisionTree):
+            coefs = be.feature_importances_      # (:1430-1432: the importances stand in the coefficient column)
+        else:
+            coefs = be.coef_[0] if self.pred_scale == "binary" else be.coef_
         X, index, kmers = self.ML["X"], self.ML["index"], self.ML["kmers"]
         # the lines are formatted by libpsk (psk_write_model_coefficients: a 2,048-sample model names a million samples --
         # 0.07 s of joins here); it appends to the file whose header this function has just written

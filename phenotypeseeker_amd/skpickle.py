@@ -6,8 +6,10 @@ GridSearchCV / LogisticRegression / Lasso / Ridge pickles as is its class (modul
 dictionary; the dictionaries of default-constructed estimators are recorded per scikit-learn version in
 sklearn_shells.json (tools/make_sklearn_shells.py), the fitted attributes come from this package's own solver.  The
 writer emits the pickle opcodes for "object of class <module>.<name> with this state" directly (GLOBAL / NEWOBJ /
-BUILD, protocol 2) and lets the standard pickler serialise the leaves (numbers, strings, numpy arrays).  When the
-installed scikit-learn has no template the caller falls back to GridSearch.to_sklearn(), which imports it.
+BUILD, protocol 2; GLOBAL / argument tuple / REDUCE / state / BUILD for an object that pickles by __reduce__, as the
+tree_ of a DecisionTreeClassifier does) and lets the standard pickler serialise the leaves (numbers, strings, numpy
+arrays).  When the installed scikit-learn has no template the caller falls back to GridSearch.to_sklearn(), which
+imports it.
 """
 import json
 import math
@@ -20,6 +22,14 @@ class Shell:
 
     def __init__(self, module, name, state):
         self.module, self.name, self.state = module, name, state
+
+
+class Reduced:
+    """Stands for the object that module.name(*args) builds and __setstate__(state) completes: what __reduce__ of an
+    extension type returns (sklearn.tree._tree.Tree: args (n_features, n_classes[], n_outputs))."""
+
+    def __init__(self, module, name, args, state):
+        self.module, self.name, self.args, self.state = module, name, tuple(args), state
 
 
 _templates = None
@@ -61,6 +71,12 @@ def _emit(obj, out):
         out.append(b")\x81")                                                          # EMPTY_TUPLE, NEWOBJ
         _emit(obj.state, out)
         out.append(b"b")                                                              # BUILD
+    elif isinstance(obj, Reduced):
+        out.append(b"c" + obj.module.encode() + b"\n" + obj.name.encode() + b"\n")   # GLOBAL
+        _emit(obj.args, out)                                                          # (a tuple of leaves)
+        out.append(b"R")                                                              # REDUCE
+        _emit(obj.state, out)
+        out.append(b"b")                                                              # BUILD
     elif isinstance(obj, dict) and _has_shell(obj):
         out.append(b"}(")                                                             # EMPTY_DICT, MARK
         for k, v in obj.items():
@@ -76,7 +92,7 @@ def _emit(obj, out):
 
 
 def _has_shell(obj):
-    if isinstance(obj, Shell):
+    if isinstance(obj, (Shell, Reduced)):
         return True
     if isinstance(obj, dict):
         return any(_has_shell(v) for v in obj.values())
@@ -178,10 +194,31 @@ def _svc_from_state(est):
     return m
 
 
+def _tree_from_state(est):
+    """model.DecisionTree from the attribute dictionary of a fitted two-class, single-output
+    sklearn.tree.DecisionTreeClassifier whose tree_ came through the stub (Tree.__getstate__: max_depth, node_count, nodes,
+    values): predict / predict_proba walk the node arrays in NumPy.  None for anything else."""
+    import numpy as np
+    from .model import DecisionTree, Tree
+    d = est.__dict__
+    classes, tree = d.get("classes_"), d.get("tree_")
+    if (classes is None or getattr(classes, "ndim", 0) != 1 or list(classes) != [0, 1] or d.get("n_outputs_") != 1 or tree is None
+            or not {"nodes", "values", "max_depth"} <= set(getattr(tree, "__dict__", {}))):
+        return None
+    values = np.asarray(tree.values)
+    if values.ndim != 3 or values.shape[1:] != (1, 2) or np.any(tree.nodes["missing_go_to_left"]):
+        return None
+    m = DecisionTree(criterion=d.get("criterion", "gini"), max_depth=d.get("max_depth"))
+    m.tree_ = Tree._from_sklearn_state(int(d["n_features_in_"]), tree.__dict__)
+    m.n_features_in_ = int(d["n_features_in_"])
+    return m
+
+
 def load_linear_package(path):
     """The model package of `path` ({'model', 'kmers', 'pca', 'pred_scale'}) with 'model' as a LinearModel -- for files
     that are plain pickles of a (grid search over a) binary linear classifier or a linear regressor, which is what
-    `modeling` writes; a two-class SVC with a Platt pair comes back as model.SVC (_svc_from_state).  None for anything else
+    `modeling` writes; a two-class SVC with a Platt pair comes back as model.SVC (_svc_from_state), a two-class decision tree
+    as model.DecisionTree (_tree_from_state).  None for anything else
     (joblib-wrapped arrays, multi-class models, other estimators, a PCA pipeline): the caller then takes joblib.load and
     scikit-learn itself."""
     try:
@@ -193,6 +230,11 @@ def load_linear_package(path):
         est = getattr(m, "best_estimator_", m)
         kind = type(est).__name__
         coef, icpt = getattr(est, "coef_", None), getattr(est, "intercept_", None)
+        if kind == "DecisionTreeClassifier":
+            model = _tree_from_state(est)
+            if model is None:
+                return None
+            return dict(pkg, model=model)
         if kind != "SVC" and (coef is None or icpt is None):   # (an SVC keeps its support vectors, coef_ is derived)
             return None
         if kind in ("LogisticRegression",):

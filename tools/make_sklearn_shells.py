@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Records, for the installed scikit-learn, what a default-constructed LogisticRegression / Lasso / Ridge / SVC /
-GridSearchCV pickles as (module, class name, state) into phenotypeseeker_amd/sklearn_shells.json, keyed by the
+DecisionTreeClassifier / GridSearchCV pickles as (module, class name, state) into phenotypeseeker_amd/sklearn_shells.json, keyed by the
 scikit-learn version.  phenotypeseeker_amd/skpickle.py writes model files from these templates without importing
 scikit-learn (0.3-0.5 s, as long as the rest of a 256-genome `modeling` run); a version without a template takes the
 import.  usage: tools/make_sklearn_shells.py"""
@@ -12,6 +12,7 @@ import sklearn
 from sklearn.linear_model import Lasso, LogisticRegression, Ridge
 from sklearn.model_selection import GridSearchCV
 from sklearn.svm import SVC
+from sklearn.tree import DecisionTreeClassifier
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 path = os.path.join(ROOT, "phenotypeseeker_amd", "sklearn_shells.json")
@@ -40,6 +41,7 @@ out[sklearn.__version__] = {
     "Lasso": shell(Lasso()),
     "Ridge": shell(Ridge()),
     "SVC": shell(SVC()),
+    "DecisionTreeClassifier": shell(DecisionTreeClassifier()),
     "GridSearchCV": shell(GridSearchCV(LogisticRegression(), {"C": [1.0]}), drop=("estimator", "param_grid")),
 }
 with open(path, "w") as f:
