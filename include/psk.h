@@ -228,6 +228,19 @@ int psk_compact_info(const psk_ctx *ctx, int *encoded, uint64_t *overflow_rows);
  * evaluation against the statistic threshold thr = -2 log(cut), else 0: the host's evaluation of the function the dense
  * kernel and the exception-coded scan's candidate table share.  Tests only (no context, no device). */
 int psk_chi2_pretest(double A, double B, double C, double D, double thr);
+/* What the exception-coded scan makes of a scan's parameters (class sizes n1, n0 of n_samples samples, the frequency
+ * filter, the statistic threshold thr of the pre-test) before it launches.  corner[base] bit a' * 8 + c' (a', c' <= 7):
+ * a row with a' case and c' control exceptions -- its table is (a', c') when the exceptions are the present samples
+ * (base 0), (n1 - a', n0 - c') when they are the absent ones (base 1) -- passes the frequency filter and the pre-test;
+ * 0 where a' > n1 or c' > n0.  *class_mask bit (e | base << 3): a row of e = 0..7 exceptions can have such a table; its
+ * exceptions among the n_samples - n1 - n0 NA samples count towards neither a' nor c'.  A class whose bit is clear is
+ * dropped on its header byte; with no bit set the scan does not read the slots at all.  Host code: no context, no device. */
+int psk_cx_plan(int n1, int n0, int n_samples, int min_samples, int max_samples, double thr, uint32_t *class_mask,
+                uint64_t *corner /* [2] */);
+/* The plan of the last chi2 scan launched or repeated on the context: *encoded = 1 when it took the exception-coded path
+ * (else the other two are 0), *class_mask as psk_cx_plan gives it, *slots_skipped = 1 when the launch read only the side
+ * matrix of overflow rows.  Measurement and tests only.  Any pointer may be NULL. */
+int psk_last_scan_plan(const psk_ctx *ctx, int *encoded, uint32_t *class_mask, int *slots_skipped);
 /* HIP-event duration of the last scan kernel launch in milliseconds (for bench.py). */
 double psk_last_scan_ms(const psk_ctx *ctx);
 /* Re-launches the last chi2 scan `reps` times back to back on the context's stream and

@@ -66,6 +66,8 @@ _SIGNATURES = {
     "psk_export_survivors": (c.c_int, [c.c_void_p, c.c_void_p, c.c_uint64, _u64p]),
     "psk_compact_info": (c.c_int, [c.c_void_p, c.POINTER(c.c_int), c.POINTER(c.c_uint64)]),
     "psk_chi2_pretest": (c.c_int, [c.c_double] * 5),
+    "psk_cx_plan": (c.c_int, [c.c_int] * 5 + [c.c_double, c.POINTER(c.c_uint32), _u64p]),
+    "psk_last_scan_plan": (c.c_int, [c.c_void_p, c.POINTER(c.c_int), c.POINTER(c.c_uint32), c.POINTER(c.c_int)]),
     "psk_last_scan_ms": (c.c_double, [c.c_void_p]),
     "psk_rescan_timed": (c.c_int, [c.c_void_p, c.c_int, c.POINTER(c.c_double)]),
     "psk_rescan_times": (c.c_int, [c.c_void_p, c.c_int, c.c_void_p]),

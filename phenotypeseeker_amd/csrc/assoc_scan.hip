@@ -43,8 +43,8 @@ __device__ __forceinline__ double chi2_exact(double A, double B, double C, doubl
 }
 
 // the division-free pre-test of a unit-weight 2 x 2 table: chi2 = T (AD - BC)^2 / (R1 R0 K1 K0) cannot be ruled out
-// against thr.  Host and device evaluate it in the same IEEE double operations (-ffp-contract=off): the host's candidate
-// table of the exception-coded scan (cx_fill_tables) decides bit for bit what the dense kernel decides.
+// against thr.  Host and device evaluate it in the same IEEE double operations (-ffp-contract=off): the host's corner
+// table of the exception-coded scan (cx_plan) decides bit for bit what the dense kernel decides.
 __host__ __device__ __forceinline__ bool chi2_pretest(double A, double B, double C, double D, double thr)
 {
     const double R1 = A + B, R0 = C + D, K1 = A + C, K0 = B + D, T = R1 + R0;
@@ -166,13 +166,16 @@ __global__ __launch_bounds__(LUT ? SC_LUT_THREADS : SC_THREADS) void chi2_scan_k
 // ---- the unweighted scan over the exception-coded rows (presence_compact.hip) ------------------------------------------
 // One lane per row: a lane's 16-byte load holds two slots, so a wave instruction reads 1 KB.  A slot's header gives e and
 // whether the exceptions are the present or the absent samples; the class table in LDS (1 = case, 0x100 = control, 0 = NA)
-// summed over the e indices gives (a', c'), hence (a, c).  Whether (a, c) is a candidate -- frequency filter and the
-// division-free pre-test -- is one bit of a table the host filled for this scan (cx_fill_tables, the same double
-// operations as chi2_pretest); candidates take chi2_scan_kernel's MODE 0 path (chi2_exact, exp, keep rule), so stat and p
-// are the dense kernel's bits.  The rows with more than CX_MAX_E exceptions are a side matrix of dense rows that the last
-// workgroups of the SAME launch scan as chi2_scan_kernel does (CPR 16-byte chunks per row, one lane each), reporting
-// their original row ids: a second launch would add a kernel boundary to every step.
-constexpr int CX_BM_WORDS = ((CX_MAX_SAMPLES / 2 + 1) * (CX_MAX_SAMPLES / 2 + 1) + 31) / 32;   // (n1 + 1)(n0 + 1) bits, n1 + n0 <= 256
+// summed over the e indices gives (a', c') with a', c' <= 7, hence (a, c) = (a', c') or (n1 - a', n0 - c').  A slot row's
+// table therefore lies in one of the two 8 x 8 corners of the (a, c) plane, and whether it is a candidate -- frequency
+// filter and the division-free pre-test -- is one bit of the two corner words the host filled for this scan (cx_plan: the
+// same double operations as chi2_pretest); candidates take chi2_scan_kernel's MODE 0 path (chi2_exact, exp, keep rule), so
+// stat and p are the dense kernel's bits.  A header class (e, base) none of whose reachable corner points is a candidate
+// is dropped on the header byte (X.class_mask); when NO class is feasible -- every Bonferroni cut-off of a real run: a row
+// of at most 7 exceptions cannot reach the statistic -- the host launches no slot workgroup and the slots are not read.
+// The rows with more than CX_MAX_E exceptions are a side matrix of dense rows that the last workgroups of the SAME launch
+// scan as chi2_scan_kernel's MODE 0 does (CPR 16-byte chunks per row, one lane each; frequency filter and chi2_pretest
+// in line), reporting their original row ids: a second launch would add a kernel boundary to every step.
 #ifndef PSK_CX_UNROLL
 #define PSK_CX_UNROLL 4
 #endif
@@ -186,13 +189,11 @@ struct CxScanArgs {
     const u32x4 *ov;             // overflow rows, dense, cpr chunks each, ascending
     const uint32_t *ov_row;      // ... their row ids
     uint64_t n_ov;
-    uint32_t slot_blocks;        // workgroups [0, slot_blocks) stream the slots, the others the overflow rows
-    uint32_t hdr_ok;             // bit (header & 15): a row of that e and base can pass the frequency filter (all set with NA samples)
-    int bm_words;
-    uint32_t bm[CX_BM_WORDS];    // bit a * (n0 + 1) + c: the table (a, c) is a candidate
+    uint32_t slot_blocks;        // workgroups [0, slot_blocks) stream the slots (none when no class is feasible),
+    uint32_t ov_blocks;          // the next ov_blocks the overflow rows; any beyond only publish their segment
+    uint32_t class_mask;         // bit (header & 15): some reachable table of that e and base is a candidate (cx_plan)
+    uint64_t corner[2];          // [base] bit a' * 8 + c': the table (a', c') / (n1 - a', n0 - c') is a candidate
 };
-// travels in the kernel arguments, like the masks: an unweighted scan uploads nothing
-static_assert(sizeof(CxScanArgs) <= 4096, "the kernel arguments of a launch are limited to 4 KB");
 
 template <int CPR>
 __global__ __launch_bounds__(SC_THREADS) void chi2_scan_kernel_cx(const CxScanArgs X)
@@ -200,22 +201,18 @@ __global__ __launch_bounds__(SC_THREADS) void chi2_scan_kernel_cx(const CxScanAr
     static_assert(SC_THREADS == CX_MAX_SAMPLES, "the class table is filled one sample per thread");
     const ScanArgs &P = X.s;
     __shared__ uint16_t s_cls[CX_MAX_SAMPLES];
-    __shared__ uint32_t s_bm[CX_BM_WORDS];
-    {
-        const int t = threadIdx.x;
-        const uint64_t b = 1ull << (t & 63);
-        s_cls[t] = (P.m1_inl[t >> 6] & b) ? 1 : (P.m0_inl[t >> 6] & b) ? 0x100 : 0;
-        for (int i = t; i < X.bm_words; i += SC_THREADS) s_bm[i] = X.bm[i];
-    }
-    __syncthreads();
     const int lane = threadIdx.x & 63;
-    const int n0p = P.n0 + 1;
-    auto candidate = [&](int a, int c) -> bool { const int bit = a * n0p + c; return (s_bm[bit >> 5] >> (bit & 31)) & 1u; };
     auto evaluate = [&](uint64_t row, int a, int c) {   // chi2_scan_kernel MODE 0
         double stat, p;
         if (chi2_keep(P, (double)a, (double)(P.n1 - a), (double)c, (double)(P.n0 - c), stat, p)) chi2_store(P, reserve_slot(P), row, stat, p, a + c);
     };
     if (blockIdx.x < X.slot_blocks) {
+        {
+            const int t = threadIdx.x;
+            const uint64_t b = 1ull << (t & 63);
+            s_cls[t] = (P.m1_inl[t >> 6] & b) ? 1 : (P.m0_inl[t >> 6] & b) ? 0x100 : 0;
+        }
+        __syncthreads();
         const uint64_t n_pairs = (P.M + 1) / 2;   // the buffer holds whole pairs; an odd last row's partner is not a row
         const uint64_t wave = (uint64_t)blockIdx.x * (SC_THREADS / 64) + (threadIdx.x >> 6);
         const uint64_t stride = (uint64_t)X.slot_blocks * (SC_THREADS / 64) * 64 * CX_UNROLL;
@@ -233,7 +230,7 @@ __global__ __launch_bounds__(SC_THREADS) void chi2_scan_kernel_cx(const CxScanAr
                     const uint64_t row = 2 * (p0 + u * 64 + lane) + sub;
                     const uint32_t lo = sub ? x[u].z : x[u].x, hi = sub ? x[u].w : x[u].y;
                     const uint32_t h = lo & 0xffu;
-                    if (row >= P.M || (h & CX_HDR_OVF) || !((X.hdr_ok >> (h & 15u)) & 1u)) continue;
+                    if (row >= P.M || (h & CX_HDR_OVF) || !((X.class_mask >> (h & 15u)) & 1u)) continue;
                     const uint32_t e = h & 7u;
                     uint32_t sum = 0;
                     if (e > 0) sum += s_cls[(lo >> 8) & 0xffu];
@@ -243,17 +240,19 @@ __global__ __launch_bounds__(SC_THREADS) void chi2_scan_kernel_cx(const CxScanAr
                     if (e > 4) sum += s_cls[(hi >> 8) & 0xffu];
                     if (e > 5) sum += s_cls[(hi >> 16) & 0xffu];
                     if (e > 6) sum += s_cls[hi >> 24];
-                    int a = (int)(sum & 0xffu), c = (int)(sum >> 8);
-                    if (h & CX_HDR_BASE) { a = P.n1 - a; c = P.n0 - c; }
-                    if (candidate(a, c)) evaluate(row, a, c);
+                    int a = (int)(sum & 0xffu), c = (int)(sum >> 8);   // (a', c'): at most e <= 7 each
+                    const bool absent = (h & CX_HDR_BASE) != 0;
+                    if (!((X.corner[absent ? 1 : 0] >> (a * 8 + c)) & 1ull)) continue;
+                    if (absent) { a = P.n1 - a; c = P.n0 - c; }
+                    evaluate(row, a, c);
                 }
         }
-    } else {
+    } else if (blockIdx.x - X.slot_blocks < X.ov_blocks) {
         constexpr int RPW = 64 / CPR;   // rows per wave step
         const int g = lane & (CPR - 1);
         const uint64_t m1a = P.m1_inl[2 * g], m1b = P.m1_inl[2 * g + 1], m0a = P.m0_inl[2 * g], m0b = P.m0_inl[2 * g + 1];
         const uint64_t wave = (uint64_t)(blockIdx.x - X.slot_blocks) * (SC_THREADS / 64) + (threadIdx.x >> 6);
-        const uint64_t total_waves = (uint64_t)(gridDim.x - X.slot_blocks) * (SC_THREADS / 64);
+        const uint64_t total_waves = (uint64_t)X.ov_blocks * (SC_THREADS / 64);
         const uint64_t n_steps = (X.n_ov + RPW - 1) / RPW;
         for (uint64_t s0 = wave * CX_UNROLL; s0 < n_steps; s0 += total_waves * CX_UNROLL) {
             u32x4 x[CX_UNROLL];
@@ -272,7 +271,12 @@ __global__ __launch_bounds__(SC_THREADS) void chi2_scan_kernel_cx(const CxScanAr
                     a += __shfl_xor(a, 1, 64);
                     c += __shfl_xor(c, 1, 64);
                 }
-                if (r < X.n_ov && g == 0 && candidate((int)a, (int)c)) evaluate(X.ov_row[r], (int)a, (int)c);
+                // chi2_scan_kernel MODE 0's on_row
+                const int n_w = (int)(a + c);
+                const int n_wo = (P.n1 - (int)a) + (P.n0 - (int)c);
+                const bool freq_ok = (r < X.n_ov) && !(n_w < P.min_samples || n_wo < 2 || n_w > P.max_samples);
+                const double A = (double)a, B = (double)(P.n1 - (int)a), C = (double)c, D = (double)(P.n0 - (int)c);
+                if (freq_ok && g == 0 && chi2_pretest(A, B, C, D, P.thr)) evaluate(X.ov_row[r], (int)a, (int)c);
             }
         }
     }
@@ -385,63 +389,75 @@ int pick_chi2_mode(psk_ctx *ctx, bool weighted, double pcut, double pcut_bonf, i
     return weighted ? PSK_OK : env_choice(ctx, "PSK_CHI2_MODE", {0, 2}, mode);   // read per scan: tests cross the two forms in one process
 }
 
-// ---- exception-coded path: launch shape and the per-scan tables ----
-// Workgroups of the two parts in proportion to their bytes, under scan_grid's cap; slot_blocks = the first part's.
-dim3 cx_grid(const psk_ctx *ctx, uint64_t M, uint64_t n_ov, int cpr, uint32_t *slot_blocks)
+// ---- exception-coded path: the per-scan plan and the launch shape ----
+// What a scan's parameters leave of the slot rows.  corner[base] bit a' * 8 + c' (a', c' <= 7): the table of a slot row
+// with a' case and c' control exceptions -- (a', c') when the exceptions are the present samples (base 0), (n1 - a',
+// n0 - c') when they are the absent ones (base 1) -- passes chi2_scan_kernel's frequency filter and chi2_pretest (the same
+// double operations); 0 where a' > n1 or c' > n0: no row has such a table.  class_mask bit (e | base << 3): a row of e
+// exceptions can have a table whose bit is set.  Its a' + c' is e less its exceptions among the NA samples, of which
+// there are n_samples - n1 - n0.  (n1 = 0, n0 = 0: the pre-test lets every NaN table through, the filter alone decides.)
+void cx_plan(int n1, int n0, int n_samples, int min_samples, int max_samples, double thr, uint32_t *class_mask, uint64_t corner[2])
 {
-    const uint64_t wpb = SC_THREADS / 64;
-    const uint64_t n_pairs = (M + 1) / 2, ov_rpw = 64 / cpr;
-    uint64_t bs = ((n_pairs + 64 * CX_UNROLL - 1) / (64 * CX_UNROLL) + wpb - 1) / wpb;
-    uint64_t bo = (((n_ov + ov_rpw - 1) / ov_rpw + CX_UNROLL - 1) / CX_UNROLL + wpb - 1) / wpb;
-    const uint64_t cap = scan_grid_cap(ctx);
-    if (bs + bo > cap) {
-        const double slot_bytes = 16.0 * n_pairs, ov_bytes = 16.0 * cpr * n_ov;
-        const uint64_t s = (uint64_t)(cap * slot_bytes / (slot_bytes + ov_bytes) + 0.5);
-        bs = std::min(bs, std::max<uint64_t>(s, 1));
-        bo = std::min(bo, cap - bs);
-        if (n_ov && bo == 0) { bo = 1; bs = std::max<uint64_t>(bs - 1, 1); }
+    corner[0] = corner[1] = 0;
+    for (int base = 0; base < 2; base++)
+        for (int ap = 0; ap <= CX_MAX_E && ap <= n1; ap++)
+            for (int cp = 0; cp <= CX_MAX_E && cp <= n0; cp++) {
+                const int ai = base ? n1 - ap : ap, ci = base ? n0 - cp : cp;
+                const int n_w = ai + ci, n_wo = (n1 - ai) + (n0 - ci);
+                const bool freq_ok = !(n_w < min_samples || n_wo < 2 || n_w > max_samples);
+                const double A = (double)ai, B = (double)(n1 - ai), C = (double)ci, D = (double)(n0 - ci);
+                if (freq_ok && chi2_pretest(A, B, C, D, thr)) corner[base] |= 1ull << (ap * 8 + cp);
+            }
+    const int n_na = n_samples - n1 - n0;
+    *class_mask = 0;
+    for (int h = 0; h < 16; h++) {
+        const int e = h & 7, base = h >> 3;
+        bool ok = false;
+        for (int ap = 0; ap <= e && !ok; ap++)
+            for (int cp = 0; ap + cp <= e && !ok; cp++)
+                ok = ap + cp >= e - n_na && ((corner[base] >> (ap * 8 + cp)) & 1ull);
+        if (ok) *class_mask |= 1u << h;
     }
-    if (bs + bo < SC_NSEG) bs = SC_NSEG - bo;   // every result segment needs a workgroup to publish its count
-    *slot_blocks = (uint32_t)bs;
-    return dim3((unsigned)(bs + bo));
 }
 
-// the most rows one workgroup of chi2_scan_kernel_cx visits
-uint64_t cx_rows_per_block(const CxScanArgs &x, dim3 grid, int cpr)
+// Workgroups of the two parts in proportion to their bytes, under scan_grid's cap; x.slot_blocks = the first part's,
+// x.ov_blocks the second's.  With no feasible class (x.class_mask == 0) the slots get none and the side matrix the whole
+// cap.  At least SC_NSEG workgroups: every result segment needs one to publish its count and re-arm its counter.
+dim3 cx_grid(const psk_ctx *ctx, CxScanArgs &x, int cpr)
 {
     const uint64_t wpb = SC_THREADS / 64;
     const uint64_t n_pairs = (x.s.M + 1) / 2, ov_rpw = 64 / cpr;
-    const uint64_t ws = (uint64_t)x.slot_blocks * wpb, wo = (uint64_t)(grid.x - x.slot_blocks) * wpb;
+    uint64_t bs = x.class_mask ? ((n_pairs + 64 * CX_UNROLL - 1) / (64 * CX_UNROLL) + wpb - 1) / wpb : 0;
+    uint64_t bo = (((x.n_ov + ov_rpw - 1) / ov_rpw + CX_UNROLL - 1) / CX_UNROLL + wpb - 1) / wpb;
+    const uint64_t cap = scan_grid_cap(ctx);
+    if (!x.class_mask) bo = std::min(bo, cap);
+    else if (bs + bo > cap) {
+        const double slot_bytes = 16.0 * n_pairs, ov_bytes = 16.0 * cpr * x.n_ov;
+        const uint64_t s = (uint64_t)(cap * slot_bytes / (slot_bytes + ov_bytes) + 0.5);
+        bs = std::min(bs, std::max<uint64_t>(s, 1));
+        bo = std::min(bo, cap - bs);
+        if (x.n_ov && bo == 0) { bo = 1; bs = std::max<uint64_t>(bs - 1, 1); }
+    }
+    uint64_t total = bs + bo;
+    if (total < SC_NSEG) {
+        if (x.class_mask) bs = SC_NSEG - bo;   // (more slot workgroups than slot work: they find p0 >= n_pairs)
+        total = SC_NSEG;
+    }
+    x.slot_blocks = (uint32_t)bs;
+    x.ov_blocks = (uint32_t)bo;
+    return dim3((unsigned)total);
+}
+
+// the most rows one workgroup of chi2_scan_kernel_cx visits
+uint64_t cx_rows_per_block(const CxScanArgs &x, int cpr)
+{
+    const uint64_t wpb = SC_THREADS / 64;
+    const uint64_t n_pairs = (x.s.M + 1) / 2, ov_rpw = 64 / cpr;
+    const uint64_t ws = (uint64_t)x.slot_blocks * wpb, wo = (uint64_t)x.ov_blocks * wpb;
     const uint64_t cs = (n_pairs + 64 - 1) / 64, co = (x.n_ov + ov_rpw - 1) / ov_rpw;   // wave steps
     const uint64_t rs = ws ? (cs + ws * CX_UNROLL - 1) / (ws * CX_UNROLL) * wpb * CX_UNROLL * 128 : 0;
     const uint64_t ro = wo ? (co + wo * CX_UNROLL - 1) / (wo * CX_UNROLL) * wpb * CX_UNROLL * ov_rpw : 0;
     return std::max(rs, ro);
-}
-
-// The candidate table over (a, c) -- chi2_scan_kernel's frequency filter and chi2_pretest, in the same double
-// operations -- and the headers that can pass the frequency filter at all (no NA: a + c = the row's popcount).
-void cx_fill_tables(CxScanArgs &x, int n_samples)
-{
-    const ScanArgs &a = x.s;
-    memset(x.bm, 0, sizeof(x.bm));
-    const int n0p = a.n0 + 1;
-    for (int ai = 0; ai <= a.n1; ai++)
-        for (int ci = 0; ci <= a.n0; ci++) {
-            const int n_w = ai + ci, n_wo = (a.n1 - ai) + (a.n0 - ci);
-            const bool freq_ok = !(n_w < a.min_samples || n_wo < 2 || n_w > a.max_samples);
-            const double A = (double)ai, B = (double)(a.n1 - ai), C = (double)ci, D = (double)(a.n0 - ci);
-            if (freq_ok && chi2_pretest(A, B, C, D, a.thr)) {
-                const int bit = ai * n0p + ci;
-                x.bm[bit >> 5] |= 1u << (bit & 31);
-            }
-        }
-    x.bm_words = ((a.n1 + 1) * n0p + 31) / 32;
-    x.hdr_ok = 0;
-    for (int h = 0; h < 16; h++) {
-        const int e = h & 7, pc = (h & (int)CX_HDR_BASE) ? n_samples - e : e;
-        const bool ok = a.n1 + a.n0 != n_samples || !(pc < a.min_samples || n_samples - pc < 2 || pc > a.max_samples);
-        if (ok) x.hdr_ok |= 1u << h;
-    }
 }
 
 // One chi2 scan as the host launches it: the dense kernels' arguments, and the exception-coded path when it runs
@@ -516,6 +532,7 @@ static int fill_chi2_args(psk_ctx *ctx, Chi2Launch &CL, int set, bool build_tabl
     ScanShape sh;   // weighted: class-weight sums from a table in LDS (e0 = class 1, e1 = class 0)
     PSK_TRY(setup_table_scan(ctx, a, L.weighted ? a.tab : nullptr, 2, L.W1, L.W0, 0.0, build_tables, &sh));
     CL.compact = ctx->cx_valid && !L.weighted && L.inline_masks && !env_flag("PSK_SCAN_DENSE");
+    ctx->cx_last_plan = false;
     if (CL.compact) {
         CxScanArgs &x = CL.x;
         CL.cpr = a.cpr;
@@ -523,9 +540,12 @@ static int fill_chi2_args(psk_ctx *ctx, Chi2Launch &CL, int set, bool build_tabl
         x.ov = ctx->cx_ov.as<u32x4>();
         x.ov_row = ctx->cx_ov_row.as<uint32_t>();
         x.n_ov = ctx->cx_n_ov;
-        CL.grid = cx_grid(ctx, a.M, x.n_ov, CL.cpr, &x.slot_blocks);
-        cx_fill_tables(x, ctx->n_samples);
-        return setup_results_rows(ctx, a, CL.grid, cx_rows_per_block(x, CL.grid, CL.cpr), set);
+        cx_plan(a.n1, a.n0, ctx->n_samples, a.min_samples, a.max_samples, a.thr, &x.class_mask, x.corner);
+        CL.grid = cx_grid(ctx, x, CL.cpr);
+        ctx->cx_last_plan = true;
+        ctx->cx_last_class_mask = x.class_mask;
+        ctx->cx_last_skipped = x.slot_blocks == 0;
+        return setup_results_rows(ctx, a, CL.grid, cx_rows_per_block(x, CL.cpr), set);
     }
     PSK_TRY(pick_chi2_mode(ctx, L.weighted, a.pcut, a.pcut_bonf, a.omit_B, &CL.mode));
     CL.grid = sh.grid;
@@ -674,3 +694,20 @@ extern "C" int psk_rescan_times(psk_ctx *ctx, int reps, double *ms_each)
 }
 
 extern "C" int psk_chi2_pretest(double A, double B, double C, double D, double thr) { return chi2_pretest(A, B, C, D, thr) ? 1 : 0; }
+
+extern "C" int psk_cx_plan(int n1, int n0, int n_samples, int min_samples, int max_samples, double thr, uint32_t *class_mask,
+                           uint64_t *corner)
+{
+    if (n1 < 0 || n0 < 0 || n_samples < 0 || n1 + n0 > n_samples || !class_mask || !corner) return PSK_EINVAL;
+    cx_plan(n1, n0, n_samples, min_samples, max_samples, thr, class_mask, corner);
+    return PSK_OK;
+}
+
+extern "C" int psk_last_scan_plan(const psk_ctx *ctx, int *encoded, uint32_t *class_mask, int *slots_skipped)
+{
+    if (!ctx) return PSK_EINVAL;
+    if (encoded) *encoded = ctx->cx_last_plan ? 1 : 0;
+    if (class_mask) *class_mask = ctx->cx_last_plan ? ctx->cx_last_class_mask : 0;
+    if (slots_skipped) *slots_skipped = ctx->cx_last_plan && ctx->cx_last_skipped ? 1 : 0;
+    return PSK_OK;
+}

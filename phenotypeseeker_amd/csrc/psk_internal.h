@@ -150,6 +150,7 @@ struct psk_ctx {
     void *scan_pinned = nullptr;  // pinned staging for the scan's masks / weights
     size_t scan_pinned_cap = 0;
     void *cnt_pinned = nullptr;   // pinned landing buffer of the scan's result counters
+    uint32_t *cnt_pinned_dev = nullptr;   // ... as the device addresses it (looked up once, with the allocation)
     static constexpr int LANES = 24;
     // .gz inputs (gz_inflate.hip): what a run of them is inflated in.  Two sets of the buffers that outlive the inflate -- the
     // compressed images in host memory, their copy and the text on the device --, because a call's runs are a pipeline: one is
@@ -181,6 +182,10 @@ struct psk_ctx {
     DevBuf cx_slots, cx_ov, cx_ov_row;
     bool cx_valid = false;
     uint64_t cx_n_ov = 0;
+    // the plan of the last chi2 scan set up (cx_plan, assoc_scan.hip): did it take the exception-coded path, which header
+    // classes were feasible, and was the slot stream left unread (psk_last_scan_plan)
+    bool cx_last_plan = false, cx_last_skipped = false;
+    uint32_t cx_last_class_mask = 0;
 
     // scan state
     DevBuf mask1, phe, res_count, res_sorted;

@@ -40,12 +40,15 @@ int setup_results_rows(psk_ctx *ctx, ScanArgs &a, dim3 grid, uint64_t rows_per_b
         PSK_TRY(dev_reserve(ctx, ctx->res_count, (SC_NSEG * SC_CNT_STRIDE + 2 * SC_NSEG) * 4));
         PSK_HIP(ctx, hipMemsetAsync(ctx->res_count.p, 0, (SC_NSEG * SC_CNT_STRIDE + 2 * SC_NSEG) * 4, ctx->stream));
     }
-    if (!ctx->cnt_pinned) PSK_HIP(ctx, hipHostMalloc(&ctx->cnt_pinned, 2 * SC_NSEG * 4, hipHostMallocDefault));
+    if (!ctx->cnt_pinned) {
+        PSK_HIP(ctx, hipHostMalloc(&ctx->cnt_pinned, 2 * SC_NSEG * 4, hipHostMallocDefault));
+        void *hc = nullptr;
+        PSK_HIP(ctx, hipHostGetDevicePointer(&hc, ctx->cnt_pinned, 0));
+        ctx->cnt_pinned_dev = static_cast<uint32_t *>(hc);
+    }
     a.counter = ctx->res_count.as<uint32_t>();
     a.final_counts = a.counter + SC_NSEG * SC_CNT_STRIDE + set * SC_NSEG;  // one compact array per result set
-    void *hc = nullptr;
-    PSK_HIP(ctx, hipHostGetDevicePointer(&hc, ctx->cnt_pinned, 0));
-    a.host_counts = static_cast<uint32_t *>(hc) + set * SC_NSEG;
+    a.host_counts = ctx->cnt_pinned_dev + set * SC_NSEG;
     a.seg_cap = (uint32_t)seg_cap;
     ctx->slot[set].seg_cap = seg_cap;
     if (set == ctx->res_set) ctx->results_valid = false;  // the last ended scan's results are about to go

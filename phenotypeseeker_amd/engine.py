@@ -362,6 +362,14 @@ class PskContext:
         self._check(self._lib.psk_compact_info(self._h, ctypes.byref(enc), ctypes.byref(n_ov)), "psk_compact_info")
         return bool(enc.value), n_ov.value
 
+    def last_scan_plan(self):
+        """(the last chi2 scan took the exception-coded path, its class mask, it left the slot stream unread):
+        psk_last_scan_plan"""
+        enc, mask, skipped = ctypes.c_int(), ctypes.c_uint32(), ctypes.c_int()
+        self._check(self._lib.psk_last_scan_plan(self._h, ctypes.byref(enc), ctypes.byref(mask), ctypes.byref(skipped)),
+                    "psk_last_scan_plan")
+        return bool(enc.value), mask.value, bool(skipped.value)
+
     def last_scan_ms(self):
         return self._lib.psk_last_scan_ms(self._h)
 
