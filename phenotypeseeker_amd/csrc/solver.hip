@@ -18,6 +18,8 @@
 #include <algorithm>
 
 #include "solver_common.h"
+#include "solver_host.h"
+#include "solver_l1_plan.h"
 
 namespace {
 
@@ -555,365 +557,209 @@ __global__ __launch_bounds__(SV_COOP_THREADS) void lasso_bits_kernel(const uint6
     }
 }
 
-// host: transpose X[n][p] -> XT[p+1][n]
-void transpose_f32(const float *X, int n, int p, std::vector<float> &XT)
+// the distinct held-out folds of a call in order of first use; of_fit[j]: index of fit j's fold among them
+std::vector<int32_t> distinct_folds(const int32_t *fit_fold, int n_fits, std::vector<int32_t> &of_fit)
 {
-    XT.assign((size_t)(p + 1) * n, 1.0f);
-    for (int i = 0; i < n; i++)
-        for (int j = 0; j < p; j++) XT[(size_t)j * n + i] = X[(size_t)i * p + j];
+    std::vector<int32_t> ids;
+    of_fit.resize(n_fits);
+    for (int j = 0; j < n_fits; j++) {
+        size_t q = 0;
+        while (q < ids.size() && ids[q] != fit_fold[j]) q++;
+        if (q == ids.size()) ids.push_back(fit_fold[j]);
+        of_fit[j] = (int32_t)q;
+    }
+    return ids;
 }
 
-struct SolverBufs {
-    void *xt = nullptr, *y = nullptr, *fold = nullptr, *param = nullptr, *ffold = nullptr, *coef = nullptr,
-         *icpt = nullptr, *iters = nullptr, *work = nullptr, *iwork = nullptr, *bits = nullptr, *bitsT = nullptr, *ggq = nullptr;
-    ~SolverBufs()
-    {
-        void *ps[] = {xt, y, fold, param, ffold, coef, icpt, iters, work, iwork, bits, bitsT, ggq};
-        for (void *q : ps) if (q) (void)hipFree(q);
-    }
-};
-
-int check_fit_args(psk_ctx *ctx, const void *X, const void *y, int n, int p, const int32_t *fold, const double *fit_param,
-                   const int32_t *fit_fold, int n_fits, double *coef_out, double *icpt_out)
+// the covariance form (solver_lasso.hip): fits of one fold share its co-occurrence counts
+int lasso_cov_fit(psk_ctx *ctx, const FitArgs &a, const double *y, const std::vector<int32_t> &fold_ids,
+                  const std::vector<int32_t> &fidx, double tol, int max_iter)
 {
-    if (!ctx) return PSK_EINVAL;
-    if (!X || !y || !fold || !fit_param || !fit_fold || !coef_out || !icpt_out)
-        return psk_fail(ctx, PSK_EINVAL, "null buffer");
-    if (n < 2 || p < 1 || n_fits < 1) return psk_fail(ctx, PSK_EINVAL, "bad problem shape n=%d p=%d fits=%d", n, p, n_fits);
-    return PSK_OK;
+    const int n = a.n, p = a.p, n_fits = a.n_fits, W = (n + 63) / 64, PP = 64 * ((p + 63) / 64), F = (int)fold_ids.size();
+    const std::vector<uint64_t> bits = pack_sample_bits(a.X, n, p, W, PP, false);
+    std::vector<uint64_t> tmask((size_t)F * W, 0);
+    std::vector<double> yc((size_t)F * n, 0.0), fstat((size_t)F * 4, 0.0);
+    for (int f = 0; f < F; f++) {
+        double sy = 0.0, cnt = 0.0, yy = 0.0;
+        for (int i = 0; i < n; i++)
+            if (a.fold[i] != fold_ids[f]) { sy += y[i]; cnt += 1.0; tmask[(size_t)f * W + (i >> 6)] |= 1ull << (i & 63); }
+        if (cnt < 1.0) return psk_fail(ctx, PSK_EINVAL, "fold %d leaves no training sample", fold_ids[f]);
+        const double ym = sy / cnt;
+        for (int i = 0; i < n; i++)
+            if (a.fold[i] != fold_ids[f]) { const double d = y[i] - ym; yc[(size_t)f * n + i] = d; yy += d * d; }
+        fstat[4 * f] = ym; fstat[4 * f + 1] = yy; fstat[4 * f + 2] = cnt;
+    }
+    // Workgroups go round the eight XCDs (workgroup b runs on XCD b % 8), each with its own 4-MB L2: the fits are
+    // ordered by fold and XCD x takes a contiguous stretch of that order, so that the fits sharing an L2 read the
+    // same one or two count matrices (1.6 MB each at 907 columns)
+    std::vector<int32_t> order(n_fits);
+    for (int j = 0; j < n_fits; j++) order[j] = j;
+    std::stable_sort(order.begin(), order.end(), [&](int32_t u, int32_t v) { return fidx[u] < fidx[v]; });
+    const int G = (n_fits + 7) / 8, n_blocks = 8 * G;
+    std::vector<int32_t> block_fit(n_blocks, -1);
+    for (int bq = 0; bq < n_blocks; bq++) {
+        const int sidx = (bq % 8) * G + bq / 8;
+        if (sidx < n_fits) block_fit[bq] = order[sidx];
+    }
+    FitIO io;
+    FitArr<uint64_t> d_bits, d_tmask;
+    FitArr<double> d_yc, d_fstat, d_Dg, d_q0;
+    FitArr<uint16_t> d_C;
+    FitArr<int32_t> d_bf, d_fidx;
+    PSK_TRY(io.upload(ctx, a, false));   // the kernels read tmask and fidx, not the folds
+    PSK_HIP(ctx, d_bits.upload(bits, ctx->stream));
+    PSK_HIP(ctx, d_tmask.upload(tmask, ctx->stream));
+    PSK_HIP(ctx, d_yc.upload(yc, ctx->stream));
+    PSK_HIP(ctx, d_fstat.upload(fstat, ctx->stream));
+    PSK_HIP(ctx, d_C.alloc((size_t)F * PP * PP));
+    PSK_HIP(ctx, d_Dg.alloc((size_t)F * (PP / 64) * 4096));
+    PSK_HIP(ctx, d_q0.alloc((size_t)F * PP));
+    PSK_HIP(ctx, d_bf.upload(block_fit, ctx->stream));
+    PSK_HIP(ctx, d_fidx.upload(fidx, ctx->stream));
+    psk_lasso_cov_args A;
+    A.bits = d_bits; A.tmask = d_tmask; A.yc = d_yc; A.fstat = d_fstat; A.C = d_C; A.Dg = d_Dg; A.q0 = d_q0;
+    A.block_fit = d_bf; A.fit_param = io.fit_param; A.fit_fidx = d_fidx;
+    A.n = n; A.p = p; A.PP = PP; A.W = W; A.n_folds = F; A.n_blocks = n_blocks; A.max_iter = max_iter; A.tol = tol;
+    A.coef = io.coef; A.icpt = io.icpt; A.gaps = nullptr; A.iters = io.iters; A.stream = ctx->stream;
+    PSK_HIP(ctx, psk_lasso_cov_launch(A));
+    return io.download(ctx, a);
+}
+
+// the four-wave kernel on the bit-packed samples; `lds`: its per-column state
+int lasso_bits_fit(psk_ctx *ctx, const FitArgs &a, const double *y, size_t lds, double tol, int max_iter)
+{
+    const int n = a.n, p = a.p, W = (n + 63) / 64;
+    const std::vector<uint64_t> bitsT = pack_lane_bits(a.X, n, p, false);
+    FitIO io;
+    FitArr<uint64_t> d_bitsT;
+    FitArr<double> d_y;
+    PSK_TRY(io.upload(ctx, a));
+    PSK_HIP(ctx, d_bitsT.upload(bitsT, ctx->stream));
+    PSK_HIP(ctx, d_y.upload(y, n, ctx->stream));
+    auto kern = W <= 16 ? lasso_bits_kernel<16> : W <= 32 ? lasso_bits_kernel<32> : lasso_bits_kernel<64>;
+    if (lds > 64 * 1024)
+        PSK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    kern<<<a.n_fits, SV_COOP_THREADS, lds, ctx->stream>>>(d_bitsT, d_y, io.fold, n, p, W, io.fit_param, io.fit_fold, tol, max_iter,
+                                                          io.coef, io.icpt, io.iters);
+    return io.download(ctx, a);
+}
+
+int lasso_float_fit(psk_ctx *ctx, const FitArgs &a, const double *y, double tol, int max_iter)
+{
+    const int n = a.n, p = a.p;
+    const std::vector<float> XT = transpose_f32(a.X, n, p, true);
+    const int use_lds = n <= 2 * SV_LDS_N ? 1 : 0;   // one residual array: 8 KiB samples fit
+    const size_t lds = use_lds ? (size_t)n * sizeof(double) : 0;
+    FitIO io;
+    FitArr<float> xt;
+    FitArr<double> d_y, work;
+    PSK_TRY(io.upload(ctx, a));
+    PSK_HIP(ctx, xt.upload(XT, ctx->stream));
+    PSK_HIP(ctx, d_y.upload(y, n, ctx->stream));
+    PSK_HIP(ctx, work.alloc((size_t)a.n_fits * (2 * (size_t)p + n)));
+    lasso_kernel<<<a.n_fits, SV_THREADS, lds, ctx->stream>>>(xt, d_y, io.fold, n, p, io.fit_param, io.fit_fold, tol, max_iter, io.coef,
+                                                             io.icpt, io.iters, work, use_lds);
+    return io.download(ctx, a);
 }
 
 }  // namespace
-
-#define SV_ALLOC(ptr, bytes) PSK_HIP(ctx, hipMalloc(&(ptr), (bytes) ? (bytes) : 8))
 
 extern "C" int psk_logreg_l1_fit(psk_ctx *ctx, const float *X, const int32_t *y01, int n, int p, const int32_t *fold,
                                  const double *fit_param, const int32_t *fit_fold, int n_fits, double tol, int max_iter,
                                  double *coef_out, double *icpt_out, int32_t *iters_out)
 {
-    PSK_TRY(check_fit_args(ctx, X, y01, n, p, fold, fit_param, fit_fold, n_fits, coef_out, icpt_out));
+    const FitArgs a = {X, n, p, fold, fit_param, fit_fold, n_fits, coef_out, icpt_out, iters_out};
+    PSK_TRY(check_fit_args(ctx, a, y01));
     // form knobs, validated before anything is allocated
-    const bool knob_no_cd_regs = env_flag("PSK_NO_CD_REGS"), knob_no_gram = env_flag("PSK_NO_GRAM"),
-               knob_no_gram_global = env_flag("PSK_NO_GRAM_GLOBAL");
-    bool set_min_p1 = false, set_reps = false;
-    int knob_min_p1 = 0, knob_wmreg = 0, knob_cg_max = 16, knob_polish_reps = 0, knob_polish_from = 32;
-    PSK_TRY(env_int(ctx, "PSK_GG_MIN_P1", 1, 1 << 20, &knob_min_p1, &set_min_p1));
-    PSK_TRY(env_choice(ctx, "PSK_FORCE_WMREG", {16, 32, 64}, &knob_wmreg));   // (0: n picks the register form)
+    psk_l1_knobs k;
+    int knob_cg_max = 16, knob_polish_from = 32;
+    k.no_cd_regs = env_flag("PSK_NO_CD_REGS"); k.no_gram = env_flag("PSK_NO_GRAM"); k.no_gram_global = env_flag("PSK_NO_GRAM_GLOBAL");
+    PSK_TRY(env_int(ctx, "PSK_GG_MIN_P1", 1, 1 << 20, &k.min_p1, &k.set_min_p1));
+    PSK_TRY(env_choice(ctx, "PSK_FORCE_WMREG", {16, 32, 64}, &k.force_wmreg));   // (0: n picks the register form)
     PSK_TRY(env_int(ctx, "PSK_CG_MAX", 0, 256, &knob_cg_max));
-    PSK_TRY(env_int(ctx, "PSK_POLISH_REPS", -4096, 4096, &knob_polish_reps, &set_reps));
+    PSK_TRY(env_int(ctx, "PSK_POLISH_REPS", -4096, 4096, &k.polish_reps, &k.set_reps));
     PSK_TRY(env_int(ctx, "PSK_GG_POLISH_FROM", 1, 1000, &knob_polish_from));
-    const bool set_wmreg = knob_wmreg != 0;
-    if (set_wmreg && knob_wmreg * 64 < n)
-        return psk_fail(ctx, PSK_EINVAL, "PSK_FORCE_WMREG=%d holds %d samples, the design has %d", knob_wmreg, knob_wmreg * 64, n);
+    if (k.force_wmreg && k.force_wmreg * 64 < n)
+        return psk_fail(ctx, PSK_EINVAL, "PSK_FORCE_WMREG=%d holds %d samples, the design has %d", k.force_wmreg, k.force_wmreg * 64, n);
     PSK_HIP(ctx, hipSetDevice(ctx->device));
-    std::vector<float> XT;
-    transpose_f32(X, n, p, XT);
-    std::vector<int8_t> ypm(n);
-    for (int i = 0; i < n; i++) ypm[i] = y01[i] ? 1 : -1;
-    SolverBufs b;
-    SV_ALLOC(b.xt, XT.size() * sizeof(float));
-    SV_ALLOC(b.y, (size_t)n);
-    SV_ALLOC(b.fold, (size_t)n * 4);
-    SV_ALLOC(b.param, (size_t)n_fits * 8);
-    SV_ALLOC(b.ffold, (size_t)n_fits * 4);
-    SV_ALLOC(b.coef, (size_t)n_fits * p * 8);
-    SV_ALLOC(b.icpt, (size_t)n_fits * 8);
-    SV_ALLOC(b.iters, (size_t)n_fits * 4);
-    // presence/absence design (every entry 0 or 1)?  -> bit-packed kernel
-    bool binary = n <= 4096;  // the bit-packed kernel keeps a column in one register per lane (64 words)
-    for (size_t q = 0; binary && q < (size_t)n * p; q++) binary = (X[q] == 0.0f || X[q] == 1.0f);
+    // presence/absence design (every entry 0 or 1)?  -> bit-packed kernel, which keeps a column in one register per lane (64 words)
+    const bool binary = n <= 4096 && design_is_binary(X, (size_t)n * p);
     const int W = (n + 63) / 64;
     const size_t n_state = binary ? (size_t)W * 64 : (size_t)n;
-    // placement of the per-fit state: everything in LDS when it fits the 160 KiB of a CU, else the sample
-    // arrays only, else global scratch
-    const size_t fbytes = 5 * (size_t)(p + 1) * 8, sbytes = 5 * n_state * 8, lds_max = 160 * 1024 - 8192;   // the kernels' static LDS (cooperation state of the bit-packed kernel: ~7 KB) comes on top
-    int f_lds = 0, s_lds = 0;
-    if (fbytes + sbytes <= lds_max) f_lds = s_lds = 1;
-    else if (sbytes <= lds_max) s_lds = 1;
-    else if (fbytes <= lds_max) f_lds = 1;
-    const size_t lds = (f_lds ? fbytes : 0) + (s_lds ? sbytes : 0);
-    SV_ALLOC(b.work, (size_t)n_fits * (fbytes + sbytes));
-    SV_ALLOC(b.iwork, (size_t)n_fits * (p + 1) * 4);
-    PSK_HIP(ctx, hipMemcpyAsync(b.y, ypm.data(), n, hipMemcpyHostToDevice, ctx->stream));
-    PSK_HIP(ctx, hipMemcpyAsync(b.fold, fold, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-    PSK_HIP(ctx, hipMemcpyAsync(b.param, fit_param, (size_t)n_fits * 8, hipMemcpyHostToDevice, ctx->stream));
-    PSK_HIP(ctx, hipMemcpyAsync(b.ffold, fit_fold, (size_t)n_fits * 4, hipMemcpyHostToDevice, ctx->stream));
+    const std::vector<int8_t> ypm = labels_pm1(y01, n);
+    FitIO io;
+    FitArr<int8_t> y;
+    FitArr<double> work;
+    FitArr<int32_t> iwork;
+    PSK_TRY(io.upload(ctx, a));
+    PSK_HIP(ctx, y.upload(ypm, ctx->stream));
+    PSK_HIP(ctx, work.alloc((size_t)n_fits * 5 * ((size_t)(p + 1) + n_state)));   // per fit: five feature, five sample arrays
+    PSK_HIP(ctx, iwork.alloc((size_t)n_fits * (p + 1)));
     if (binary) {
-        // LDS budget of the bit-packed kernel.  The inner QP works on the Gram block, the per-feature arrays and the
-        // active list only, so those come first; the five sample arrays are streamed (coalesced) once per Newton
-        // step and line-search trial and move to global scratch when they do not fit beside the Gram block of the
-        // problem (thousands of samples: 5 x 2048 doubles are 80 KiB); the column bit words take what is left.
-        // (With the sample arrays first, a 2048-sample fit with 170 distinct patterns had room for 79 Gram columns,
-        // fell back to the array-form descent and took 0.5 s instead of 0.02 s, r01.)
-        const size_t fa = fbytes + (((size_t)(p + 1) + 1) / 2) * 8, cbytes = (size_t)(p + 1) * W * 8;
-        // More coordinates than the LDS Gram block takes (192): the Gram matrix of a fit in global memory, f32, a column
-        // per slot (gg_run).  Its LDS arrays (slot parameters, ring, D in operand order, orders, flags) take the place of
-        // the Gram block; the feature arrays must be in LDS beside them.
-        const int P1 = p + 1, wmreg_h = knob_no_cd_regs ? 0 : (W <= 16 ? 16 : W <= 32 ? 32 : 64);
-        int gg_sl = 0;
-        size_t gg_stride = 0, gg_lds = 0;
-        // up to 192 columns the LDS Gram form (exact f64 Hessian, columns built sample by sample) keeps the designs with
-        // fewer than 1,024 samples: its builds are cheap there and an ill-conditioned fit at a tight tolerance converges in
-        // fewer Newton steps than with the f32 / bf16-split Q of the global form (256 x 150 near-duplicates at tol = 1e-7:
-        // inside 300 steps against not); from 1,024 samples on the global form is 3-10 x faster (2048 x 169 grid 0.27 ->
-        // 0.03 s, 2000 x 150: 0.14 -> 0.012 s)
-        const int gg_min_p1 = set_min_p1 ? knob_min_p1 : (n >= 1024 ? 64 : 192);
-        if (P1 > gg_min_p1 && P1 <= 1024 && wmreg_h > 0 && SV_COOP_WAVES == 4 && !knob_no_gram && !knob_no_gram_global) {
-            const size_t sl = 256 * (((size_t)P1 + 255) / 256), np_h = (size_t)W * 64;
-            // (+ the build's tables / wave 3's counters, + the owners' column buffers)
-            const size_t need = (4 * sl + np_h + sl / 2 + sl / 4 + sl / 8) * 8 + 8192 + 16384, stride = (((size_t)P1 + 15) / 16 * 16) * sl;
-            if (fa + need <= lds_max && (size_t)n_fits * stride * 4 <= ((size_t)32 << 30)) {
-                // (a device too full for the Gram matrices keeps the array form: slower, the same optimum)
-                if (hipMalloc(&b.ggq, (size_t)n_fits * stride * 4) == hipSuccess) { gg_sl = (int)sl; gg_stride = stride; gg_lds = need; }
-                else { (void)hipGetLastError(); b.ggq = nullptr; }
-            }
-        }
-        const bool gram = !knob_no_gram && gg_sl == 0;
-        const size_t pq = (size_t)(p + 1) < 192 ? (size_t)(p + 1) : 192;   // Gram columns the kernel can use
-        const size_t need_q = gram ? pq * (pq + 1) / 2 * 8 : 0;             // its packed triangle
-        size_t left = lds_max - gg_lds;
-        f_lds = fa <= left ? 1 : 0; left -= f_lds ? fa : 0;
-        // sample arrays: all five when they fit beside the whole Gram block; else only the two hot ones (tau, D) if
-        // THAT makes room for the whole Gram block (thousands of samples, up to ~170 distinct patterns: the Gram form
-        // with its accelerator converges where the array form runs into its sweep limit, r01: 2048 x 170, objective sum
-        // of the grid 8.051e6 against 8.153e6, 0.73 s against 1.06 s); else all five again with a partial Gram block in
-        // what is left (the previous behaviour); the hot ones alone when five do not fit at all
-        const size_t hot_b = sbytes / 5 * 2;
-        if (sbytes + need_q <= left) s_lds = 3;
-        else if (gram && hot_b + need_q <= left) s_lds = 1;
-        else if (sbytes <= left) s_lds = 3;
-        else s_lds = hot_b <= left ? 1 : 0;
-        const size_t s_in_lds = s_lds == 3 ? sbytes : (s_lds == 1 ? hot_b : 0);
-        left -= s_in_lds;
-        // the Gram block: up to the packed triangle of 192 features (a 64 x 64 or 128 x 128 square is preferred by the
-        // kernel when it fits), before the column words
-        size_t q_doubles = 0;
-        if (gram) {
-            const size_t square = pq <= 64 ? 64 * 64 : (pq <= 128 ? 128 * 128 : 0);
-            q_doubles = need_q / 8;
-            if (square * 8 <= left && square > q_doubles) q_doubles = square;
-            if (q_doubles * 8 > left) q_doubles = left / 8;
-            if (q_doubles < 36) q_doubles = 0;
-        }
-        left -= q_doubles * 8;
-        const int c_lds = cbytes <= left ? 1 : 0; left -= c_lds ? cbytes : 0;
-        if (gram && left >= 8) {   // leftover goes to the Gram block too (a square layout may now fit)
-            const size_t most = (size_t)192 * 193 / 2;
-            size_t more = q_doubles + left / 8;
-            if (more > most) more = most;
-            q_doubles = more;
-        }
-        if (gg_sl) q_doubles = gg_lds / 8;
-        const size_t qbytes = q_doubles * 8;
-        const int q_lds = q_doubles > 0;
-        const size_t lds_b = s_in_lds + qbytes + (f_lds ? fa : 0) + (c_lds ? cbytes : 0);
-        std::vector<uint64_t> bits((size_t)(p + 1) * W, 0);
-        for (int i = 0; i < n; i++) {
-            for (int j = 0; j < p; j++)
-                if (X[(size_t)i * p + j] != 0.0f) bits[(size_t)j * W + (i >> 6)] |= 1ull << (i & 63);
-            bits[(size_t)p * W + (i >> 6)] |= 1ull << (i & 63);  // constant-1 intercept column
-        }
-        SV_ALLOC(b.bits, bits.size() * 8);
-        PSK_HIP(ctx, hipMemcpyAsync(b.bits, bits.data(), bits.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-        // the same columns transposed for the register form of the descent: bit t of word l = sample 64 t + l
-        std::vector<uint64_t> bitsT(!knob_no_cd_regs ? (size_t)(p + 1) * 64 : 0, 0);
-        if (!bitsT.empty()) {
-            for (int j = 0; j <= p; j++)
-                for (int t = 0; t < W; t++) {
-                    uint64_t x = bits[(size_t)j * W + t];
-                    while (x) {
-                        const int l = __builtin_ctzll(x);
-                        x &= x - 1;
-                        bitsT[(size_t)j * 64 + l] |= 1ull << t;
-                    }
-                }
-            SV_ALLOC(b.bitsT, bitsT.size() * 8);
-            PSK_HIP(ctx, hipMemcpyAsync(b.bitsT, bitsT.data(), bitsT.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-        }
-        const bool all_lds = f_lds && s_lds == 3 && c_lds && q_lds;
-        const int wmreg = bitsT.empty() ? 0 : set_wmreg ? knob_wmreg : (W <= 16 ? 16 : W <= 32 ? 32 : 64);
+        const std::vector<uint64_t> bits = pack_sample_bits(X, n, p, W, p + 1, true);
+        // the same columns transposed for the register form of the descent
+        const std::vector<uint64_t> bitsT = k.no_cd_regs ? std::vector<uint64_t>() : pack_lane_bits(X, n, p, true);
+        FitArr<uint64_t> d_bits, d_bitsT;
+        FitArr<float> ggq;
+        PSK_HIP(ctx, d_bits.upload(bits, ctx->stream));
+        if (!bitsT.empty()) PSK_HIP(ctx, d_bitsT.upload(bitsT, ctx->stream));
+        psk_l1_placement P = psk_l1_gg_wanted(n, p, W, n_fits, k, SV_COOP_WAVES);
+        // (a device too full for the Gram matrices keeps the array form: slower, the same optimum)
+        if (P.gg_sl && ggq.alloc((size_t)n_fits * P.gg_stride) != hipSuccess) { (void)hipGetLastError(); P = psk_l1_placement(); }
+        P = psk_l1_place(p, W, k, P);
         psk_l1_bits_launch L;
-        L.bits = (const uint64_t *)b.bits; L.bitsT = (const uint64_t *)b.bitsT; L.ypm = (const int8_t *)b.y;
-        L.fold = (const int32_t *)b.fold; L.fit_fold = (const int32_t *)b.ffold; L.fit_param = (const double *)b.param;
+        L.bits = d_bits; L.bitsT = d_bitsT; L.ypm = y;
+        L.fold = io.fold; L.fit_fold = io.fit_fold; L.fit_param = io.fit_param;
         L.n = n; L.p = p; L.W = W; L.n_fits = n_fits; L.max_iter = max_iter; L.tol = tol;
-        L.coef = (double *)b.coef; L.icpt = (double *)b.icpt; L.work = (double *)b.work; L.iters = (int32_t *)b.iters; L.iwork = (int32_t *)b.iwork;
-        L.f_lds = f_lds; L.s_lds = s_lds; L.c_lds = c_lds; L.q_doubles = (int)q_doubles;
+        L.coef = io.coef; L.icpt = io.icpt; L.work = work; L.iters = io.iters; L.iwork = iwork;
+        L.f_lds = P.f_lds; L.s_lds = P.s_lds; L.c_lds = P.c_lds; L.q_doubles = P.q_doubles;
         // CG steps per polish (the Gram-global form uses a quarter of them, at least 4, while steps are cut short early)
         L.cg_max = knob_cg_max;
-        // polishes in a row while signs change; negative (the Gram-global form's default): as many as the descent has needed
-        // sweeps when the accelerator is called (32, 64, 128), at most that many -- the 2048 x 169 grid 0.105 -> 0.031 s, the
-        // 2048 x 907 grid 0.236 -> 0.245 s against a fixed 64
-        L.polish_reps = set_reps ? knob_polish_reps : (gg_sl ? -128 : 64);
-        L.gg_sl = gg_sl; L.gg_q = (float *)b.ggq; L.gg_stride = gg_stride;
+        L.polish_reps = P.polish_reps;
+        L.gg_sl = P.gg_sl; L.gg_q = ggq; L.gg_stride = P.gg_stride;
         L.gg_polish_from = knob_polish_from;   // first polish of a descent after this many sweeps
-        L.wmreg = wmreg; L.all_lds = all_lds ? 1 : 0; L.lds_bytes = lds_b; L.stream = ctx->stream;
+        L.wmreg = P.wmreg; L.all_lds = P.all_lds; L.lds_bytes = P.lds_bytes; L.stream = ctx->stream;
         // two kernels, compiled apart (solver_l1_bits.h): the Gram matrix in global memory, or the LDS Gram block / array forms
-        PSK_HIP(ctx, gg_sl ? psk_l1_bits_launch_gg(L) : psk_l1_bits_launch_gram(L));
-        PSK_HIP(ctx, hipGetLastError());
-        PSK_HIP(ctx, hipStreamSynchronize(ctx->stream));  // `bits` (host) must outlive the copy
-    } else {
-        PSK_HIP(ctx, hipMemcpyAsync(b.xt, XT.data(), XT.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-        if (lds > 64 * 1024)
-            PSK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(logreg_newglmnet_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        logreg_newglmnet_kernel<<<n_fits, SV_THREADS, lds, ctx->stream>>>(
-            (const float *)b.xt, (const int8_t *)b.y, (const int32_t *)b.fold, n, p, (const double *)b.param,
-            (const int32_t *)b.ffold, tol, max_iter, (double *)b.coef, (double *)b.icpt, (int32_t *)b.iters,
-            (double *)b.work, (int32_t *)b.iwork, f_lds, s_lds);
+        PSK_HIP(ctx, P.gg_sl ? psk_l1_bits_launch_gg(L) : psk_l1_bits_launch_gram(L));
+        return io.download(ctx, a);   // (synchronises: `bits` and `bitsT` outlive their copies)
     }
-    PSK_HIP(ctx, hipGetLastError());
-    PSK_HIP(ctx, hipMemcpyAsync(coef_out, b.coef, (size_t)n_fits * p * 8, hipMemcpyDeviceToHost, ctx->stream));
-    PSK_HIP(ctx, hipMemcpyAsync(icpt_out, b.icpt, (size_t)n_fits * 8, hipMemcpyDeviceToHost, ctx->stream));
-    std::vector<int32_t> it(n_fits);
-    PSK_HIP(ctx, hipMemcpyAsync(it.data(), b.iters, (size_t)n_fits * 4, hipMemcpyDeviceToHost, ctx->stream));
-    PSK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (iters_out) memcpy(iters_out, it.data(), (size_t)n_fits * 4);
-    return PSK_OK;
+    // placement of the per-fit state: everything in LDS when it fits the 160 KiB of a CU, else the sample
+    // arrays only, else global scratch
+    const size_t fbytes = psk_l1_feature_bytes(p), sbytes = 5 * n_state * 8;
+    int f_lds = 0, s_lds = 0;
+    if (fbytes + sbytes <= PSK_L1_LDS_MAX) f_lds = s_lds = 1;
+    else if (sbytes <= PSK_L1_LDS_MAX) s_lds = 1;
+    else if (fbytes <= PSK_L1_LDS_MAX) f_lds = 1;
+    const size_t lds = (f_lds ? fbytes : 0) + (s_lds ? sbytes : 0);
+    const std::vector<float> XT = transpose_f32(X, n, p, true);
+    FitArr<float> xt;
+    PSK_HIP(ctx, xt.upload(XT, ctx->stream));
+    if (lds > 64 * 1024)
+        PSK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(logreg_newglmnet_kernel),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    logreg_newglmnet_kernel<<<n_fits, SV_THREADS, lds, ctx->stream>>>(xt, y, io.fold, n, p, io.fit_param, io.fit_fold, tol, max_iter, io.coef,
+                                                                      io.icpt, io.iters, work, iwork, f_lds, s_lds);
+    return io.download(ctx, a);
 }
 
 extern "C" int psk_lasso_fit(psk_ctx *ctx, const float *X, const double *y, int n, int p, const int32_t *fold,
                              const double *fit_param, const int32_t *fit_fold, int n_fits, double tol, int max_iter,
                              double *coef_out, double *icpt_out, int32_t *iters_out)
 {
-    PSK_TRY(check_fit_args(ctx, X, y, n, p, fold, fit_param, fit_fold, n_fits, coef_out, icpt_out));
+    const FitArgs a = {X, n, p, fold, fit_param, fit_fold, n_fits, coef_out, icpt_out, iters_out};
+    PSK_TRY(check_fit_args(ctx, a, y));
     PSK_HIP(ctx, hipSetDevice(ctx->device));
-    std::vector<float> XT;
-    transpose_f32(X, n, p, XT);
-    SolverBufs b;
-    SV_ALLOC(b.xt, XT.size() * sizeof(float));
-    SV_ALLOC(b.y, (size_t)n * 8);
-    SV_ALLOC(b.fold, (size_t)n * 4);
-    SV_ALLOC(b.param, (size_t)n_fits * 8);
-    SV_ALLOC(b.ffold, (size_t)n_fits * 4);
-    SV_ALLOC(b.coef, (size_t)n_fits * p * 8);
-    SV_ALLOC(b.icpt, (size_t)n_fits * 8);
-    SV_ALLOC(b.iters, (size_t)n_fits * 4);
-    // presence/absence design (every entry 0 or 1): the covariance form (solver_lasso.hip) up to 1,024 columns, else the
-    // four-wave kernel on the bit-packed samples (per-column state in LDS); PSK_NO_LASSO_COV / PSK_NO_LASSO_BITS for A/B runs
-    bool binary = n <= 4096 && !env_flag("PSK_NO_LASSO_BITS");
-    for (size_t q = 0; binary && q < (size_t)n * p; q++) binary = (X[q] == 0.0f || X[q] == 1.0f);
+    // presence/absence design (every entry 0 or 1): the covariance form up to 1,024 columns and 2 GiB of count matrices, else
+    // the four-wave kernel on the bit-packed samples while its per-column state fits in LDS; else the float kernel.
+    // PSK_NO_LASSO_COV / PSK_NO_LASSO_BITS for A/B runs
+    const bool binary = n <= 4096 && !env_flag("PSK_NO_LASSO_BITS") && design_is_binary(X, (size_t)n * p);
     if (binary && p <= 1024 && !env_flag("PSK_NO_LASSO_COV")) {
-        const int W = (n + 63) / 64, PP = 64 * ((p + 63) / 64);
-        // the distinct held-out folds of the call: fits of one fold share its counts
-        std::vector<int32_t> fold_ids, fidx(n_fits);
-        for (int j = 0; j < n_fits; j++) {
-            size_t q = 0;
-            while (q < fold_ids.size() && fold_ids[q] != fit_fold[j]) q++;
-            if (q == fold_ids.size()) fold_ids.push_back(fit_fold[j]);
-            fidx[j] = (int32_t)q;
-        }
-        const int F = (int)fold_ids.size();
-        if ((size_t)F * PP * PP * 2 <= ((size_t)2 << 30)) {
-            std::vector<uint64_t> bits((size_t)PP * W, 0), tmask((size_t)F * W, 0);
-            for (int i = 0; i < n; i++)
-                for (int j = 0; j < p; j++)
-                    if (X[(size_t)i * p + j] != 0.0f) bits[(size_t)j * W + (i >> 6)] |= 1ull << (i & 63);
-            std::vector<double> yc((size_t)F * n, 0.0), fstat((size_t)F * 4, 0.0);
-            for (int f = 0; f < F; f++) {
-                double sy = 0.0, cnt = 0.0, yy = 0.0;
-                for (int i = 0; i < n; i++)
-                    if (fold[i] != fold_ids[f]) { sy += y[i]; cnt += 1.0; tmask[(size_t)f * W + (i >> 6)] |= 1ull << (i & 63); }
-                if (cnt < 1.0) return psk_fail(ctx, PSK_EINVAL, "fold %d leaves no training sample", fold_ids[f]);
-                const double ym = sy / cnt;
-                for (int i = 0; i < n; i++)
-                    if (fold[i] != fold_ids[f]) { const double d = y[i] - ym; yc[(size_t)f * n + i] = d; yy += d * d; }
-                fstat[4 * f] = ym; fstat[4 * f + 1] = yy; fstat[4 * f + 2] = cnt;
-            }
-            // Workgroups go round the eight XCDs (workgroup b runs on XCD b % 8), each with its own 4-MB L2: the fits are
-            // ordered by fold and XCD x takes a contiguous stretch of that order, so that the fits sharing an L2 read the
-            // same one or two count matrices (1.6 MB each at 907 columns)
-            std::vector<int32_t> order(n_fits);
-            for (int j = 0; j < n_fits; j++) order[j] = j;
-            std::stable_sort(order.begin(), order.end(), [&](int32_t u, int32_t v) { return fidx[u] < fidx[v]; });
-            const int G = (n_fits + 7) / 8, n_blocks = 8 * G;
-            std::vector<int32_t> block_fit(n_blocks, -1);
-            for (int bq = 0; bq < n_blocks; bq++) {
-                const int sidx = (bq % 8) * G + bq / 8;
-                if (sidx < n_fits) block_fit[bq] = order[sidx];
-            }
-            void *d_bits = nullptr, *d_tmask = nullptr, *d_yc = nullptr, *d_fstat = nullptr, *d_C = nullptr, *d_Dg = nullptr, *d_q0 = nullptr,
-                 *d_bf = nullptr, *d_fidx = nullptr;
-            struct Free { std::vector<void **> v; ~Free() { for (void **q : v) if (*q) (void)hipFree(*q); } } fr;
-            fr.v = {&d_bits, &d_tmask, &d_yc, &d_fstat, &d_C, &d_Dg, &d_q0, &d_bf, &d_fidx};
-            SV_ALLOC(d_bits, bits.size() * 8);
-            SV_ALLOC(d_tmask, tmask.size() * 8);
-            SV_ALLOC(d_yc, yc.size() * 8);
-            SV_ALLOC(d_fstat, fstat.size() * 8);
-            SV_ALLOC(d_C, (size_t)F * PP * PP * 2);
-            SV_ALLOC(d_Dg, (size_t)F * (PP / 64) * 4096 * 8);
-            SV_ALLOC(d_q0, (size_t)F * PP * 8);
-            SV_ALLOC(d_bf, (size_t)n_blocks * 4);
-            SV_ALLOC(d_fidx, (size_t)n_fits * 4);
-            PSK_HIP(ctx, hipMemcpyAsync(d_bits, bits.data(), bits.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-            PSK_HIP(ctx, hipMemcpyAsync(d_tmask, tmask.data(), tmask.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-            PSK_HIP(ctx, hipMemcpyAsync(d_yc, yc.data(), yc.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-            PSK_HIP(ctx, hipMemcpyAsync(d_fstat, fstat.data(), fstat.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-            PSK_HIP(ctx, hipMemcpyAsync(d_bf, block_fit.data(), (size_t)n_blocks * 4, hipMemcpyHostToDevice, ctx->stream));
-            PSK_HIP(ctx, hipMemcpyAsync(d_fidx, fidx.data(), (size_t)n_fits * 4, hipMemcpyHostToDevice, ctx->stream));
-            PSK_HIP(ctx, hipMemcpyAsync(b.param, fit_param, (size_t)n_fits * 8, hipMemcpyHostToDevice, ctx->stream));
-            psk_lasso_cov_args A;
-            A.bits = (const uint64_t *)d_bits; A.tmask = (const uint64_t *)d_tmask; A.yc = (const double *)d_yc;
-            A.fstat = (const double *)d_fstat; A.C = (uint16_t *)d_C; A.Dg = (double *)d_Dg; A.q0 = (double *)d_q0;
-            A.block_fit = (const int32_t *)d_bf; A.fit_param = (const double *)b.param; A.fit_fidx = (const int32_t *)d_fidx;
-            A.n = n; A.p = p; A.PP = PP; A.W = W; A.n_folds = F; A.n_blocks = n_blocks; A.max_iter = max_iter; A.tol = tol;
-            A.coef = (double *)b.coef; A.icpt = (double *)b.icpt; A.gaps = nullptr; A.iters = (int32_t *)b.iters; A.stream = ctx->stream;
-            PSK_HIP(ctx, psk_lasso_cov_launch(A));
-            PSK_HIP(ctx, hipMemcpyAsync(coef_out, b.coef, (size_t)n_fits * p * 8, hipMemcpyDeviceToHost, ctx->stream));
-            PSK_HIP(ctx, hipMemcpyAsync(icpt_out, b.icpt, (size_t)n_fits * 8, hipMemcpyDeviceToHost, ctx->stream));
-            std::vector<int32_t> itc(n_fits);
-            PSK_HIP(ctx, hipMemcpyAsync(itc.data(), b.iters, (size_t)n_fits * 4, hipMemcpyDeviceToHost, ctx->stream));
-            PSK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the host vectors must outlive their copies
-            if (iters_out) memcpy(iters_out, itc.data(), (size_t)n_fits * 4);
-            return PSK_OK;
-        }
+        std::vector<int32_t> fidx;
+        const std::vector<int32_t> fold_ids = distinct_folds(fit_fold, n_fits, fidx);
+        const size_t PP = 64 * (((size_t)p + 63) / 64);
+        if (fold_ids.size() * PP * PP * 2 <= ((size_t)2 << 30)) return lasso_cov_fit(ctx, a, y, fold_ids, fidx, tol, max_iter);
     }
     const size_t lds_bits = (size_t)p * (4 * 8 + SV_COOP_WAVES * 4);
-    if (binary && lds_bits <= 150 * 1024) {
-        const int W = (n + 63) / 64;
-        std::vector<uint64_t> bitsT((size_t)p * 64, 0);   // word l of column j: bit t = sample 64 t + l
-        for (int i = 0; i < n; i++)
-            for (int j = 0; j < p; j++)
-                if (X[(size_t)i * p + j] != 0.0f) bitsT[(size_t)j * 64 + (i & 63)] |= 1ull << (i >> 6);
-        SV_ALLOC(b.bitsT, bitsT.size() * 8);
-        PSK_HIP(ctx, hipMemcpyAsync(b.bitsT, bitsT.data(), bitsT.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-        PSK_HIP(ctx, hipMemcpyAsync(b.y, y, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-        PSK_HIP(ctx, hipMemcpyAsync(b.fold, fold, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-        PSK_HIP(ctx, hipMemcpyAsync(b.param, fit_param, (size_t)n_fits * 8, hipMemcpyHostToDevice, ctx->stream));
-        PSK_HIP(ctx, hipMemcpyAsync(b.ffold, fit_fold, (size_t)n_fits * 4, hipMemcpyHostToDevice, ctx->stream));
-        auto kern = W <= 16 ? lasso_bits_kernel<16> : W <= 32 ? lasso_bits_kernel<32> : lasso_bits_kernel<64>;
-        if (lds_bits > 64 * 1024)
-            PSK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bits));
-        kern<<<n_fits, SV_COOP_THREADS, lds_bits, ctx->stream>>>((const uint64_t *)b.bitsT, (const double *)b.y, (const int32_t *)b.fold, n, p, W,
-                                                                 (const double *)b.param, (const int32_t *)b.ffold, tol, max_iter,
-                                                                 (double *)b.coef, (double *)b.icpt, (int32_t *)b.iters);
-        PSK_HIP(ctx, hipGetLastError());
-        PSK_HIP(ctx, hipMemcpyAsync(coef_out, b.coef, (size_t)n_fits * p * 8, hipMemcpyDeviceToHost, ctx->stream));
-        PSK_HIP(ctx, hipMemcpyAsync(icpt_out, b.icpt, (size_t)n_fits * 8, hipMemcpyDeviceToHost, ctx->stream));
-        std::vector<int32_t> itb(n_fits);
-        PSK_HIP(ctx, hipMemcpyAsync(itb.data(), b.iters, (size_t)n_fits * 4, hipMemcpyDeviceToHost, ctx->stream));
-        PSK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // bitsT (host) must outlive its copy
-        if (iters_out) memcpy(iters_out, itb.data(), (size_t)n_fits * 4);
-        return PSK_OK;
-    }
-    const int use_lds = n <= 2 * SV_LDS_N ? 1 : 0;   // one residual array: 8 KiB samples fit
-    const size_t lds = use_lds ? (size_t)n * sizeof(double) : 0;
-    SV_ALLOC(b.work, (size_t)n_fits * (2 * (size_t)p + n) * 8);
-    PSK_HIP(ctx, hipMemcpyAsync(b.xt, XT.data(), XT.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    PSK_HIP(ctx, hipMemcpyAsync(b.y, y, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    PSK_HIP(ctx, hipMemcpyAsync(b.fold, fold, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-    PSK_HIP(ctx, hipMemcpyAsync(b.param, fit_param, (size_t)n_fits * 8, hipMemcpyHostToDevice, ctx->stream));
-    PSK_HIP(ctx, hipMemcpyAsync(b.ffold, fit_fold, (size_t)n_fits * 4, hipMemcpyHostToDevice, ctx->stream));
-    lasso_kernel<<<n_fits, SV_THREADS, lds, ctx->stream>>>((const float *)b.xt, (const double *)b.y,
-                                                           (const int32_t *)b.fold, n, p, (const double *)b.param,
-                                                           (const int32_t *)b.ffold, tol, max_iter, (double *)b.coef,
-                                                           (double *)b.icpt, (int32_t *)b.iters, (double *)b.work,
-                                                           use_lds);
-    PSK_HIP(ctx, hipGetLastError());
-    PSK_HIP(ctx, hipMemcpyAsync(coef_out, b.coef, (size_t)n_fits * p * 8, hipMemcpyDeviceToHost, ctx->stream));
-    PSK_HIP(ctx, hipMemcpyAsync(icpt_out, b.icpt, (size_t)n_fits * 8, hipMemcpyDeviceToHost, ctx->stream));
-    std::vector<int32_t> it(n_fits);
-    PSK_HIP(ctx, hipMemcpyAsync(it.data(), b.iters, (size_t)n_fits * 4, hipMemcpyDeviceToHost, ctx->stream));
-    PSK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (iters_out) memcpy(iters_out, it.data(), (size_t)n_fits * 4);
-    return PSK_OK;
+    if (binary && lds_bits <= 150 * 1024) return lasso_bits_fit(ctx, a, y, lds_bits, tol, max_iter);
+    return lasso_float_fit(ctx, a, y, tol, max_iter);
 }

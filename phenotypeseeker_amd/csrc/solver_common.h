@@ -1,6 +1,9 @@
-// Shared by the solver translation units (solver.hip: float kernels, Lasso, the host entry points; solver_l1_gram.hip /
-// solver_l1_gg.hip: the two bit-packed L1-logistic kernels): launch shape constants, lane-0 loads, additions under a lane
-// mask held in SGPRs, and the launch record the host hands to the bit-packed kernels.
+// Device-side helpers and launch records of the L1 solvers.  Included by solver.hip (the float L1-logistic and Lasso
+// kernels, the four-wave bit-packed Lasso, the entry points psk_logreg_l1_fit and psk_lasso_fit), by solver_l1_bits.h (the
+// bit-packed L1-logistic kernel, compiled twice: solver_l1_gram.hip, solver_l1_gg.hip) and by solver_lasso.hip (the
+// covariance-form Lasso).  It holds the launch shape constants, the lane-0 load, the additions under a lane mask held in
+// SGPRs, and the two records the entry points hand to the kernels compiled apart: psk_l1_bits_launch, psk_lasso_cov_args.
+// The host side of the entry points is in solver_host.h, the LDS placement of the bit-packed L1 kernel in solver_l1_plan.h.
 #pragma once
 #include <type_traits>
 

@@ -13,11 +13,11 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstring>
 #include <vector>
 
 #include "dev_utils.h"
 #include "psk_internal.h"
+#include "solver_host.h"
 
 namespace {
 
@@ -298,101 +298,50 @@ __global__ __launch_bounds__(L2_THREADS) void logreg_l2_newton_kernel(
     if (tid == 0) { icpt[fit] = b; iters[fit] = newton; }
 }
 
-struct L2Bufs {
-    void *x = nullptr, *xt = nullptr, *y = nullptr, *fold = nullptr, *param = nullptr, *ffold = nullptr, *coef = nullptr,
-         *icpt = nullptr, *iters = nullptr, *work = nullptr;
-    ~L2Bufs()
-    {
-        void *ps[] = {x, xt, y, fold, param, ffold, coef, icpt, iters, work};
-        for (void *q : ps) if (q) (void)hipFree(q);
-    }
-};
-
-int check_l2_args(psk_ctx *ctx, const void *X, const void *y, int n, int p, const int32_t *fold, const double *fit_param,
-                  const int32_t *fit_fold, int n_fits, double *coef_out, double *icpt_out)
-{
-    if (!ctx) return PSK_EINVAL;
-    if (!X || !y || !fold || !fit_param || !fit_fold || !coef_out || !icpt_out)
-        return psk_fail(ctx, PSK_EINVAL, "null buffer");
-    if (n < 2 || p < 1 || n_fits < 1) return psk_fail(ctx, PSK_EINVAL, "bad problem shape n=%d p=%d fits=%d", n, p, n_fits);
-    return PSK_OK;
-}
-
-#define L2_ALLOC(ptr, bytes) PSK_HIP(ctx, hipMalloc(&(ptr), (bytes) ? (bytes) : 8))
-
-// uploads the shared inputs; `work_doubles` = per-fit scratch length
-int l2_upload(psk_ctx *ctx, L2Bufs &b, const float *X, int n, int p, const int32_t *fold, const double *fit_param,
-              const int32_t *fit_fold, int n_fits, size_t work_doubles, std::vector<float> &XT)
-{
-    XT.resize((size_t)n * p);
-    for (int i = 0; i < n; i++)
-        for (int j = 0; j < p; j++) XT[(size_t)j * n + i] = X[(size_t)i * p + j];
-    L2_ALLOC(b.x, (size_t)n * p * 4);
-    L2_ALLOC(b.xt, (size_t)n * p * 4);
-    L2_ALLOC(b.fold, (size_t)n * 4);
-    L2_ALLOC(b.param, (size_t)n_fits * 8);
-    L2_ALLOC(b.ffold, (size_t)n_fits * 4);
-    L2_ALLOC(b.coef, (size_t)n_fits * p * 8);
-    L2_ALLOC(b.icpt, (size_t)n_fits * 8);
-    L2_ALLOC(b.iters, (size_t)n_fits * 4);
-    L2_ALLOC(b.work, (size_t)n_fits * work_doubles * 8);
-    PSK_HIP(ctx, hipMemcpyAsync(b.x, X, (size_t)n * p * 4, hipMemcpyHostToDevice, ctx->stream));
-    PSK_HIP(ctx, hipMemcpyAsync(b.xt, XT.data(), (size_t)n * p * 4, hipMemcpyHostToDevice, ctx->stream));
-    PSK_HIP(ctx, hipMemcpyAsync(b.fold, fold, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-    PSK_HIP(ctx, hipMemcpyAsync(b.param, fit_param, (size_t)n_fits * 8, hipMemcpyHostToDevice, ctx->stream));
-    PSK_HIP(ctx, hipMemcpyAsync(b.ffold, fit_fold, (size_t)n_fits * 4, hipMemcpyHostToDevice, ctx->stream));
-    return PSK_OK;
-}
-
-int l2_download(psk_ctx *ctx, L2Bufs &b, int p, int n_fits, double *coef_out, double *icpt_out, int32_t *iters_out)
-{
-    PSK_HIP(ctx, hipGetLastError());
-    std::vector<int32_t> it(n_fits);
-    PSK_HIP(ctx, hipMemcpyAsync(coef_out, b.coef, (size_t)n_fits * p * 8, hipMemcpyDeviceToHost, ctx->stream));
-    PSK_HIP(ctx, hipMemcpyAsync(icpt_out, b.icpt, (size_t)n_fits * 8, hipMemcpyDeviceToHost, ctx->stream));
-    PSK_HIP(ctx, hipMemcpyAsync(it.data(), b.iters, (size_t)n_fits * 4, hipMemcpyDeviceToHost, ctx->stream));
-    PSK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (iters_out) memcpy(iters_out, it.data(), (size_t)n_fits * 4);
-    return PSK_OK;
-}
-
 }  // namespace
 
+// Both entry points keep X in both orientations (x, xt) and a per-fit scratch slice in `work`.
 extern "C" int psk_ridge_fit(psk_ctx *ctx, const float *X, const double *y, int n, int p, const int32_t *fold,
                              const double *fit_param, const int32_t *fit_fold, int n_fits, double *coef_out,
                              double *icpt_out, int32_t *iters_out)
 {
-    PSK_TRY(check_l2_args(ctx, X, y, n, p, fold, fit_param, fit_fold, n_fits, coef_out, icpt_out));
+    const FitArgs a = {X, n, p, fold, fit_param, fit_fold, n_fits, coef_out, icpt_out, iters_out};
+    PSK_TRY(check_fit_args(ctx, a, y));
     PSK_HIP(ctx, hipSetDevice(ctx->device));
-    L2Bufs b;
-    std::vector<float> XT;
-    PSK_TRY(l2_upload(ctx, b, X, n, p, fold, fit_param, fit_fold, n_fits, 5 * (size_t)p + 2 * (size_t)n, XT));
-    L2_ALLOC(b.y, (size_t)n * 8);
-    PSK_HIP(ctx, hipMemcpyAsync(b.y, y, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    ridge_cg_kernel<<<n_fits, L2_THREADS, 0, ctx->stream>>>(
-        (const float *)b.x, (const float *)b.xt, (const double *)b.y, (const int32_t *)b.fold, n, p,
-        (const double *)b.param, (const int32_t *)b.ffold, (double *)b.coef, (double *)b.icpt, (int32_t *)b.iters,
-        (double *)b.work);
-    return l2_download(ctx, b, p, n_fits, coef_out, icpt_out, iters_out);
+    const std::vector<float> XT = transpose_f32(X, n, p, false);
+    FitIO io;
+    FitArr<float> x, xt;
+    FitArr<double> d_y, work;
+    PSK_TRY(io.upload(ctx, a));
+    PSK_HIP(ctx, x.upload(X, (size_t)n * p, ctx->stream));
+    PSK_HIP(ctx, xt.upload(XT, ctx->stream));
+    PSK_HIP(ctx, work.alloc((size_t)n_fits * (5 * (size_t)p + 2 * (size_t)n)));
+    PSK_HIP(ctx, d_y.upload(y, n, ctx->stream));
+    ridge_cg_kernel<<<n_fits, L2_THREADS, 0, ctx->stream>>>(x, xt, d_y, io.fold, n, p, io.fit_param, io.fit_fold, io.coef, io.icpt, io.iters,
+                                                            work);
+    return io.download(ctx, a);
 }
 
 extern "C" int psk_logreg_l2_fit(psk_ctx *ctx, const float *X, const int32_t *y01, int n, int p, const int32_t *fold,
                                  const double *fit_param, const int32_t *fit_fold, int n_fits, double tol, int max_iter,
                                  int penalise_intercept, double *coef_out, double *icpt_out, int32_t *iters_out)
 {
-    PSK_TRY(check_l2_args(ctx, X, y01, n, p, fold, fit_param, fit_fold, n_fits, coef_out, icpt_out));
+    const FitArgs a = {X, n, p, fold, fit_param, fit_fold, n_fits, coef_out, icpt_out, iters_out};
+    PSK_TRY(check_fit_args(ctx, a, y01));
     if (!(tol > 0.0) || max_iter < 1) return psk_fail(ctx, PSK_EINVAL, "tol must be > 0 and max_iter >= 1");
     PSK_HIP(ctx, hipSetDevice(ctx->device));
-    L2Bufs b;
-    std::vector<float> XT;
-    PSK_TRY(l2_upload(ctx, b, X, n, p, fold, fit_param, fit_fold, n_fits, 5 * (size_t)p + 4 * (size_t)n, XT));
-    std::vector<int8_t> ypm(n);
-    for (int i = 0; i < n; i++) ypm[i] = y01[i] ? 1 : -1;
-    L2_ALLOC(b.y, (size_t)n);
-    PSK_HIP(ctx, hipMemcpyAsync(b.y, ypm.data(), (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    logreg_l2_newton_kernel<<<n_fits, L2_THREADS, 0, ctx->stream>>>(
-        (const float *)b.x, (const float *)b.xt, (const int8_t *)b.y, (const int32_t *)b.fold, n, p,
-        (const double *)b.param, (const int32_t *)b.ffold, tol, max_iter, penalise_intercept ? 1 : 0, (double *)b.coef,
-        (double *)b.icpt, (int32_t *)b.iters, (double *)b.work);
-    return l2_download(ctx, b, p, n_fits, coef_out, icpt_out, iters_out);
+    const std::vector<float> XT = transpose_f32(X, n, p, false);
+    const std::vector<int8_t> ypm = labels_pm1(y01, n);
+    FitIO io;
+    FitArr<float> x, xt;
+    FitArr<double> work;
+    FitArr<int8_t> d_y;
+    PSK_TRY(io.upload(ctx, a));
+    PSK_HIP(ctx, x.upload(X, (size_t)n * p, ctx->stream));
+    PSK_HIP(ctx, xt.upload(XT, ctx->stream));
+    PSK_HIP(ctx, work.alloc((size_t)n_fits * (5 * (size_t)p + 4 * (size_t)n)));
+    PSK_HIP(ctx, d_y.upload(ypm, ctx->stream));
+    logreg_l2_newton_kernel<<<n_fits, L2_THREADS, 0, ctx->stream>>>(x, xt, d_y, io.fold, n, p, io.fit_param, io.fit_fold, tol, max_iter,
+                                                                    penalise_intercept ? 1 : 0, io.coef, io.icpt, io.iters, work);
+    return io.download(ctx, a);
 }

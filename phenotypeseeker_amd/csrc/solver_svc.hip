@@ -24,6 +24,7 @@
 
 #include "dev_utils.h"
 #include "psk_internal.h"
+#include "solver_host.h"
 
 namespace {
 
@@ -312,30 +313,22 @@ __global__ __launch_bounds__(SVC_THREADS) void svc_smo_kernel(
     }
 }
 
-struct SvcBufs {
-    void *x = nullptr, *D = nullptr, *diag = nullptr, *y = nullptr, *fold = nullptr, *C = nullptr, *gamma = nullptr,
-         *ffold = nullptr, *dual = nullptr, *rho = nullptr, *dec = nullptr, *iters = nullptr;
-    ~SvcBufs()
-    {
-        void *ps[] = {x, D, diag, y, fold, C, gamma, ffold, dual, rho, dec, iters};
-        for (void *q : ps) if (q) (void)hipFree(q);
-    }
+// what every SMO launch reads and writes, beside its kernel matrix
+struct SvcArrs {
+    FitArr<double> diag, C, gamma, dual, rho, dec;
+    FitArr<int32_t> y, fold, fit_fold, iters;
 };
 
-#define SVC_ALLOC(ptr, bytes) PSK_HIP(ctx, hipMalloc(&(ptr), (bytes) ? (bytes) : 8))
-
-template <typename T, int KERN>
-int svc_launch_smo(psk_ctx *ctx, SvcBufs &b, int n, int n_fits, double tol, int max_iter)
+template <typename T>
+int svc_launch_smo(psk_ctx *ctx, const T *D, const SvcArrs &b, int n, int n_fits, int kernel, double tol, int max_iter)
 {
     const int l_cap = (n + 7) & ~7;
     const size_t lds = SVC_RED_BYTES + (size_t)l_cap * (3 * 8 + 4 + 4 + 1);
-    auto kern = svc_smo_kernel<T, KERN>;
+    auto kern = kernel == 0 ? svc_smo_kernel<T, 0> : svc_smo_kernel<T, 1>;
     if (lds > 64 * 1024)
         PSK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    kern<<<n_fits, SVC_THREADS, lds, ctx->stream>>>((const T *)b.D, (const double *)b.diag, (const int32_t *)b.y,
-                                                    (const int32_t *)b.fold, n, l_cap, (const double *)b.C,
-                                                    (const double *)b.gamma, (const int32_t *)b.ffold, tol, max_iter,
-                                                    (double *)b.dual, (double *)b.rho, (double *)b.dec, (int32_t *)b.iters);
+    kern<<<n_fits, SVC_THREADS, lds, ctx->stream>>>(D, b.diag, b.y, b.fold, n, l_cap, b.C, b.gamma, b.fit_fold, tol, max_iter, b.dual,
+                                                    b.rho, b.dec, b.iters);
     PSK_HIP(ctx, hipGetLastError());
     return PSK_OK;
 }
@@ -365,64 +358,52 @@ extern "C" int psk_svc_fit(psk_ctx *ctx, const float *X, const int32_t *y01, int
             if (fold[i] != fit_fold[f]) { if (y01[i]) c1++; else c0++; }
         if (!c0 || !c1) return psk_fail(ctx, PSK_EINVAL, "fit %d trains on one class only (%d of class 0, %d of class 1)", f, c0, c1);
     }
-    bool binary = true;
-    for (size_t t = 0; t < (size_t)n * p && binary; t++) binary = X[t] == 0.0f || X[t] == 1.0f;
+    const bool binary = design_is_binary(X, (size_t)n * p);
 
     PSK_HIP(ctx, hipSetDevice(ctx->device));
-    SvcBufs b;
+    SvcArrs b;
+    FitArr<uint64_t> xbits;
+    FitArr<float> x, Df;   // the kernel matrix of a 0/1 design holds counts: exact in f32
+    FitArr<double> Dd;
     const dim3 tiles(div_up(n, SVC_TILE), div_up(n, SVC_TILE));
-    SVC_ALLOC(b.diag, (size_t)n * 8);
+    PSK_HIP(ctx, b.diag.alloc(n));
     if (binary) {
         const int W = (p + 63) / 64;
         std::vector<uint64_t> bits((size_t)n * W, 0);
         for (int i = 0; i < n; i++)
             for (int j = 0; j < p; j++)
                 if (X[(size_t)i * p + j] != 0.0f) bits[(size_t)i * W + (j >> 6)] |= 1ull << (j & 63);
-        SVC_ALLOC(b.x, bits.size() * 8);
-        SVC_ALLOC(b.D, (size_t)n * n * 4);
-        PSK_HIP(ctx, hipMemcpyAsync(b.x, bits.data(), bits.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+        PSK_HIP(ctx, xbits.upload(bits, ctx->stream));
+        PSK_HIP(ctx, Df.alloc((size_t)n * n));
         PSK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // `bits` leaves scope
-        svc_gram_bits_kernel<<<tiles, SVC_TILE * SVC_TILE, 0, ctx->stream>>>((const uint64_t *)b.x, n, W, (float *)b.D);
-        svc_diag_kernel<float><<<div_up(n, 256), 256, 0, ctx->stream>>>((const float *)b.D, n, (double *)b.diag);
+        svc_gram_bits_kernel<<<tiles, SVC_TILE * SVC_TILE, 0, ctx->stream>>>(xbits, n, W, Df);
+        svc_diag_kernel<float><<<div_up(n, 256), 256, 0, ctx->stream>>>(Df, n, b.diag);
     } else {
-        SVC_ALLOC(b.x, (size_t)n * p * 4);
-        SVC_ALLOC(b.D, (size_t)n * n * 8);
-        PSK_HIP(ctx, hipMemcpyAsync(b.x, X, (size_t)n * p * 4, hipMemcpyHostToDevice, ctx->stream));
-        svc_gram_dense_kernel<<<tiles, SVC_TILE * SVC_TILE, 0, ctx->stream>>>((const float *)b.x, n, p, (double *)b.D);
-        svc_diag_kernel<double><<<div_up(n, 256), 256, 0, ctx->stream>>>((const double *)b.D, n, (double *)b.diag);
+        PSK_HIP(ctx, x.upload(X, (size_t)n * p, ctx->stream));
+        PSK_HIP(ctx, Dd.alloc((size_t)n * n));
+        svc_gram_dense_kernel<<<tiles, SVC_TILE * SVC_TILE, 0, ctx->stream>>>(x, n, p, Dd);
+        svc_diag_kernel<double><<<div_up(n, 256), 256, 0, ctx->stream>>>(Dd, n, b.diag);
     }
     PSK_HIP(ctx, hipGetLastError());
 
     std::vector<double> gam(n_fits, 0.0);
     if (kernel == 1) memcpy(gam.data(), fit_gamma, (size_t)n_fits * 8);
-    SVC_ALLOC(b.y, (size_t)n * 4);
-    SVC_ALLOC(b.fold, (size_t)n * 4);
-    SVC_ALLOC(b.C, (size_t)n_fits * 8);
-    SVC_ALLOC(b.gamma, (size_t)n_fits * 8);
-    SVC_ALLOC(b.ffold, (size_t)n_fits * 4);
-    SVC_ALLOC(b.dual, (size_t)n_fits * n * 8);
-    SVC_ALLOC(b.rho, (size_t)n_fits * 8);
-    SVC_ALLOC(b.dec, (size_t)n_fits * n * 8);
-    SVC_ALLOC(b.iters, (size_t)n_fits * 4);
-    PSK_HIP(ctx, hipMemcpyAsync(b.y, y01, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-    PSK_HIP(ctx, hipMemcpyAsync(b.fold, fold, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-    PSK_HIP(ctx, hipMemcpyAsync(b.C, fit_C, (size_t)n_fits * 8, hipMemcpyHostToDevice, ctx->stream));
-    PSK_HIP(ctx, hipMemcpyAsync(b.gamma, gam.data(), (size_t)n_fits * 8, hipMemcpyHostToDevice, ctx->stream));
-    PSK_HIP(ctx, hipMemcpyAsync(b.ffold, fit_fold, (size_t)n_fits * 4, hipMemcpyHostToDevice, ctx->stream));
-    PSK_HIP(ctx, hipMemsetAsync(b.dual, 0, (size_t)n_fits * n * 8, ctx->stream));   // samples a fit did not train on
-    if (binary) {
-        if (kernel == 0) PSK_TRY((svc_launch_smo<float, 0>(ctx, b, n, n_fits, tol, max_iter)));
-        else PSK_TRY((svc_launch_smo<float, 1>(ctx, b, n, n_fits, tol, max_iter)));
-    } else {
-        if (kernel == 0) PSK_TRY((svc_launch_smo<double, 0>(ctx, b, n, n_fits, tol, max_iter)));
-        else PSK_TRY((svc_launch_smo<double, 1>(ctx, b, n, n_fits, tol, max_iter)));
-    }
-    std::vector<int32_t> it(n_fits);
-    PSK_HIP(ctx, hipMemcpyAsync(dual_out, b.dual, (size_t)n_fits * n * 8, hipMemcpyDeviceToHost, ctx->stream));
-    PSK_HIP(ctx, hipMemcpyAsync(rho_out, b.rho, (size_t)n_fits * 8, hipMemcpyDeviceToHost, ctx->stream));
-    PSK_HIP(ctx, hipMemcpyAsync(dec_out, b.dec, (size_t)n_fits * n * 8, hipMemcpyDeviceToHost, ctx->stream));
-    PSK_HIP(ctx, hipMemcpyAsync(it.data(), b.iters, (size_t)n_fits * 4, hipMemcpyDeviceToHost, ctx->stream));
-    PSK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (iters_out) memcpy(iters_out, it.data(), (size_t)n_fits * 4);
+    PSK_HIP(ctx, b.y.upload(y01, n, ctx->stream));
+    PSK_HIP(ctx, b.fold.upload(fold, n, ctx->stream));
+    PSK_HIP(ctx, b.C.upload(fit_C, n_fits, ctx->stream));
+    PSK_HIP(ctx, b.gamma.upload(gam, ctx->stream));
+    PSK_HIP(ctx, b.fit_fold.upload(fit_fold, n_fits, ctx->stream));
+    PSK_HIP(ctx, b.dual.alloc((size_t)n_fits * n));
+    PSK_HIP(ctx, b.rho.alloc(n_fits));
+    PSK_HIP(ctx, b.dec.alloc((size_t)n_fits * n));
+    PSK_HIP(ctx, b.iters.alloc(n_fits));
+    PSK_HIP(ctx, b.dual.zero(ctx->stream));   // samples a fit did not train on
+    if (binary) PSK_TRY(svc_launch_smo<float>(ctx, Df, b, n, n_fits, kernel, tol, max_iter));
+    else PSK_TRY(svc_launch_smo<double>(ctx, Dd, b, n, n_fits, kernel, tol, max_iter));
+    PSK_HIP(ctx, b.dual.download(dual_out, (size_t)n_fits * n, ctx->stream));
+    PSK_HIP(ctx, b.rho.download(rho_out, n_fits, ctx->stream));
+    PSK_HIP(ctx, b.dec.download(dec_out, (size_t)n_fits * n, ctx->stream));
+    if (iters_out) PSK_HIP(ctx, b.iters.download(iters_out, n_fits, ctx->stream));
+    PSK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (`gam` must outlive its copy)
     return PSK_OK;
 }

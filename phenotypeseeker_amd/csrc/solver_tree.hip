@@ -28,6 +28,7 @@
 
 #include "dev_utils.h"
 #include "psk_internal.h"
+#include "solver_host.h"
 
 namespace {
 
@@ -238,19 +239,6 @@ __global__ __launch_bounds__(TREE_THREADS) void tree_fit_kernel(
                       stack, path_feat, red_v, red_i, red_c);
 }
 
-struct TreeBufs {
-    void *x = nullptr, *bits = nullptr, *ymask = nullptr, *bad = nullptr, *y = nullptr, *fold = nullptr, *depth = nullptr,
-         *crit = nullptr, *ffold = nullptr, *off = nullptr, *count = nullptr, *dout = nullptr, *nodes = nullptr, *imp = nullptr,
-         *leaf = nullptr, *frac = nullptr;
-    ~TreeBufs()
-    {
-        void *ps[] = {x, bits, ymask, bad, y, fold, depth, crit, ffold, off, count, dout, nodes, imp, leaf, frac};
-        for (void *q : ps) if (q) (void)hipFree(q);
-    }
-};
-
-#define TREE_ALLOC(ptr, bytes) PSK_HIP(ctx, hipMalloc(&(ptr), (bytes) ? (bytes) : 8))
-
 }  // namespace
 
 extern "C" int psk_tree_fit(psk_ctx *ctx, const float *X, const int32_t *y01, int n, int p, const int32_t *fold,
@@ -276,21 +264,21 @@ extern "C" int psk_tree_fit(psk_ctx *ctx, const float *X, const int32_t *y01, in
     }
 
     PSK_HIP(ctx, hipSetDevice(ctx->device));
-    TreeBufs b;
     const int W = (n + 63) / 64;
-    TREE_ALLOC(b.x, (size_t)n * p * 4);
-    TREE_ALLOC(b.y, (size_t)n * 4);
-    TREE_ALLOC(b.bits, (size_t)p * W * 8);
-    TREE_ALLOC(b.ymask, (size_t)W * 8);
-    TREE_ALLOC(b.bad, 4);
-    PSK_HIP(ctx, hipMemcpyAsync(b.x, X, (size_t)n * p * 4, hipMemcpyHostToDevice, ctx->stream));
-    PSK_HIP(ctx, hipMemcpyAsync(b.y, y01, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-    PSK_HIP(ctx, hipMemsetAsync(b.bad, 0, 4, ctx->stream));
-    tree_pack_kernel<<<dim3(div_up(p, 256), W), 256, 0, ctx->stream>>>((const float *)b.x, (const int32_t *)b.y, n, p, W,
-                                                                       (uint64_t *)b.bits, (uint64_t *)b.ymask, (int32_t *)b.bad);
+    FitArr<float> x;
+    FitArr<uint64_t> bits, ymask;
+    FitArr<int32_t> bad_flag, y, d_fold, depth, crit, d_fit_fold, d_off, count, dout, d_nodes, leaf;
+    FitArr<double> d_imp, frac;
+    PSK_HIP(ctx, x.upload(X, (size_t)n * p, ctx->stream));
+    PSK_HIP(ctx, y.upload(y01, n, ctx->stream));
+    PSK_HIP(ctx, bits.alloc((size_t)p * W));
+    PSK_HIP(ctx, ymask.alloc(W));
+    PSK_HIP(ctx, bad_flag.alloc(1));
+    PSK_HIP(ctx, bad_flag.zero(ctx->stream));
+    tree_pack_kernel<<<dim3(div_up(p, 256), W), 256, 0, ctx->stream>>>(x, y, n, p, W, bits, ymask, bad_flag);
     PSK_HIP(ctx, hipGetLastError());
     int32_t bad = 0;
-    PSK_HIP(ctx, hipMemcpyAsync(&bad, b.bad, 4, hipMemcpyDeviceToHost, ctx->stream));
+    PSK_HIP(ctx, bad_flag.download(&bad, 1, ctx->stream));
     PSK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (bad)
         return psk_fail(ctx, PSK_EINVAL, "psk_tree_fit takes a 0/1 design (k-mer presence): the matrix holds another value");
@@ -300,35 +288,28 @@ extern "C" int psk_tree_fit(psk_ctx *ctx, const float *X, const int32_t *y01, in
     std::vector<int32_t> off((size_t)n_fits + 1, 0);
     for (int f = 0; f < n_fits; f++) off[f + 1] = off[f] + (2 << fit_max_depth[f]) - 1;
     const size_t total = (size_t)off[n_fits];
-    TREE_ALLOC(b.fold, (size_t)n * 4);
-    TREE_ALLOC(b.depth, (size_t)n_fits * 4);
-    TREE_ALLOC(b.crit, (size_t)n_fits * 4);
-    TREE_ALLOC(b.ffold, (size_t)n_fits * 4);
-    TREE_ALLOC(b.off, (size_t)n_fits * 4);
-    TREE_ALLOC(b.count, (size_t)n_fits * 4);
-    TREE_ALLOC(b.dout, (size_t)n_fits * 4);
-    TREE_ALLOC(b.nodes, total * TREE_NODE_FIELDS * 4);
-    TREE_ALLOC(b.imp, total * 8);
-    TREE_ALLOC(b.leaf, (size_t)n_fits * n * 4);
-    TREE_ALLOC(b.frac, (size_t)n_fits * n * 8);
-    PSK_HIP(ctx, hipMemcpyAsync(b.fold, fold, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-    PSK_HIP(ctx, hipMemcpyAsync(b.depth, fit_max_depth, (size_t)n_fits * 4, hipMemcpyHostToDevice, ctx->stream));
-    PSK_HIP(ctx, hipMemcpyAsync(b.crit, fit_criterion, (size_t)n_fits * 4, hipMemcpyHostToDevice, ctx->stream));
-    PSK_HIP(ctx, hipMemcpyAsync(b.ffold, fit_fold, (size_t)n_fits * 4, hipMemcpyHostToDevice, ctx->stream));
-    PSK_HIP(ctx, hipMemcpyAsync(b.off, off.data(), (size_t)n_fits * 4, hipMemcpyHostToDevice, ctx->stream));
-    tree_fit_kernel<<<n_fits, TREE_THREADS, 0, ctx->stream>>>(
-        (const uint64_t *)b.bits, (const uint64_t *)b.ymask, (const int32_t *)b.fold, n, p, W, (const int32_t *)b.depth,
-        (const int32_t *)b.crit, (const int32_t *)b.ffold, (int32_t *)b.count, (int32_t *)b.dout, (int32_t *)b.nodes,
-        (double *)b.imp, (int32_t *)b.leaf, (double *)b.frac, (const int32_t *)b.off);
+    PSK_HIP(ctx, d_fold.upload(fold, n, ctx->stream));
+    PSK_HIP(ctx, depth.upload(fit_max_depth, n_fits, ctx->stream));
+    PSK_HIP(ctx, crit.upload(fit_criterion, n_fits, ctx->stream));
+    PSK_HIP(ctx, d_fit_fold.upload(fit_fold, n_fits, ctx->stream));
+    PSK_HIP(ctx, d_off.upload(off.data(), n_fits, ctx->stream));
+    PSK_HIP(ctx, count.alloc(n_fits));
+    PSK_HIP(ctx, dout.alloc(n_fits));
+    PSK_HIP(ctx, d_nodes.alloc(total * TREE_NODE_FIELDS));
+    PSK_HIP(ctx, d_imp.alloc(total));
+    PSK_HIP(ctx, leaf.alloc((size_t)n_fits * n));
+    PSK_HIP(ctx, frac.alloc((size_t)n_fits * n));
+    tree_fit_kernel<<<n_fits, TREE_THREADS, 0, ctx->stream>>>(bits, ymask, d_fold, n, p, W, depth, crit, d_fit_fold, count, dout, d_nodes,
+                                                              d_imp, leaf, frac, d_off);
     PSK_HIP(ctx, hipGetLastError());
-    PSK_HIP(ctx, hipMemcpyAsync(node_count_out, b.count, (size_t)n_fits * 4, hipMemcpyDeviceToHost, ctx->stream));
-    PSK_HIP(ctx, hipMemcpyAsync(max_depth_out, b.dout, (size_t)n_fits * 4, hipMemcpyDeviceToHost, ctx->stream));
     std::vector<int32_t> nodes(total * TREE_NODE_FIELDS);
     std::vector<double> imp(total);
-    PSK_HIP(ctx, hipMemcpyAsync(nodes.data(), b.nodes, total * TREE_NODE_FIELDS * 4, hipMemcpyDeviceToHost, ctx->stream));
-    PSK_HIP(ctx, hipMemcpyAsync(imp.data(), b.imp, total * 8, hipMemcpyDeviceToHost, ctx->stream));
-    PSK_HIP(ctx, hipMemcpyAsync(leaf_out, b.leaf, (size_t)n_fits * n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    PSK_HIP(ctx, hipMemcpyAsync(frac_out, b.frac, (size_t)n_fits * n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    PSK_HIP(ctx, count.download(node_count_out, n_fits, ctx->stream));
+    PSK_HIP(ctx, dout.download(max_depth_out, n_fits, ctx->stream));
+    PSK_HIP(ctx, d_nodes.download(nodes.data(), nodes.size(), ctx->stream));
+    PSK_HIP(ctx, d_imp.download(imp.data(), imp.size(), ctx->stream));
+    PSK_HIP(ctx, leaf.download(leaf_out, (size_t)n_fits * n, ctx->stream));
+    PSK_HIP(ctx, frac.download(frac_out, (size_t)n_fits * n, ctx->stream));
     PSK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (int f = 0; f < n_fits; f++) {
         const size_t k = (size_t)node_count_out[f];

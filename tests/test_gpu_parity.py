@@ -982,13 +982,13 @@ def test_lasso_grid_search_on_the_large_design_matches_sklearn(ctx):
     assert gs.best_params_["alpha"] == pytest.approx(float(z["gs_best_alpha"]))
 
 
-@pytest.mark.parametrize("n", [90, 1000, 2500])
-def test_lasso_bit_packed_kernel_equals_the_float_kernel(ctx, n, monkeypatch):
+@pytest.mark.parametrize("n, p", [(90, 120), (1000, 120), (2500, 120)], ids=["90", "1000", "2500"])
+def test_lasso_bit_packed_kernel_equals_the_float_kernel(ctx, n, p, monkeypatch):
     """0/1 designs take the four-wave bit-packed Lasso (masked sums over the samples that have the k-mer, the residual
     as r' + c); the float kernel (PSK_NO_LASSO_BITS, also what --real_counts uses) is the same cyclic descent: run to
-    convergence the two agree on every fit of a (value, fold) grid, folds and NA-free rows included."""
+    convergence the two agree on every fit of a (value, fold) grid, folds and NA-free rows included.  Up to 1,024 columns
+    the first call takes the covariance form (a case past that size rule, such as (130, 1030), would take the bit-packed kernel)."""
     rng = np.random.default_rng(n)
-    p = 120
     base = rng.random((n, 10)) < 0.4
     X = (base[:, rng.integers(0, 10, p)] ^ (rng.random((n, p)) < 0.1)).astype(np.float32)
     X[:, 7] = 1.0                      # a constant column: zero norm, skipped
