@@ -1,5 +1,5 @@
 // Record framing on the GPU (the host half of a1's tokeniser, DESIGN.md "Tokeniser contract"): raw FASTA / FASTQ
-// file bytes in, the clean stream of kmer_count.hip out (bases kept, window breaks as '\n', everything else
+// file bytes in, the clean stream of frame_host.hip out (bases kept, window breaks as '\n', everything else
 // dropped) -- so that the host only moves file bytes into pinned memory.  Replaces the sequential byte state machine
 // frame_sequence_counting() for the two shapes real inputs have; anything else stays with the host machine.
 //
@@ -347,7 +347,7 @@ __global__ __launch_bounds__(FR_THREADS) void fq_pass_kernel(const uint8_t *__re
 
 // ---- FASTQ, any line structure (r06) -----------------------------------------------------------------------------------------
 // Line kinds.  SEQ0: a sequence line read from its first byte (the line behind a header, or behind a swallowed empty line); SEQ1: a
-// continued sequence line -- the machine consumes the byte behind a sequence line's '\n' (kmer_count.hip: frame_sequence_counting,
+// continued sequence line -- the machine consumes the byte behind a sequence line's '\n' (frame_host.hip: frame_sequence_counting,
 // "the byte after a sequence newline is consumed"), so its first byte emits nothing; SEQE: that byte was the '\n' of an empty line;
 // SKIP: a line behind the quality line that does not start with '@' (further quality lines); SKIPE: an empty such line -- its '\n' is
 // taken for the line's first byte, so the line BEHIND it is skipped whatever it starts with.
@@ -638,7 +638,7 @@ extern "C" int64_t psk_frame_sequence_gpu(psk_ctx *ctx, const uint8_t *bytes, si
     if (rc == PSK_OK && hipMemcpyAsync(raw.p, bytes + st, rl, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) fail(PSK_EHIP, "upload failed");
     if (rc == PSK_OK) rc = frame_gpu_enqueue(ctx, ctx->stream, format, raw.as<uint8_t>(), rl, clean.as<uint8_t>(), scratch.p, res);
     if (rc == PSK_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) fail(PSK_EHIP, "framing kernels failed");
-    if (rc == PSK_OK && format == 2 && res[1]) {   // not four-line FASTQ: the general route (what kmer_count.hip does with such a sample)
+    if (rc == PSK_OK && format == 2 && res[1]) {   // not four-line FASTQ: the general route (what count_batch.hip does with such a sample)
         rc = frame_gpu_enqueue(ctx, ctx->stream, 3, raw.as<uint8_t>(), rl, clean.as<uint8_t>(), scratch.p, res);
         if (rc == PSK_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) fail(PSK_EHIP, "framing kernels failed");
     }

@@ -9,6 +9,28 @@ namespace {
 
 constexpr int KW_SEG = 32;   // window ends per thread
 
+// ---- the byte-by-byte roll (count_chain.hip extract_kernel: every k; count_dict.hip) -----------------------------------
+constexpr int EX_THREADS = 256;
+constexpr int EX_SEG = 32;   // window-end positions per thread
+constexpr int EX_HALO = 32;  // bytes before the segment that are rolled first (k - 1 <= 31)
+
+struct Roll {
+    uint64_t fw, rc;
+    int run;
+};
+
+__device__ __forceinline__ void roll_byte(Roll &r, uint32_t c, uint64_t mask, int rcshift, int k)
+{
+    if (c == '\n') {
+        r.run = 0;
+    } else {
+        const uint64_t code = ((c >> 1) ^ (c >> 2)) & 3u;  // A/a 0, C/c 1, G/g 2, T/t/U/u 3
+        r.fw = ((r.fw << 2) | code) & mask;
+        r.rc = (r.rc >> 2) | ((3ull - code) << rcshift);
+        r.run = (r.run < k) ? r.run + 1 : k;
+    }
+}
+
 // ---- the 32 window ends of a thread, without a byte-by-byte roll ------------------------------------------------
 // A thread owns 32 consecutive bytes of the clean stream and reads the 16 before them (K - 1 <= 15).  The 48 bytes
 // become three bit streams, four bytes per multiply: F (2 bits per base, earlier bases more significant), R (the

@@ -5,7 +5,7 @@
 // upper-case ASCII string with MurmurHash3_x64_128 (seed 42); the hash is the first 8 output bytes
 // (first 4 when 4^k <= 2^32); the sketch is the `sketch_size` smallest DISTINCT hashes, ascending.
 //
-//   extract_kernel (kmer_count.hip)  canonical 2-bit words of every window (same tokeniser as a1)
+//   extract_kernel (count_chain.hip)  canonical 2-bit words of every window (same tokeniser as a1)
 //   kmer_hash_kernel                 word -> ASCII -> MurmurHash3 h1, in place
 //   dev_radix_sort_u64 + run heads   ascending distinct hashes; the first `sketch_size` go to the host
 #include "dev_utils.h"
@@ -165,8 +165,6 @@ __global__ void take_first_heads_kernel(const uint64_t *__restrict__ keys, uint6
 
 }  // namespace
 
-int upload_clean_stream(psk_ctx *ctx, const uint8_t *bytes, size_t len, uint64_t *clean_len);  // kmer_count.hip
-
 // sketch of a clean stream that already sits in device memory (stream-ordered after whatever produced it)
 int sketch_from_device(psk_ctx *ctx, const uint8_t *d_clean, uint64_t clean_len, int k, int sketch_size, uint32_t seed,
                        uint64_t *hashes_out, uint64_t *n_out)
@@ -321,7 +319,7 @@ extern "C" int psk_minhash_sketch(psk_ctx *ctx, const uint8_t *bytes, size_t len
     if (!hashes_out || !n_out || (!bytes && len)) return psk_fail(ctx, PSK_EINVAL, "null buffer");
     PSK_HIP(ctx, hipSetDevice(ctx->device));
     uint64_t clean_len = 0;
-    PSK_TRY(upload_clean_stream(ctx, bytes, len, &clean_len));
+    PSK_TRY(upload_clean(ctx, bytes, len, &clean_len));
     return sketch_from_device(ctx, ctx->raw.as<uint8_t>(), clean_len, k, sketch_size, seed, hashes_out, n_out);
 }
 

@@ -7,6 +7,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <chrono>
+#include <functional>
 #include <initializer_list>
 #include <string>
 #include <thread>
@@ -207,7 +209,7 @@ struct psk_ctx {
 int psk_fail(psk_ctx *ctx, int code, const char *fmt, ...);
 std::string psk_error_text(psk_ctx *ctx);                        // (copies under the lock psk_fail writes under)
 void psk_set_error_text(psk_ctx *ctx, const std::string &text);
-void psk_forget_lane_slices(psk_ctx *ctx);   // kmer_count.hip
+void psk_forget_lane_slices(psk_ctx *ctx);   // count_chain.hip
 
 #define PSK_HIP(ctx, call)                                                                            \
     do {                                                                                              \
@@ -318,10 +320,85 @@ int dev_radix_sort_kv(psk_ctx *ctx, uint64_t *a, uint64_t *b, uint32_t *va, uint
                       int bit_hi, uint64_t **sorted_out, uint32_t **sorted_vals_out, const uint32_t *n_dev = nullptr);
 
 // ---- stages --------------------------------------------------------------------------------------
-int64_t frame_sequence_host(const uint8_t *bytes, size_t len, uint8_t *out, size_t out_cap);
+int64_t frame_sequence_host(const uint8_t *bytes, size_t len, uint8_t *out, size_t out_cap);   // frame_host.hip
+// frames `bytes` into `stage` (host, thread-safe) and pads it for the extract kernel; k > 0: *n_windows = its k-base windows
+int frame_into(uint8_t *stage, size_t stage_cap, const uint8_t *bytes, size_t len, uint64_t *clean_len, uint64_t *padded_len,
+               int k = 0, uint64_t *n_windows = nullptr);   // frame_host.hip
+int frame_gpu_enqueue(psk_ctx *ctx, hipStream_t stream, int format, const uint8_t *d_raw, uint64_t raw_len, uint8_t *d_clean,
+                      void *scratch, uint64_t *host_out);   // frame_gpu.hip
+size_t frame_gpu_scratch_bytes(uint64_t raw_len);           // frame_gpu.hip
+int frame_probe(const uint8_t *bytes, size_t len, size_t *start, size_t *end);                   // frame_gpu.hip
+int frame_probe_known_end(const uint8_t *bytes, size_t nul_at, size_t *start, size_t *end);     // frame_gpu.hip
+int sketch_enqueue(psk_ctx *ctx, CountLane &L, const uint8_t *d_clean, uint64_t clean_len, int k, int sketch_size, uint32_t seed);   // minhash.hip
+int sketch_collect(psk_ctx *ctx, CountLane &L, const uint8_t *d_clean, uint64_t clean_len, int k, int sketch_size,
+                   uint32_t seed, uint64_t *hashes_out, uint64_t *n_out);   // minhash.hip
+int sketch_from_device(psk_ctx *ctx, const uint8_t *d_clean, uint64_t clean_len, int k, int sketch_size, uint32_t seed,
+                       uint64_t *hashes_out, uint64_t *n_out);   // minhash.hip
 // clean stream (device) -> canonical words inside [lo, hi) appended to out; *n_out (device u32) counts them
 int launch_extract(psk_ctx *ctx, const uint8_t *clean, uint64_t len, int k, uint64_t lo, uint64_t hi, uint64_t *out,
-                   uint32_t *n_out);
+                   uint32_t *n_out);   // count_chain.hip
+
+// ---- the lanes and the three stages of a sample's chain (count_chain.hip) ---------------------------------------------------
+// {clean length, irregular flag} of a sample framed on the GPU land here (pinned, behind the lane's counters)
+static inline uint64_t *lane_frame_result(CountLane &L) { return reinterpret_cast<uint64_t *>(L.pinned_cnt + 8); }
+size_t lane_set_bytes(psk_ctx *ctx, size_t max_len, bool gpu_framing);   // bytes of ONE buffer set of a grouped batch
+int carve_lanes(psk_ctx *ctx, int n_lanes, size_t max_len, bool gpu_framing);
+int chain_upload(psk_ctx *ctx, CountLane &L, const uint8_t *src, uint64_t bytes, int format, bool src_on_device = false);
+int chain_compute(psk_ctx *ctx, CountLane &L, int sample_idx, uint64_t clean_len, uint64_t n, bool n_exact);
+int chain_finalize(psk_ctx *ctx, CountLane &L);
+int ensure_pinned(psk_ctx *ctx, void **buf, size_t *cap, size_t need);
+// frame into the context's single pinned buffer and upload into ctx->raw (dictionary counting, MinHash)
+int upload_clean(psk_ctx *ctx, const uint8_t *bytes, size_t len, uint64_t *clean_len);
+
+// ---- one counting call (count_batch.hip; count_gz.hip cuts it into runs when samples are .gz images) --------------------------
+// sample i with dev != nullptr is a .gz input whose text is already on the device
+struct GzSample {
+    const uint8_t *dev = nullptr;
+    int fmt = 0;                 // as frame_probe reports
+    uint64_t roff = 0, rlen = 0; // its records
+};
+// `consumer` != nullptr (prediction: count_dict.hip): the framed clean stream of sample i on buffer set L goes to it instead
+// of the counting chain -- consumer(L, i, clean_len) queues its kernel on ctx->stream -- and no list is made; k_window is
+// then the k of the windows (psk_begin need not have been called)
+typedef std::function<int(CountLane &, int, uint64_t)> StreamConsumer;
+struct CountRequest {
+    int first_sample_idx = 0, n = 0;
+    const uint8_t *const *bytes = nullptr;   // file images, or
+    const char *const *paths = nullptr;      // ... (bytes or bytes[i] null) files of lens[i] bytes, read by the framing threads
+    const size_t *lens = nullptr;
+    const GzSample *gzs = nullptr;           // may be null
+    uint64_t *n_unique = nullptr, *n_total = nullptr;
+    int n_threads = 1;
+    int sketch_k = 0, sketch_size = 0;       // sketch_k > 0: the MinHash sketch of every sample as well
+    uint32_t sketch_seed = 0;
+    uint64_t *hashes_out = nullptr, *n_hashes_out = nullptr;
+    int k_window = 0;
+    const StreamConsumer *consumer = nullptr;
+    // samples [lo, lo + cnt) of this request as a request of their own
+    CountRequest slice(int lo, int cnt) const
+    {
+        CountRequest s = *this;
+        s.first_sample_idx += lo; s.n = cnt;
+        if (bytes) s.bytes += lo;
+        if (paths) s.paths += lo;
+        if (lens) s.lens += lo;
+        if (gzs) s.gzs += lo;
+        if (n_unique) s.n_unique += lo;
+        if (n_total) s.n_total += lo;
+        if (hashes_out) s.hashes_out += (size_t)lo * sketch_size;
+        if (n_hashes_out) s.n_hashes_out += lo;
+        return s;
+    }
+};
+int count_batch_core(psk_ctx *ctx, const CountRequest &q);   // count_batch.hip: one run, no .gz image among its inputs
+int count_batch_impl(psk_ctx *ctx, const CountRequest &q);   // count_gz.hip: the call as the entry points hand it over
+// exactly len bytes of the file at `offset` (negative: from its end) into dst; 0 on success
+int read_exact(const char *path, long offset, size_t len, void *dst);   // count_gz.hip
+
+struct Stopwatch {
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    double s() const { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
+};
 
 // ---- dense list form (dense_count.hip, presence_dense.hip) ---------------------------------------------------
 constexpr int DC_VB = 15;                  // word values per bucket: 2^15

@@ -1785,3 +1785,56 @@ def test_counting_from_files_equals_counting_from_memory(ctx, tmp_path):
     assert ctx.count_kmers_files(0, paths[:3], 2)[0] == nu[:3]
     with pytest.raises(PskError, match="reading or framing"):
         ctx.count_kmers_files(0, [paths[0], os.path.join(tmp_path, "missing.fa")], 2)
+
+
+@pytest.fixture(scope="module")
+def failing_batch(ctx, tmp_path_factory):
+    """k -> (the paths of ten FASTA files, path 4 replaced by one that does not exist; the nine good paths; their lists from nine
+    single count_kmers calls).  Made once per k, before a test sets a knob, and not changed."""
+    from phenotypeseeker_amd.synth import GenomeSet
+    made = {}
+
+    def get(k):
+        if k not in made:
+            gs = GenomeSet(10, 150_000 if k >= 14 else 60_000, seed=300 + k)
+            d = tmp_path_factory.mktemp("failing_batch_k%d" % k)
+            paths, datas = [], []
+            for i in range(10):
+                name, fa = gs.sample(i)
+                paths.append(os.path.join(d, name + ".fa"))
+                with open(paths[-1], "wb") as f:
+                    f.write(fa)
+                datas.append(fa)
+            good = paths[:4] + paths[5:]
+            ctx.begin(k, len(good))
+            ref = []
+            for i, data in enumerate(datas[:4] + datas[5:]):
+                nu, nt = ctx.count_kmers(i, data)
+                ref.append((nu, nt) + ctx.get_list(i, nu))
+            made[k] = (paths[:4] + [os.path.join(d, "missing.fa")] + paths[5:], good, ref)
+        return made[k]
+    return get
+
+
+@pytest.mark.parametrize("k", [13, 16])
+@pytest.mark.parametrize("knobs", [{"PSK_DC_GROUP": "3"}, {"PSK_DC_GROUP": "3", "PSK_HOST_FRAMING": "1"}, {"PSK_DC_GROUP": "1"}],
+                         ids=["groups_of_3", "groups_of_3_host_framing", "one_sample_chains"])
+def test_a_missing_file_in_the_middle_of_a_batch_fails_the_call_and_the_context_counts_on(ctx, failing_batch, monkeypatch, k, knobs):
+    """The ways out of the batch driver in the middle of a call: of ten files, sample 4 (counted from 0, as the message counts)
+    does not exist -- its worker reports it, stage A of that sample fails while the chains of the samples before it are queued or
+    pending (in groups of 3: in the middle of a group's uploads at k = 13; at k = 16 the first sample goes alone, so it is the
+    first of a group), the call raises and the worker threads are stopped and joined.  The same context then counts the nine good
+    files by the same route, and their lists are those of nine single calls: nothing of the failed call is left switched on."""
+    from phenotypeseeker_amd._lib import PskError
+    bad, good, ref = failing_batch(k)
+    for name, value in knobs.items():
+        monkeypatch.setenv(name, value)
+    ctx.begin(k, len(bad))
+    with pytest.raises(PskError, match="reading or framing"):
+        ctx.count_kmers_files(0, bad, 4)
+    ctx.begin(k, len(good))
+    nu, nt = ctx.count_kmers_files(0, good, 4)
+    for i, (rnu, rnt, rw, rf) in enumerate(ref):
+        assert (nu[i], nt[i]) == (rnu, rnt), i
+        w, f = ctx.get_list(i, nu[i])
+        assert np.array_equal(w, rw) and np.array_equal(f, rf), i

@@ -60,7 +60,7 @@ static std::string put(const std::string &dir, const std::string &name, const st
     return p;
 }
 
-static int run(const std::vector<std::string> &paths, const std::vector<size_t> &sizes, int k, int threads, bool expect_gz_error)
+static int run(const std::vector<std::string> &paths, const std::vector<size_t> &sizes, int k, int threads, int expect)
 {
     psk_ctx *ctx = nullptr;
     if (psk_init(0, &ctx) != PSK_OK) return 1;
@@ -72,14 +72,14 @@ static int run(const std::vector<std::string> &paths, const std::vector<size_t> 
     for (int rep = 0; rep < 3; rep++) {
         if (psk_begin(ctx, k, n, 0, 0) != PSK_OK) bad = 1;
         const int rc = psk_count_kmers_files(ctx, 0, n, p.data(), sizes.data(), nu.data(), nt.data(), threads, 0, 0, 0, nullptr, nullptr);
-        if (expect_gz_error ? rc != PSK_EINVAL : rc != PSK_OK) {
+        if (rc != expect) {
             std::fprintf(stderr, "psk_count_kmers_files: rc %d (%s)\n", rc, psk_last_error(ctx));
             bad = 1;
         }
     }
     std::vector<uint64_t> dict = {1, 5, 77, 1000, 4242};
     std::vector<uint32_t> counts((size_t)n * dict.size());
-    if (!expect_gz_error && psk_count_dict_files(ctx, n, p.data(), sizes.data(), k, dict.data(), (uint64_t)dict.size(), counts.data(), threads) != PSK_OK) {
+    if (expect == PSK_OK && psk_count_dict_files(ctx, n, p.data(), sizes.data(), k, dict.data(), (uint64_t)dict.size(), counts.data(), threads) != PSK_OK) {
         std::fprintf(stderr, "psk_count_dict_files: %s\n", psk_last_error(ctx));
         bad = 1;
     }
@@ -109,8 +109,8 @@ int main(int argc, char **argv)
         add("s" + std::to_string(i) + "_wrapped.fastq.gz", gz(fw, 6));
     }
     int bad = 0;
-    std::thread other([&] { bad |= run(paths, sizes, 21, 4, false); });   // a second context on another caller thread
-    bad |= run(paths, sizes, 13, 8, false);
+    std::thread other([&] { bad |= run(paths, sizes, 21, 4, PSK_OK); });   // a second context on another caller thread
+    bad |= run(paths, sizes, 13, 8, PSK_OK);
     other.join();
     // a corrupt .gz among good ones: the error path of the stage threads (first error wins, the others wind down)
     std::string broken = gz(fasta(rng, 50000), 6);
@@ -120,7 +120,28 @@ int main(int argc, char **argv)
     std::vector<size_t> s2(sizes.begin(), sizes.begin() + 12);
     p2.push_back(put(dir, "broken.fasta.gz", broken));
     s2.push_back(broken.size());
-    bad |= run(p2, s2, 13, 8, true);
-    std::printf(bad ? "tsan driver: FAILED\n" : "tsan driver: ok (%zu files, two contexts, three rounds each, error path)\n", paths.size());
+    bad |= run(p2, s2, 13, 8, PSK_EINVAL);
+    // a file that does not exist in the middle of a batch of genomes: the batch driver's ways out (its worker reports the sample,
+    // stage A fails with chains queued or pending, the workers are stopped and joined) in groups of 3 and one by one, dense
+    // (k = 13) and bucketed (k = 16); the same files without it are then counted by the same route
+    std::vector<std::string> good, holed;
+    std::vector<size_t> sg, sh;
+    for (int i = 0; i < 9; i++) {
+        const std::string fa = fasta(rng, 60000 + 100 * i);
+        good.push_back(put(dir, "g" + std::to_string(i) + ".fasta", fa));
+        sg.push_back(fa.size());
+    }
+    holed = good;
+    sh = sg;
+    holed.insert(holed.begin() + 4, dir + "/missing.fasta");
+    sh.insert(sh.begin() + 4, 0);
+    for (const char *group : {"3", "1"})
+        for (int k : {13, 16}) {
+            setenv("PSK_DC_GROUP", group, 1);
+            bad |= run(holed, sh, k, 4, PSK_ERANGE);
+            bad |= run(good, sg, k, 4, PSK_OK);
+        }
+    unsetenv("PSK_DC_GROUP");
+    std::printf(bad ? "tsan driver: FAILED\n" : "tsan driver: ok (%zu files, two contexts, three rounds each, error paths)\n", paths.size());
     return bad;
 }

@@ -3,7 +3,8 @@
 #   every translation unit's host half is compiled with -fsanitize=thread (the device code as usual), linked -- with clang++, not
 #   hipcc, so that no real HIP runtime comes in -- against tools/tsan/hip_stub.cpp, a HIP with no device (kernels do nothing,
 #   "device" memory is host memory), and driven by tools/tsan/driver.cpp: the file-ingest pipeline (reader + upload | inflate |
-#   count stage threads, kmer_count.hip), the framing pool, prediction's counting, two contexts on two threads, the error path.
+#   count stage threads: count_gz.hip, stage_pipeline.h), the framing pool of the batch driver (count_batch.hip), prediction's
+#   counting, two contexts on two threads, the error path.
 # Builds into a scratch directory; the in-tree library is not touched.  usage: tools/tsan_host.sh [scratch-dir]
 set -eu
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
