@@ -357,24 +357,24 @@ __global__ __launch_bounds__(SC_FIN_THREADS) void chi2w_finalize_kernel(const Sc
 }
 
 template <int MODE, bool LUT = false, bool F32 = false>
-void launch_chi2_form(int G, dim3 grid, size_t lds, hipStream_t st, const ScanArgs &a)
+void launch_chi2_form(int G, dim3 grid, size_t lds, hipStream_t st, TimedBy ev, const ScanArgs &a)
 {
     dispatch_G<LUT ? 16 : 64>(G, [&](auto g) {
-        if constexpr (LUT) launch_with_lds(chi2_scan_kernel<decltype(g)::value, MODE, LUT, F32>, grid, SC_LUT_THREADS, lds, st, a);
-        else chi2_scan_kernel<decltype(g)::value, MODE, LUT, F32><<<grid, SC_THREADS, 0, st>>>(a);
+        launch_timed(chi2_scan_kernel<decltype(g)::value, MODE, LUT, F32>, grid, LUT ? SC_LUT_THREADS : SC_THREADS, lds, st, ev, a);
     });
 }
 
-void launch_chi2(int mode, int G, dim3 grid, hipStream_t st, const ScanArgs &a)
+// (the weighted form is two kernels: the scan's time runs from the start of the first to the end of the second)
+void launch_chi2(int mode, int G, dim3 grid, hipStream_t st, TimedBy ev, const ScanArgs &a)
 {
     if (mode == 1) {
-        if (a.lut6) launch_chi2_form<1, true, true>(G, grid, lut6_bytes(a.cpr, 2), st, a);
-        else if (a.lut) launch_chi2_form<1, true>(G, grid, lut_bytes(a.c_lut, 2), st, a);
-        else launch_chi2_form<1>(G, grid, 0, st, a);
-        chi2w_finalize_kernel<<<SC_NSEG, SC_FIN_THREADS, 0, st>>>(a);
+        if (a.lut6) launch_chi2_form<1, true, true>(G, grid, lut6_bytes(a.cpr, 2), st, ev.first(), a);
+        else if (a.lut) launch_chi2_form<1, true>(G, grid, lut_bytes(a.c_lut, 2), st, ev.first(), a);
+        else launch_chi2_form<1>(G, grid, 0, st, ev.first(), a);
+        launch_timed(chi2w_finalize_kernel, dim3(SC_NSEG), SC_FIN_THREADS, 0, st, ev.last(), a);
     }
-    else if (mode == 2) launch_chi2_form<2>(G, grid, 0, st, a);
-    else launch_chi2_form<0>(G, grid, 0, st, a);
+    else if (mode == 2) launch_chi2_form<2>(G, grid, 0, st, ev, a);
+    else launch_chi2_form<0>(G, grid, 0, st, ev, a);
 }
 
 // Kernel form of a chi2 scan.  Unit weights: MODE 2 (queued candidates) when many rows are expected to pass the
@@ -469,25 +469,23 @@ struct Chi2Launch {
     dim3 grid;
 };
 
-void launch_chi2_any(psk_ctx *ctx, const Chi2Launch &L)
+void launch_chi2_any(psk_ctx *ctx, const Chi2Launch &L, TimedBy ev)
 {
     const ScanArgs &a = L.x.s;
     if (L.compact) {
-        if (L.cpr == 1) chi2_scan_kernel_cx<1><<<L.grid, SC_THREADS, 0, ctx->stream>>>(L.x);
-        else chi2_scan_kernel_cx<2><<<L.grid, SC_THREADS, 0, ctx->stream>>>(L.x);
+        if (L.cpr == 1) launch_timed(chi2_scan_kernel_cx<1>, L.grid, SC_THREADS, 0, ctx->stream, ev, L.x);
+        else launch_timed(chi2_scan_kernel_cx<2>, L.grid, SC_THREADS, 0, ctx->stream, ev, L.x);
         return;
     }
-    launch_chi2(L.mode, group_lanes(a), L.grid, ctx->stream, a);
+    launch_chi2(L.mode, group_lanes(a), L.grid, ctx->stream, ev, a);
 }
 
 int run_chi2(psk_ctx *ctx, const Chi2Launch &L, int reps, double *ms_total, double *ms_each = nullptr)
 {
     *ms_total = 0;
     for (int r = 0; r < reps; r++) {
-        PSK_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-        launch_chi2_any(ctx, L);
+        launch_chi2_any(ctx, L, {ctx->ev0, ctx->ev1});
         PSK_HIP(ctx, hipGetLastError());
-        PSK_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
         PSK_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the kernel has written the counts to pinned memory
         float ms = 0;
         PSK_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
@@ -612,10 +610,8 @@ static int chi2_scan_launch(psk_ctx *ctx, const int8_t *pheno, const double *wei
     ctx->last_scan_kind = 1;
     if (ctx->n_kmers) {
         ScanSlot &sl = ctx->slot[set];
-        PSK_HIP(ctx, hipEventRecord(sl.ev0, ctx->stream));
-        launch_chi2_any(ctx, CL);
+        launch_chi2_any(ctx, CL, {sl.ev0, sl.ev1});   // the events ride on the dispatch: one command per scan
         PSK_HIP(ctx, hipGetLastError());
-        PSK_HIP(ctx, hipEventRecord(sl.ev1, ctx->stream));
         sl.in_flight = true;
         sl.seq = ++ctx->scan_seq;
         ctx->n_in_flight++;

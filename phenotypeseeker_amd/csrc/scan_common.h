@@ -6,6 +6,7 @@
 #include "dev_utils.h"
 #include "psk_internal.h"
 
+#include <hip/hip_ext.h>
 #include <type_traits>
 
 // tuning knobs (overridable at build time for A/B runs: make EXTRA=-DPSK_SC_UNROLL=...)
@@ -489,10 +490,20 @@ void dispatch_G(int G, F &&f)
     }
 }
 
-// launches a kernel that keeps `lds` bytes of tables in dynamic LDS (beyond the 64 KB a kernel gets unasked)
+// The event pair of a timed launch; either may be null.  The events ride on the kernel's own dispatch: nothing is queued
+// before or after the kernel for them, hipEventSynchronize(stop) waits for the kernel, and hipEventElapsedTime(start, stop)
+// is the dispatch's start to its end.  A scan of several kernels puts start on the first and stop on the last.
+struct TimedBy {
+    hipEvent_t start = nullptr, stop = nullptr;
+    TimedBy first() const { return {start, nullptr}; }
+    TimedBy last() const { return {nullptr, stop}; }
+};
+
+// The one way a scan kernel is launched: on `st`, timed by `ev`; lds > 0: the kernel keeps `lds` bytes of tables in
+// dynamic LDS (beyond the 64 KB a kernel gets unasked).
 template <class... KA, class... A>
-void launch_with_lds(void (*kern)(KA...), dim3 grid, int threads, size_t lds, hipStream_t st, const A &...args)
+void launch_timed(void (*kern)(KA...), dim3 grid, int threads, size_t lds, hipStream_t st, TimedBy ev, const A &...args)
 {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    kern<<<grid, threads, lds, st>>>(args...);
+    if (lds) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipExtLaunchKernelGGL(kern, grid, dim3(threads), (uint32_t)lds, st, ev.start, ev.stop, 0, KA(args)...);
 }

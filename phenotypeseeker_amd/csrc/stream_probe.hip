@@ -4,12 +4,11 @@
 // ceiling".  The ceiling is measured where the scan runs: the presence matrix itself -- the same bytes, the same residency
 // in the 256-MiB Infinity Cache as the scan sees between back-to-back launches -- is read once per launch by a kernel that
 // does nothing else (16 B per lane, four independent loads in flight per lane, XOR-folded so that the loads cannot be
-// dropped), timed with HIP events on the context's stream like the scan.  No reference counterpart: measurement only.
-#include "psk_internal.h"
+// dropped), timed on the context's stream the way the scan is (scan_common.h launch_timed: the events ride on the kernel's
+// dispatch).  No reference counterpart: measurement only.
+#include "scan_common.h"
 
 namespace {
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // Shape 0: grid-stride, four loads 1/4 of the grid's span apart per lane.
 // Shape 1: the scan's own shape -- a wave owns UNR consecutive 1-KiB pieces per step (64 lanes x 16 B each), the waves of the
@@ -52,11 +51,9 @@ int time_shape(psk_ctx *ctx, unsigned blocks, uint64_t n_vec, int reps, double *
 {
     double total = 0;
     for (int r = 0; r < reps; r++) {
-        PSK_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-        stream_read_kernel<SHAPE, NT><<<blocks, 256, 0, ctx->stream>>>(reinterpret_cast<const u32x4 *>(ctx->bits.p), n_vec,
-                                                                       ctx->bits.as<uint32_t>(), 0x9e3779b9u ^ (uint32_t)r);
+        launch_timed(stream_read_kernel<SHAPE, NT>, dim3(blocks), 256, 0, ctx->stream, {ctx->ev0, ctx->ev1},
+                     reinterpret_cast<const u32x4 *>(ctx->bits.p), n_vec, ctx->bits.as<uint32_t>(), 0x9e3779b9u ^ (uint32_t)r);
         PSK_HIP(ctx, hipGetLastError());
-        PSK_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
         PSK_HIP(ctx, hipStreamSynchronize(ctx->stream));
         float ms = 0;
         PSK_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));

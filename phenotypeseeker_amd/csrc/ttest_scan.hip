@@ -337,28 +337,28 @@ __global__ __launch_bounds__(256) void ttest_means_kernel(const ScanArgs P)
 }
 
 template <bool WT, bool LUT = false, bool F32 = false>
-void launch_ttest_form(int G, dim3 grid, size_t lds, hipStream_t st, const ScanArgs &a, double mu)
+void launch_ttest_form(int G, dim3 grid, size_t lds, hipStream_t st, TimedBy ev, const ScanArgs &a, double mu)
 {
     dispatch_G<LUT ? 16 : 64>(G, [&](auto g) {
-        if constexpr (LUT) launch_with_lds(ttest_scan_kernel<decltype(g)::value, WT, LUT, F32>, grid, SC_LUT_THREADS, lds, st, a, mu);
-        else ttest_scan_kernel<decltype(g)::value, WT, LUT, F32><<<grid, SC_THREADS, 0, st>>>(a, mu);
+        launch_timed(ttest_scan_kernel<decltype(g)::value, WT, LUT, F32>, grid, LUT ? SC_LUT_THREADS : SC_THREADS, lds, st, ev, a, mu);
     });
 }
 
+// (three kernels: the scan's time runs from the start of the first to the end of the third)
 template <bool WT>
-void launch_ttest_w(int G, dim3 grid, hipStream_t st, const ScanArgs &a, double mu)
+void launch_ttest_w(int G, dim3 grid, hipStream_t st, TimedBy ev, const ScanArgs &a, double mu)
 {
-    if (a.lut6) launch_ttest_form<WT, true, true>(G, grid, lut6_bytes(a.cpr, WT ? 3 : 2), st, a, mu);
-    else if (a.lut) launch_ttest_form<WT, true>(G, grid, lut_bytes(a.c_lut, WT ? 3 : 2), st, a, mu);
-    else launch_ttest_form<WT>(G, grid, 0, st, a, mu);
-    ttest_finalize_kernel<WT><<<SC_NSEG, SC_FIN_THREADS, 0, st>>>(a);
-    ttest_means_kernel<WT><<<SC_NSEG, 256, 0, st>>>(a);
+    if (a.lut6) launch_ttest_form<WT, true, true>(G, grid, lut6_bytes(a.cpr, WT ? 3 : 2), st, ev.first(), a, mu);
+    else if (a.lut) launch_ttest_form<WT, true>(G, grid, lut_bytes(a.c_lut, WT ? 3 : 2), st, ev.first(), a, mu);
+    else launch_ttest_form<WT>(G, grid, 0, st, ev.first(), a, mu);
+    launch_timed(ttest_finalize_kernel<WT>, dim3(SC_NSEG), SC_FIN_THREADS, 0, st, TimedBy(), a);
+    launch_timed(ttest_means_kernel<WT>, dim3(SC_NSEG), 256, 0, st, ev.last(), a);
 }
 
-void launch_ttest(int G, dim3 grid, hipStream_t st, const ScanArgs &a, double mu, bool weighted)
+void launch_ttest(int G, dim3 grid, hipStream_t st, TimedBy ev, const ScanArgs &a, double mu, bool weighted)
 {
-    if (weighted) launch_ttest_w<true>(G, grid, st, a, mu);
-    else launch_ttest_w<false>(G, grid, st, a, mu);
+    if (weighted) launch_ttest_w<true>(G, grid, st, ev, a, mu);
+    else launch_ttest_w<false>(G, grid, st, ev, a, mu);
 }
 
 // builds the nibble table of row_moments_lut (scan_common.h)
@@ -584,10 +584,8 @@ extern "C" int psk_ttest_scan(psk_ctx *ctx, const double *pheno, const uint8_t *
     ctx->last_scan_kind = 2;
     ctx->last.valid = false;
     if (ctx->n_kmers) {
-        PSK_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-        launch_ttest(G, sh.grid, ctx->stream, a, T.mu, !T.unit_w);
+        launch_ttest(G, sh.grid, ctx->stream, {ctx->ev0, ctx->ev1}, a, T.mu, !T.unit_w);
         PSK_HIP(ctx, hipGetLastError());
-        PSK_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
         PSK_HIP(ctx, hipStreamSynchronize(ctx->stream));
         float ms = 0;
         PSK_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));

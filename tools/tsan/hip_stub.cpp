@@ -1,4 +1,4 @@
-// A HIP runtime that has no device: the 31 entry points libpsk.so imports, for tools/tsan_host.sh (the
+// A HIP runtime that has no device: the 32 entry points libpsk.so imports, for tools/tsan_host.sh (the
 // threaded host ingest -- reader + upload | inflate | count -- had no race-detector pass; GPU sanitizers are not available on
 // this pool and TSan cannot follow a real runtime's threads anyway).  "Device" memory is host memory, copies and memsets are
 // done on the spot, kernel launches do NOTHING and succeed: the host code's threads, locks and hand-overs run exactly as they do
@@ -36,6 +36,7 @@ hipError_t __hipPopCallConfiguration(dim3 *grid, dim3 *block, size_t *shmem, hip
     return hipSuccess;
 }
 hipError_t hipLaunchKernel(const void *, dim3, dim3, void **, size_t, hipStream_t) { return hipSuccess; }
+hipError_t hipExtLaunchKernel(const void *, dim3, dim3, void **, size_t, hipStream_t, hipEvent_t, hipEvent_t, int) { return hipSuccess; }
 
 hipError_t hipGetDeviceCount(int *n) { *n = 1; return hipSuccess; }
 hipError_t hipSetDevice(int) { return hipSuccess; }
