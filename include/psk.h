@@ -237,6 +237,13 @@ int psk_chi2_pretest(double A, double B, double C, double D, double thr);
  * dropped on its header byte; with no bit set the scan does not read the slots at all.  Host code: no context, no device. */
 int psk_cx_plan(int n1, int n0, int n_samples, int min_samples, int max_samples, double thr, uint32_t *class_mask,
                 uint64_t *corner /* [2] */);
+/* The launch shape of the side-matrix kernel (chi2_scan_kernel_cx_side) of a scan with no feasible slot class: n_ov
+ * overflow rows of cpr (1 or 2) 16-byte chunks, at most cap_blocks workgroups.  *blocks = workgroups of the launch (what
+ * one batch per wave needs, capped, never below the 256 result segments); a wave takes the batches of *batch_rows rows
+ * w, w + W, ... of the W = 4 * blocks waves; *rows_per_block bounds the rows one workgroup visits (it sizes the result
+ * segments).  batch_rows may be NULL.  Host code: no context, no device. */
+int psk_cx_side_shape(uint64_t n_ov, int cpr, uint64_t cap_blocks, uint32_t *blocks, uint64_t *rows_per_block,
+                      uint32_t *batch_rows);
 /* The plan of the last chi2 scan launched or repeated on the context: *encoded = 1 when it took the exception-coded path
  * (else the other two are 0), *class_mask as psk_cx_plan gives it, *slots_skipped = 1 when the launch read only the side
  * matrix of overflow rows.  Measurement and tests only.  Any pointer may be NULL. */

@@ -67,6 +67,7 @@ _SIGNATURES = {
     "psk_compact_info": (c.c_int, [c.c_void_p, c.POINTER(c.c_int), c.POINTER(c.c_uint64)]),
     "psk_chi2_pretest": (c.c_int, [c.c_double] * 5),
     "psk_cx_plan": (c.c_int, [c.c_int] * 5 + [c.c_double, c.POINTER(c.c_uint32), _u64p]),
+    "psk_cx_side_shape": (c.c_int, [c.c_uint64, c.c_int, c.c_uint64, c.POINTER(c.c_uint32), _u64p, c.POINTER(c.c_uint32)]),
     "psk_last_scan_plan": (c.c_int, [c.c_void_p, c.POINTER(c.c_int), c.POINTER(c.c_uint32), c.POINTER(c.c_int)]),
     "psk_last_scan_ms": (c.c_double, [c.c_void_p]),
     "psk_rescan_timed": (c.c_int, [c.c_void_p, c.c_int, c.POINTER(c.c_double)]),

@@ -341,6 +341,7 @@ extern "C" int psk_begin(psk_ctx *ctx, int k, int n_samples, uint64_t slab_lo, u
     ctx->n_in_flight = 0;
     ctx->results_valid = false;
     ctx->dense_hint = -1;
+    ctx->cx_plan.valid = false;
     reset_lists(ctx, n_samples);
     ctx->k = k;
     ctx->n_samples = n_samples;

@@ -20,6 +20,7 @@
 // so round(chi2, 2) and "%.2E" % p come out string-identical.  The expensive exact evaluation only
 // runs on rows that a division-free test T*(ad-bc)^2 >= thr*R1*R0*K1*K0*(1-1e-9) cannot rule out.
 #include "scan_common.h"
+#include "cx_side_plan.h"
 
 #include <algorithm>
 #include <cmath>
@@ -56,25 +57,32 @@ __host__ __device__ __forceinline__ bool chi2_pretest(double A, double B, double
 // The chi2 decision, once: statistic, p and the keep rule from the four cells.  The scan kernels append what is kept to
 // a reserved slot (chi2_decide); chi2w_finalize_kernel compacts on the answer (`valid`: the lane holds a candidate) and
 // stores to the compacted position.  The operation order is the reference's and must not move.
-__device__ __forceinline__ bool chi2_keep(const ScanArgs &P, double A, double B, double C, double D, double &stat, double &p, bool valid = true)
+__device__ __forceinline__ bool chi2_keep(const ScanCuts &K, double A, double B, double C, double D, double &stat, double &p, bool valid = true)
 {
     stat = chi2_exact(A, B, C, D);
     p = exp(-0.5 * stat);  // chi2.sf(stat, df = 2), modeling.py:782-792
-    return valid && ((P.omit_B && p < P.pcut) || (p < P.pcut_bonf));  // modeling.py:795
+    return valid && ((K.omit_B && p < K.pcut) || (p < K.pcut_bonf));  // modeling.py:795
 }
 
-__device__ __forceinline__ void chi2_store(const ScanArgs &P, uint64_t idx, uint64_t row, double stat, double p, int n_w)
+__device__ __forceinline__ void chi2_store(const ScanSink &S, uint64_t idx, uint64_t row, double stat, double p, int n_w)
 {
-    P.res_row[idx] = row;
-    P.res_stat[idx] = stat;
-    P.res_p[idx] = p;
-    P.res_nw[idx] = n_w;
+    S.res_row[idx] = row;
+    S.res_stat[idx] = stat;
+    S.res_p[idx] = p;
+    S.res_nw[idx] = n_w;
 }
 
 __device__ __forceinline__ void chi2_decide(const ScanArgs &P, uint64_t row, double A, double B, double C, double D, int n_w)
 {
     double stat, p;
-    if (chi2_keep(P, A, B, C, D, stat, p)) chi2_store(P, reserve_slot(P), row, stat, p, n_w);
+    if (chi2_keep(P.cut, A, B, C, D, stat, p)) chi2_store(P.sink, reserve_slot(P.sink), row, stat, p, n_w);
+}
+
+// chi2_scan_kernel MODE 0 from the two class counts of a row
+__device__ __forceinline__ void chi2_evaluate(const ScanCuts &K, const ScanSink &S, uint64_t row, int a, int c)
+{
+    double stat, p;
+    if (chi2_keep(K, (double)a, (double)(K.n1 - a), (double)c, (double)(K.n0 - c), stat, p)) chi2_store(S, reserve_slot(S), row, stat, p, a + c);
 }
 
 // MODE 0: unit weights, the exact evaluation in line -- the usual case, where almost no row passes the pre-test.
@@ -118,8 +126,8 @@ __global__ __launch_bounds__(LUT ? SC_LUT_THREADS : SC_THREADS) void chi2_scan_k
             const double T = P.W1 + P.W0, err = P.e0 + P.e1;
             const double det = fabs(ws[0] * P.W0 - ws[1] * P.W1) + (P.e0 * P.W0 + P.e1 * P.W1);
             const double K1 = (ws[0] + ws[1]) - err, K0 = (T - (ws[0] + ws[1])) - err;
-            const bool cand = !(K1 > 0.0 && K0 > 0.0) || !(T * det * det < P.thr * P.W1 * P.W0 * K1 * K0 * (1.0 - 1e-9));
-            if (act && cand) append_candidate(P, r, r_nw);
+            const bool cand = !(K1 > 0.0 && K0 > 0.0) || !(T * det * det < P.cut.thr * P.W1 * P.W0 * K1 * K0 * (1.0 - 1e-9));
+            if (act && cand) append_candidate(P.sink, r, r_nw);
             return;
         } else if (WEIGHTED) {
             double ws[2];
@@ -128,14 +136,14 @@ __global__ __launch_bounds__(LUT ? SC_LUT_THREADS : SC_THREADS) void chi2_scan_k
             A = ws[0]; B = P.W1 - ws[0]; C = ws[1]; D = P.W0 - ws[1];
             const double R1 = A + B, R0 = C + D, K1 = A + C, K0 = B + D, T = R1 + R0;
             const double det = A * D - B * C;
-            const double lhs = T * det * det, rhs = P.thr * R1 * R0 * K1 * K0;
+            const double lhs = T * det * det, rhs = P.cut.thr * R1 * R0 * K1 * K0;
             // candidates only: chi2w_finalize_kernel gives them the reference's own cells and decides (the sums here
             // associate differently, ~1e-15: hence the 1e-9 margin)
-            if (act && !(lhs < rhs * (1.0 - 1e-9))) append_candidate(P, r, r_nw);
+            if (act && !(lhs < rhs * (1.0 - 1e-9))) append_candidate(P.sink, r, r_nw);
             return;
         } else {
             if (!act) return;
-            A = (double)qv.x; B = (double)(P.n1 - qv.x); C = (double)qv.y; D = (double)(P.n0 - qv.y);
+            A = (double)qv.x; B = (double)(P.cut.n1 - qv.x); C = (double)qv.y; D = (double)(P.cut.n0 - qv.y);
             r_nw = qv.x + qv.y;
         }
         chi2_decide(P, r, A, B, C, D, r_nw);
@@ -144,14 +152,14 @@ __global__ __launch_bounds__(LUT ? SC_LUT_THREADS : SC_THREADS) void chi2_scan_k
     auto on_row = [&](uint64_t row, const uint32_t (&cnt)[2], bool lead) {
         const uint32_t a = cnt[0], c = cnt[1];
         const int n_w = (int)(a + c);
-        const int n_wo = (P.n1 - (int)a) + (P.n0 - (int)c);
-        const bool freq_ok = (row < P.M) && !(n_w < P.min_samples || n_wo < 2 || n_w > P.max_samples);
+        const int n_wo = (P.cut.n1 - (int)a) + (P.cut.n0 - (int)c);
+        const bool freq_ok = (row < P.M) && !(n_w < P.cut.min_samples || n_wo < 2 || n_w > P.cut.max_samples);
         if (WEIGHTED) {
             Q.n = queue_rows(freq_ok && lead, row, make_int2(n_w, 0), Q.row, Q.val, Q.n, lane);
             return;
         }
-        const double A = (double)a, B = (double)(P.n1 - (int)a), C = (double)c, D = (double)(P.n0 - (int)c);
-        const bool cand = freq_ok && lead && chi2_pretest(A, B, C, D, P.thr);
+        const double A = (double)a, B = (double)(P.cut.n1 - (int)a), C = (double)c, D = (double)(P.cut.n0 - (int)c);
+        const bool cand = freq_ok && lead && chi2_pretest(A, B, C, D, P.cut.thr);
         if (MODE == 2) {
             Q.n = queue_rows(cand, row, make_int2((int)a, (int)c), Q.row, Q.val, Q.n, lane);
             return;
@@ -160,7 +168,7 @@ __global__ __launch_bounds__(LUT ? SC_LUT_THREADS : SC_THREADS) void chi2_scan_k
     };
     if constexpr (QUEUED) stream_rows<G, LUT>(P, mk, Q, on_row, process);
     else stream_rows<G, LUT>(P, mk, Q, on_row, NoQueue());
-    if (!WEIGHTED) publish_segment(P);   // weighted: chi2w_finalize_kernel publishes
+    if (!WEIGHTED) publish_segment(P.sink);   // weighted: chi2w_finalize_kernel publishes
 }
 
 // ---- the unweighted scan over the exception-coded rows (presence_compact.hip) ------------------------------------------
@@ -182,7 +190,79 @@ __global__ __launch_bounds__(LUT ? SC_LUT_THREADS : SC_THREADS) void chi2_scan_k
 #ifndef PSK_CX_NT
 #define PSK_CX_NT 0   // plain loads: 57.4 us against 60.7 us with the nontemporal hint at config 2
 #endif
+#ifndef PSK_CX_SIDE_NT
+#define PSK_CX_SIDE_NT 1   // nontemporal hint on the side matrix: lower in five of six pairs of the r13 table (docs/NOTEBOOK.md), also re-read launch after launch
+#endif
+#ifndef PSK_CX_SIDE_GRID_MULT
+#define PSK_CX_SIDE_GRID_MULT 8   // workgroups per CU of chi2_scan_kernel_cx_side when PSK_GRID_MULT is unset (r13 table: 8 before 4 and the one-batch grid)
+#endif
 constexpr int CX_UNROLL = PSK_CX_UNROLL;   // 16-byte loads in flight per lane
+static_assert(CX_SIDE_WAVES * 64 == SC_THREADS && CX_SIDE_NSEG == SC_NSEG, "cx_side_plan.h restates the launch constants");
+
+// The rows of the side matrix, once: UNR wave steps of 64 / CPR rows from step s0 on, one lane per 16-byte chunk.
+// load() issues the batch's loads; evaluate() is chi2_scan_kernel MODE 0's on_row on what came back -- popcounts against
+// the lane's mask words, the sum over the row's CPR lanes, frequency filter and chi2_pretest in line, then the exact
+// decision -- and reports a survivor under its original row id.  Both are called by whole waves (the CPR = 2 shuffle).
+template <int CPR, int UNR, bool NT>
+struct SideRows {
+    static constexpr int RPW = 64 / CPR;   // rows per wave step
+    const u32x4 *ov;
+    const uint32_t *ov_row;
+    uint64_t n_ov;
+    uint64_t m1a, m1b, m0a, m0b;           // this lane's two words of each mask
+    int lane, g;
+
+    __device__ __forceinline__ SideRows(const u32x4 *ov_, const uint32_t *ov_row_, uint64_t n_ov_, const uint64_t *m1, const uint64_t *m0)
+        : ov(ov_), ov_row(ov_row_), n_ov(n_ov_)
+    {
+        lane = threadIdx.x & 63;
+        g = lane & (CPR - 1);
+        m1a = m1[2 * g]; m1b = m1[2 * g + 1]; m0a = m0[2 * g]; m0b = m0[2 * g + 1];
+    }
+    __device__ __forceinline__ uint64_t n_steps() const { return (n_ov + RPW - 1) / RPW; }
+    __device__ __forceinline__ void load(u32x4 (&x)[UNR], uint64_t s0) const
+    {
+#pragma unroll
+        for (int u = 0; u < UNR; u++) {
+            const uint64_t r = (s0 + u) * RPW + lane / CPR;
+            x[u] = r < n_ov ? (NT ? __builtin_nontemporal_load(&ov[r * CPR + g]) : ov[r * CPR + g]) : (u32x4)(0u);
+        }
+    }
+    __device__ __forceinline__ void evaluate(const u32x4 (&x)[UNR], uint64_t s0, const ScanCuts &K, const ScanSink &S) const
+    {
+        uint32_t ac[UNR], pend = 0;   // a | c << 16 of the batch's rows; bit u: row u passed the filter and the pre-test
+#pragma unroll
+        for (int u = 0; u < UNR; u++) {
+            const uint64_t r = (s0 + u) * RPW + lane / CPR;
+            const uint64_t xa = ((uint64_t)x[u].y << 32) | x[u].x, xb = ((uint64_t)x[u].w << 32) | x[u].z;
+            uint32_t a = __popcll(xa & m1a) + __popcll(xb & m1b);
+            uint32_t c = __popcll(xa & m0a) + __popcll(xb & m0b);
+            if (CPR == 2) {
+                a += __shfl_xor(a, 1, 64);
+                c += __shfl_xor(c, 1, 64);
+            }
+            // chi2_scan_kernel MODE 0's on_row
+            const int n_w = (int)(a + c);
+            const int n_wo = (K.n1 - (int)a) + (K.n0 - (int)c);
+            const bool freq_ok = (r < n_ov) && !(n_w < K.min_samples || n_wo < 2 || n_w > K.max_samples);
+            const double A = (double)a, B = (double)(K.n1 - (int)a), C = (double)c, D = (double)(K.n0 - (int)c);
+            ac[u] = a | (c << 16);
+            if (freq_ok && g == 0 && chi2_pretest(A, B, C, D, K.thr)) pend |= 1u << u;
+        }
+        // the exact decision, one copy of it: almost no row gets here, and UNR copies in line cost the streaming part
+        // its registers (122 VGPRs against 64 at UNR = 4).  Ascending u, as the in-line form appended them.
+        while (pend) {
+            const int u = __builtin_ctz(pend);
+            pend &= pend - 1;
+            uint32_t v = ac[0];
+#pragma unroll
+            for (int j = 1; j < UNR; j++) v = u == j ? ac[j] : v;
+            const uint64_t r = (s0 + u) * RPW + lane / CPR;
+            chi2_evaluate(K, S, ov_row[r], (int)(v & 0xffffu), (int)(v >> 16));
+        }
+    }
+};
+
 struct CxScanArgs {
     ScanArgs s;                  // the scan: unit weights, masks inline
     const u32x4 *slots;          // two slots per 16 bytes
@@ -202,10 +282,6 @@ __global__ __launch_bounds__(SC_THREADS) void chi2_scan_kernel_cx(const CxScanAr
     const ScanArgs &P = X.s;
     __shared__ uint16_t s_cls[CX_MAX_SAMPLES];
     const int lane = threadIdx.x & 63;
-    auto evaluate = [&](uint64_t row, int a, int c) {   // chi2_scan_kernel MODE 0
-        double stat, p;
-        if (chi2_keep(P, (double)a, (double)(P.n1 - a), (double)c, (double)(P.n0 - c), stat, p)) chi2_store(P, reserve_slot(P), row, stat, p, a + c);
-    };
     if (blockIdx.x < X.slot_blocks) {
         {
             const int t = threadIdx.x;
@@ -243,44 +319,62 @@ __global__ __launch_bounds__(SC_THREADS) void chi2_scan_kernel_cx(const CxScanAr
                     int a = (int)(sum & 0xffu), c = (int)(sum >> 8);   // (a', c'): at most e <= 7 each
                     const bool absent = (h & CX_HDR_BASE) != 0;
                     if (!((X.corner[absent ? 1 : 0] >> (a * 8 + c)) & 1ull)) continue;
-                    if (absent) { a = P.n1 - a; c = P.n0 - c; }
-                    evaluate(row, a, c);
+                    if (absent) { a = P.cut.n1 - a; c = P.cut.n0 - c; }
+                    chi2_evaluate(P.cut, P.sink, row, a, c);
                 }
         }
     } else if (blockIdx.x - X.slot_blocks < X.ov_blocks) {
-        constexpr int RPW = 64 / CPR;   // rows per wave step
-        const int g = lane & (CPR - 1);
-        const uint64_t m1a = P.m1_inl[2 * g], m1b = P.m1_inl[2 * g + 1], m0a = P.m0_inl[2 * g], m0b = P.m0_inl[2 * g + 1];
+        const SideRows<CPR, CX_UNROLL, PSK_CX_NT != 0> R(X.ov, X.ov_row, X.n_ov, P.m1_inl, P.m0_inl);
         const uint64_t wave = (uint64_t)(blockIdx.x - X.slot_blocks) * (SC_THREADS / 64) + (threadIdx.x >> 6);
         const uint64_t total_waves = (uint64_t)X.ov_blocks * (SC_THREADS / 64);
-        const uint64_t n_steps = (X.n_ov + RPW - 1) / RPW;
+        const uint64_t n_steps = R.n_steps();
         for (uint64_t s0 = wave * CX_UNROLL; s0 < n_steps; s0 += total_waves * CX_UNROLL) {
             u32x4 x[CX_UNROLL];
-#pragma unroll
-            for (int u = 0; u < CX_UNROLL; u++) {
-                const uint64_t r = (s0 + u) * RPW + lane / CPR;
-                x[u] = r < X.n_ov ? (PSK_CX_NT ? __builtin_nontemporal_load(&X.ov[r * CPR + g]) : X.ov[r * CPR + g]) : (u32x4)(0u);
-            }
-#pragma unroll
-            for (int u = 0; u < CX_UNROLL; u++) {
-                const uint64_t r = (s0 + u) * RPW + lane / CPR;
-                const uint64_t xa = ((uint64_t)x[u].y << 32) | x[u].x, xb = ((uint64_t)x[u].w << 32) | x[u].z;
-                uint32_t a = __popcll(xa & m1a) + __popcll(xb & m1b);
-                uint32_t c = __popcll(xa & m0a) + __popcll(xb & m0b);
-                if (CPR == 2) {
-                    a += __shfl_xor(a, 1, 64);
-                    c += __shfl_xor(c, 1, 64);
-                }
-                // chi2_scan_kernel MODE 0's on_row
-                const int n_w = (int)(a + c);
-                const int n_wo = (P.n1 - (int)a) + (P.n0 - (int)c);
-                const bool freq_ok = (r < X.n_ov) && !(n_w < P.min_samples || n_wo < 2 || n_w > P.max_samples);
-                const double A = (double)a, B = (double)(P.n1 - (int)a), C = (double)c, D = (double)(P.n0 - (int)c);
-                if (freq_ok && g == 0 && chi2_pretest(A, B, C, D, P.thr)) evaluate(X.ov_row[r], (int)a, (int)c);
-            }
+            R.load(x, s0);
+            R.evaluate(x, s0, P.cut, P.sink);
         }
     }
-    publish_segment(P);
+    publish_segment(P.sink);
+}
+
+// ---- the side matrix alone: what every scan with no feasible class launches (the Bonferroni scans of a real run) ------
+// The mixed kernel above gives the side matrix one batch per wave; its registers are the slot branch's and its 864 bytes
+// of arguments every form's.  Here the arguments are what the rows need, there is no LDS, and the grid is what stays
+// resident (cx_side_shape): every wave walks its batches grid-stride and has the next batch's loads in flight while it
+// evaluates the current one (two register sets, swapped by unrolling the loop twice).
+struct CxSideArgs {
+    const u32x4 *ov;
+    const uint32_t *ov_row;
+    uint64_t n_ov;
+    uint64_t m1[4], m0[4];       // the mask words of the row's (at most two) chunks
+    ScanCuts cut;
+    ScanSink sink;
+};
+static_assert(sizeof(CxSideArgs) <= 256, "chi2_scan_kernel_cx_side's arguments are meant to stay small");
+
+template <int CPR>
+__global__ __launch_bounds__(SC_THREADS) void chi2_scan_kernel_cx_side(const CxSideArgs X)
+{
+    const SideRows<CPR, CX_SIDE_UNROLL, PSK_CX_SIDE_NT != 0> R(X.ov, X.ov_row, X.n_ov, X.m1, X.m0);
+    const uint64_t stride = (uint64_t)gridDim.x * CX_SIDE_WAVES * CX_SIDE_UNROLL;
+    const uint64_t n_steps = R.n_steps();
+    uint64_t s0 = ((uint64_t)blockIdx.x * CX_SIDE_WAVES + (threadIdx.x >> 6)) * CX_SIDE_UNROLL;
+    u32x4 xa[CX_SIDE_UNROLL], xb[CX_SIDE_UNROLL];
+    if (s0 < n_steps) R.load(xa, s0);
+    while (s0 < n_steps) {
+        if (s0 + stride < n_steps) R.load(xb, s0 + stride);
+        R.evaluate(xa, s0, X.cut, X.sink);
+        s0 += stride;
+        if (!(s0 < n_steps)) break;
+        if (s0 + stride < n_steps) R.load(xa, s0 + stride);
+        R.evaluate(xb, s0, X.cut, X.sink);
+        s0 += stride;
+    }
+#ifdef PSK_CX_SIDE_TWO_ATOMICS   // A/B builds: the other kernels' publish (r13: 13.4-13.6 us against 13.1-13.2)
+    publish_segment(X.sink);
+#else
+    publish_segment_once(X.sink);
+#endif
 }
 
 // Second pass of the weighted chi2 scan: one workgroup per result segment, one candidate per lane.  The 2 x 2 table is
@@ -300,15 +394,15 @@ __global__ __launch_bounds__(SC_FIN_THREADS) void chi2w_finalize_kernel(const Sc
     // operations per sample.
     __shared__ double2 s_tab[SC_FIN_BLK * 128];
     const uint32_t seg = blockIdx.x;
-    const uint32_t c = P.counter[seg * SC_CNT_STRIDE];
-    const uint64_t base = (uint64_t)seg * P.seg_cap;
+    const uint32_t c = P.sink.counter[seg * SC_CNT_STRIDE];
+    const uint64_t base = (uint64_t)seg * P.sink.seg_cap;
     if (threadIdx.x == 0) s_out = 0;
     __syncthreads();
     for (uint32_t s0 = 0; s0 < c; s0 += SC_FIN_THREADS) {
         const uint32_t i = s0 + threadIdx.x;
         const bool valid = i < c;
-        const uint64_t row = valid ? P.res_row[base + i] : 0;
-        const int32_t nw = valid ? P.res_nw[base + i] : 0;
+        const uint64_t row = valid ? P.sink.res_row[base + i] : 0;
+        const int32_t nw = valid ? P.sink.res_nw[base + i] : 0;
         const bool wave_any = __any(valid);
         const u32x4 *rp = P.half ? sc_row_ptr<true>(P, row) : sc_row_ptr<false>(P, row);
         // the four cells, sample by sample
@@ -340,19 +434,19 @@ __global__ __launch_bounds__(SC_FIN_THREADS) void chi2w_finalize_kernel(const Sc
         }
         double stat = 0.0, p = 1.0;
         bool keep = false;
-        if (wave_any) keep = chi2_keep(P, ca, cb, cc, cd, stat, p, valid);
+        if (wave_any) keep = chi2_keep(P.cut, ca, cb, cc, cd, stat, p, valid);
         uint32_t tot;
         const uint32_t pos = psk_block_excl_scan_u32<SC_FIN_THREADS>(keep ? 1u : 0u, &tot, scan_lds);  // barriers inside
         const uint32_t out = s_out;
-        if (keep) chi2_store(P, base + out + pos, row, stat, p, nw);  // <= base + i: compaction only moves entries down
+        if (keep) chi2_store(P.sink, base + out + pos, row, stat, p, nw);  // <= base + i: compaction only moves entries down
         __syncthreads();
         if (threadIdx.x == 0) s_out = out + tot;
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        P.counter[seg * SC_CNT_STRIDE] = 0;  // re-armed for the next scan
-        P.final_counts[seg] = s_out;
-        P.host_counts[seg] = s_out;
+        P.sink.counter[seg * SC_CNT_STRIDE] = 0;  // re-armed for the next scan
+        P.sink.final_counts[seg] = s_out;
+        P.sink.host_counts[seg] = s_out;
     }
 }
 
@@ -448,6 +542,9 @@ dim3 cx_grid(const psk_ctx *ctx, CxScanArgs &x, int cpr)
     return dim3((unsigned)total);
 }
 
+// most workgroups of chi2_scan_kernel_cx_side: PSK_GRID_MULT per CU when set, else the kernel's own multiple
+uint64_t cx_side_grid_cap(const psk_ctx *ctx) { return (uint64_t)(ctx->n_cu > 0 ? ctx->n_cu : 256) * (ctx->grid_mult ? ctx->grid_mult : PSK_CX_SIDE_GRID_MULT); }
+
 // the most rows one workgroup of chi2_scan_kernel_cx visits
 uint64_t cx_rows_per_block(const CxScanArgs &x, int cpr)
 {
@@ -463,7 +560,8 @@ uint64_t cx_rows_per_block(const CxScanArgs &x, int cpr)
 // One chi2 scan as the host launches it: the dense kernels' arguments, and the exception-coded path when it runs
 struct Chi2Launch {
     CxScanArgs x;      // x.s: every form's arguments; the rest: chi2_scan_kernel_cx's
-    bool compact = false;
+    CxSideArgs side;   // chi2_scan_kernel_cx_side's, when the plan says so (side_kernel)
+    bool compact = false, side_kernel = false;
     int mode = 0;      // of the dense kernels (pick_chi2_mode)
     int cpr = 0;
     dim3 grid;
@@ -472,6 +570,11 @@ struct Chi2Launch {
 void launch_chi2_any(psk_ctx *ctx, const Chi2Launch &L, TimedBy ev)
 {
     const ScanArgs &a = L.x.s;
+    if (L.compact && L.side_kernel) {
+        if (L.cpr == 1) launch_timed(chi2_scan_kernel_cx_side<1>, L.grid, SC_THREADS, 0, ctx->stream, ev, L.side);
+        else launch_timed(chi2_scan_kernel_cx_side<2>, L.grid, SC_THREADS, 0, ctx->stream, ev, L.side);
+        return;
+    }
     if (L.compact) {
         if (L.cpr == 1) launch_timed(chi2_scan_kernel_cx<1>, L.grid, SC_THREADS, 0, ctx->stream, ev, L.x);
         else launch_timed(chi2_scan_kernel_cx<2>, L.grid, SC_THREADS, 0, ctx->stream, ev, L.x);
@@ -515,18 +618,18 @@ static int fill_chi2_args(psk_ctx *ctx, Chi2Launch &CL, int set, bool build_tabl
     a.tab = reinterpret_cast<const double *>(a.m1 + 2 * (size_t)mw);  // [sample][w if pheno 1 | w if pheno 0]
     a.inline_masks = L.inline_masks;
     if (L.inline_masks) { memcpy(a.m1_inl, L.m1, sizeof(a.m1_inl)); memcpy(a.m0_inl, L.m0, sizeof(a.m0_inl)); }
-    a.min_samples = L.min_samples;
-    a.max_samples = L.max_samples;
-    a.pcut = L.pvalue_cutoff;
-    a.pcut_bonf = L.pvalue_cutoff / (double)L.n_kmers_global;
-    a.omit_B = L.omit_B;
-    double pmax = a.pcut_bonf;
-    if (L.omit_B && a.pcut > pmax) pmax = a.pcut;
-    if (pmax >= 1.0) a.thr = 0.0;
-    else if (pmax <= 0.0) a.thr = INFINITY;
-    else a.thr = -2.0 * log(pmax);
+    a.cut.min_samples = L.min_samples;
+    a.cut.max_samples = L.max_samples;
+    a.cut.pcut = L.pvalue_cutoff;
+    a.cut.pcut_bonf = L.pvalue_cutoff / (double)L.n_kmers_global;
+    a.cut.omit_B = L.omit_B;
+    double pmax = a.cut.pcut_bonf;
+    if (L.omit_B && a.cut.pcut > pmax) pmax = a.cut.pcut;
+    if (pmax >= 1.0) a.cut.thr = 0.0;
+    else if (pmax <= 0.0) a.cut.thr = INFINITY;
+    else a.cut.thr = -2.0 * log(pmax);
     a.W1 = L.W1; a.W0 = L.W0;
-    a.n1 = L.n1; a.n0 = L.n0;
+    a.cut.n1 = L.n1; a.cut.n0 = L.n0;
     ScanShape sh;   // weighted: class-weight sums from a table in LDS (e0 = class 1, e1 = class 0)
     PSK_TRY(setup_table_scan(ctx, a, L.weighted ? a.tab : nullptr, 2, L.W1, L.W0, 0.0, build_tables, &sh));
     CL.compact = ctx->cx_valid && !L.weighted && L.inline_masks && !env_flag("PSK_SCAN_DENSE");
@@ -538,14 +641,52 @@ static int fill_chi2_args(psk_ctx *ctx, Chi2Launch &CL, int set, bool build_tabl
         x.ov = ctx->cx_ov.as<u32x4>();
         x.ov_row = ctx->cx_ov_row.as<uint32_t>();
         x.n_ov = ctx->cx_n_ov;
-        cx_plan(a.n1, a.n0, ctx->n_samples, a.min_samples, a.max_samples, a.thr, &x.class_mask, x.corner);
-        CL.grid = cx_grid(ctx, x, CL.cpr);
+        int side_on = 1;   // read per scan: A/B runs and tests in one build
+        PSK_TRY(env_choice(ctx, "PSK_CX_SIDE_KERNEL", {0, 1}, &side_on));
+        CxPlanKey key;
+        key.M = a.M; key.n_ov = x.n_ov; key.cap = scan_grid_cap(ctx); key.side_cap = cx_side_grid_cap(ctx);
+        memcpy(&key.thr_bits, &a.cut.thr, 8);
+        key.n1 = a.cut.n1; key.n0 = a.cut.n0; key.n_samples = ctx->n_samples;
+        key.min_samples = a.cut.min_samples; key.max_samples = a.cut.max_samples; key.side_kernel = side_on;
+        CxPlan &pl = ctx->cx_plan;
+        if (!pl.valid || !(pl.key == key)) {
+            pl.valid = false;
+            cx_plan(a.cut.n1, a.cut.n0, ctx->n_samples, a.cut.min_samples, a.cut.max_samples, a.cut.thr, &pl.class_mask, pl.corner);
+            pl.side = side_on && pl.class_mask == 0;
+            uint64_t rows_per_block;
+            if (pl.side) {
+                const cx_side_shape_t sh = cx_side_shape(x.n_ov, CL.cpr, key.side_cap);
+                pl.grid = sh.blocks; pl.slot_blocks = 0; pl.ov_blocks = sh.blocks;
+                rows_per_block = sh.rows_per_block;
+            } else {
+                x.class_mask = pl.class_mask;
+                pl.grid = cx_grid(ctx, x, CL.cpr).x;
+                pl.slot_blocks = x.slot_blocks; pl.ov_blocks = x.ov_blocks;
+                rows_per_block = cx_rows_per_block(x, CL.cpr);
+            }
+            pl.seg_cap = result_seg_cap(dim3(pl.grid), rows_per_block);
+            pl.key = key;
+            pl.valid = true;
+        }
+        x.class_mask = pl.class_mask; x.corner[0] = pl.corner[0]; x.corner[1] = pl.corner[1];
+        x.slot_blocks = pl.slot_blocks; x.ov_blocks = pl.ov_blocks;
+        CL.grid = dim3(pl.grid);
+        CL.side_kernel = pl.side;
         ctx->cx_last_plan = true;
-        ctx->cx_last_class_mask = x.class_mask;
-        ctx->cx_last_skipped = x.slot_blocks == 0;
-        return setup_results_rows(ctx, a, CL.grid, cx_rows_per_block(x, CL.cpr), set);
+        ctx->cx_last_class_mask = pl.class_mask;
+        ctx->cx_last_skipped = pl.slot_blocks == 0;
+        PSK_TRY(bind_results(ctx, a.sink, pl.seg_cap, set));
+        if (pl.side) {
+            CxSideArgs &sd = CL.side;
+            sd.ov = x.ov; sd.ov_row = x.ov_row; sd.n_ov = x.n_ov;
+            memcpy(sd.m1, a.m1_inl, sizeof(sd.m1));
+            memcpy(sd.m0, a.m0_inl, sizeof(sd.m0));
+            sd.cut = a.cut;
+            sd.sink = a.sink;
+        }
+        return PSK_OK;
     }
-    PSK_TRY(pick_chi2_mode(ctx, L.weighted, a.pcut, a.pcut_bonf, a.omit_B, &CL.mode));
+    PSK_TRY(pick_chi2_mode(ctx, L.weighted, a.cut.pcut, a.cut.pcut_bonf, a.cut.omit_B, &CL.mode));
     CL.grid = sh.grid;
     return setup_results(ctx, a, CL.grid, group_lanes(a), sh.unroll, set, sh.threads);
 }
@@ -696,6 +837,16 @@ extern "C" int psk_cx_plan(int n1, int n0, int n_samples, int min_samples, int m
 {
     if (n1 < 0 || n0 < 0 || n_samples < 0 || n1 + n0 > n_samples || !class_mask || !corner) return PSK_EINVAL;
     cx_plan(n1, n0, n_samples, min_samples, max_samples, thr, class_mask, corner);
+    return PSK_OK;
+}
+
+extern "C" int psk_cx_side_shape(uint64_t n_ov, int cpr, uint64_t cap_blocks, uint32_t *blocks, uint64_t *rows_per_block, uint32_t *batch_rows)
+{
+    if ((cpr != 1 && cpr != 2) || cap_blocks < 1 || cap_blocks > 0xffffffffull || !blocks || !rows_per_block) return PSK_EINVAL;
+    const cx_side_shape_t sh = cx_side_shape(n_ov, cpr, cap_blocks);
+    *blocks = sh.blocks;
+    *rows_per_block = sh.rows_per_block;
+    if (batch_rows) *batch_rows = sh.batch_rows;
     return PSK_OK;
 }
 

@@ -98,11 +98,13 @@ void compact_release(psk_ctx *ctx)
     dev_release(ctx->cx_ov_row);
     ctx->cx_valid = false;
     ctx->cx_n_ov = 0;
+    ctx->cx_plan.valid = false;
 }
 
 int compact_encode(psk_ctx *ctx)
 {
     ctx->cx_valid = false;
+    ctx->cx_plan.valid = false;   // the scan plan belongs to the matrix and its encoded copy
     const uint64_t M = ctx->n_kmers;
     const int n = ctx->n_samples, wpr = ctx->wpr;
     const bool trace = env_flag("PSK_TRACE");

@@ -98,15 +98,54 @@ struct ScanParams {  // what psk_rescan_timed needs to re-launch the last chi2 s
     double W1 = 0, W0 = 0;   // class weight totals
 };
 
+// Where a scan's survivors go (SoA arrays of SC_NSEG segments, scan_common.h) and how a segment's count is published:
+// part of every scan kernel's arguments.
+struct ScanSink {
+    uint64_t *res_row;
+    double *res_stat, *res_p, *res_mx, *res_my;
+    int32_t *res_nw;
+    uint32_t *counter;   // SC_NSEG slots, SC_CNT_STRIDE u32 apart: [0] appended entries, [1] finished workgroups
+    // end of a scan: the last workgroup of a segment (chi2) / the segment's finalize workgroup (Welch) publishes
+    // the segment's count to final_counts (device, compact) and host_counts (pinned host memory, written
+    // straight from the kernel) and zeroes the counter for the next scan -- no memset, no read-back copy
+    uint32_t *final_counts, *host_counts;
+    uint32_t seg_cap;    // entries per segment
+};
+
 // One of the two result sets of the scans.
 struct ScanSlot {
     DevBuf res;                      // SoA result arrays (setup_results)
+    ScanSink sink = {};              // ... as a kernel addresses them: laid out when `res` is reserved or seg_cap changes
+    bool sink_valid = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;   // around the scan's kernels
     hipEvent_t ev_export = nullptr;  // recorded on the caller's stream after an asynchronous export of this set
     bool export_pending = false;     // the next scan that writes this set waits for ev_export on the device
     bool in_flight = false;
     uint64_t seq = 0;                // launch order
     uint64_t seg_cap = 0;            // entries per result segment of the scan that wrote this set
+};
+
+// The plan of an exception-coded chi2 scan (assoc_scan.hip), kept from scan to scan: what cx_plan, the launch shape and
+// the result segments' size come to for `key`, which names everything they are a function of -- none of it derived from
+// WHICH samples are cases.  A scan with another key recomputes; a new matrix or encoded copy drops the plan.
+struct CxPlanKey {
+    uint64_t M = 0, n_ov = 0, cap = 0, side_cap = 0, thr_bits = 0;
+    int n1 = 0, n0 = 0, n_samples = 0, min_samples = 0, max_samples = 0, side_kernel = 0;
+    bool operator==(const CxPlanKey &o) const
+    {
+        return M == o.M && n_ov == o.n_ov && cap == o.cap && side_cap == o.side_cap && thr_bits == o.thr_bits && n1 == o.n1 &&
+               n0 == o.n0 && n_samples == o.n_samples && min_samples == o.min_samples && max_samples == o.max_samples &&
+               side_kernel == o.side_kernel;
+    }
+};
+struct CxPlan {
+    bool valid = false;
+    CxPlanKey key;
+    uint32_t class_mask = 0;
+    uint64_t corner[2] = {0, 0};
+    bool side = false;               // launched as chi2_scan_kernel_cx_side (no feasible class, PSK_CX_SIDE_KERNEL on)
+    uint32_t grid = 0, slot_blocks = 0, ov_blocks = 0;
+    uint64_t seg_cap = 0;            // entries per result segment
 };
 
 struct psk_ctx {
@@ -188,6 +227,7 @@ struct psk_ctx {
     // classes were feasible, and was the slot stream left unread (psk_last_scan_plan)
     bool cx_last_plan = false, cx_last_skipped = false;
     uint32_t cx_last_class_mask = 0;
+    CxPlan cx_plan;                  // dropped wherever the matrix or its encoded copy changes (compact_release, compact_encode, psk_begin)
 
     // scan state
     DevBuf mask1, phe, res_count, res_sorted;

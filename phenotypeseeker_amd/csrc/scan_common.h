@@ -34,6 +34,14 @@ constexpr int SC_CNT_STRIDE = 32;  // u32 per counter slot
 constexpr int SC_INL_WORDS = 16;   // mask words carried inside ScanArgs
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
+// What decides a row: the class sizes (popcounts of the masks), the frequency filter and the cut-offs.
+struct ScanCuts {
+    double pcut, pcut_bonf, thr;  // thr: statistic threshold of the division-free pre-test
+    int n1, n0;
+    int min_samples, max_samples;
+    int omit_B;
+};
+
 struct ScanArgs {
     const u32x4 *bits;
     uint64_t M;
@@ -48,49 +56,36 @@ struct ScanArgs {
     const float *lut6;         // f32 six-bit table of the same moments (row_moments_f32) -- candidate selection only
     double e0, e1, e2;         // ... and what its sums may be off by: |sum w| <= e0, |sum w u| <= e1, |sum w u^2| <= e2 (chi2: e0 = class 1, e1 = class 0)
     double eref;               // Welch: what the REFERENCE's own arithmetic may be off by in a group mean (it sums the raw, unshifted values)
-    int n1, n0;                // popcounts of the masks
     double W1, W0;             // weight totals of the two phenotype classes
     // t-test
     const uint64_t *mvalid;    // non-NA mask
     int nvalid;
-    // filters
-    int min_samples, max_samples;
-    double pcut, pcut_bonf, thr;  // thr: statistic threshold of the division-free pre-test
-    double tcrit;                 // t-test: |t| a row must exceed to be a candidate
-    int omit_B;
-    // output (SoA), counter
-    uint64_t *res_row;
-    double *res_stat, *res_p, *res_mx, *res_my;
-    int32_t *res_nw;
-    uint32_t *counter;   // SC_NSEG slots, SC_CNT_STRIDE u32 apart: [0] appended entries, [1] finished workgroups
-    uint32_t seg_cap;    // entries per segment
-    // end of a scan: the last workgroup of a segment (chi2) / the segment's finalize workgroup (Welch) publishes
-    // the segment's count to final_counts (device, compact) and host_counts (pinned host memory, written
-    // straight from the kernel) and zeroes the counter for the next scan -- no memset, no read-back copy
-    uint32_t *final_counts, *host_counts;
+    double tcrit;              // t-test: |t| a row must exceed to be a candidate
+    ScanCuts cut;              // class sizes, filters, cut-offs
+    ScanSink sink;             // output
     // phenotype masks of up to 1024 samples travel in the kernel arguments (no upload per scan)
     int inline_masks;
     uint64_t m1_inl[SC_INL_WORDS], m0_inl[SC_INL_WORDS];
 };
 
-__device__ __forceinline__ uint64_t reserve_slot(const ScanArgs &P)
+__device__ __forceinline__ uint64_t reserve_slot(const ScanSink &S)
 {
     const uint32_t seg = blockIdx.x & (SC_NSEG - 1);
-    const uint32_t idx = atomicAdd(&P.counter[seg * SC_CNT_STRIDE], 1u);
-    return (uint64_t)seg * P.seg_cap + (idx < P.seg_cap ? idx : P.seg_cap - 1);
+    const uint32_t idx = atomicAdd(&S.counter[seg * SC_CNT_STRIDE], 1u);
+    return (uint64_t)seg * S.seg_cap + (idx < S.seg_cap ? idx : S.seg_cap - 1);
 }
 
 // a candidate of a moment scan: (row, n_with) only -- the scan's second pass computes its statistic and decides
-__device__ __forceinline__ void append_candidate(const ScanArgs &P, uint64_t row, int n_w)
+__device__ __forceinline__ void append_candidate(const ScanSink &S, uint64_t row, int n_w)
 {
-    const uint64_t idx = reserve_slot(P);
-    P.res_row[idx] = row;
-    P.res_nw[idx] = n_w;
+    const uint64_t idx = reserve_slot(S);
+    S.res_row[idx] = row;
+    S.res_nw[idx] = n_w;
 }
 
 // Called by every thread at the very end of a chi2 scan workgroup: the LAST workgroup of a segment to get here
 // publishes the segment's count and re-arms the counter (ticket = second word of the counter's 128-byte line).
-__device__ __forceinline__ void publish_segment(const ScanArgs &P)
+__device__ __forceinline__ void publish_segment(const ScanSink &S)
 {
     // No fence: the count lives in device-scope atomics only, and every append of this workgroup has returned
     // its slot index (it was needed for the stores) before the barrier.  A __threadfence() here is an L2
@@ -99,12 +94,32 @@ __device__ __forceinline__ void publish_segment(const ScanArgs &P)
     if (threadIdx.x != 0) return;
     const uint32_t seg = blockIdx.x & (SC_NSEG - 1);
     const uint32_t n_blocks = (gridDim.x - seg + SC_NSEG - 1) / SC_NSEG;  // workgroups that map to this segment
-    uint32_t *slot = &P.counter[seg * SC_CNT_STRIDE];
+    uint32_t *slot = &S.counter[seg * SC_CNT_STRIDE];
     if (atomicAdd(slot + 1, 1u) == n_blocks - 1) {
         const uint32_t c = atomicExch(slot, 0u);
         slot[1] = 0;
-        P.final_counts[seg] = c;
-        P.host_counts[seg] = c;
+        S.final_counts[seg] = c;
+        S.host_counts[seg] = c;
+    }
+}
+
+// The same for a kernel whose workgroups end one atomic round trip sooner: the slot's two words are one aligned u64 (count
+// low, tickets high), and adding 1 << 32 returns both -- every append of the scan was counted before the last ticket,
+// so the last workgroup has the segment's count with its ticket and re-arms the slot with a plain store.  (The count
+// stays below 2^32: a scan has fewer rows.)  Interchangeable with publish_segment from launch to launch.
+__device__ __forceinline__ void publish_segment_once(const ScanSink &S)
+{
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    const uint32_t seg = blockIdx.x & (SC_NSEG - 1);
+    const uint32_t n_blocks = (gridDim.x - seg + SC_NSEG - 1) / SC_NSEG;  // workgroups that map to this segment
+    unsigned long long *slot = reinterpret_cast<unsigned long long *>(&S.counter[seg * SC_CNT_STRIDE]);
+    const unsigned long long old = atomicAdd(slot, 1ull << 32);
+    if ((uint32_t)(old >> 32) == n_blocks - 1) {
+        const uint32_t c = (uint32_t)old;
+        *slot = 0ull;
+        S.final_counts[seg] = c;
+        S.host_counts[seg] = c;
     }
 }
 
@@ -114,7 +129,9 @@ int mask_words(const psk_ctx *ctx);
 int group_lanes(const ScanArgs &a);
 uint64_t scan_grid_cap(const psk_ctx *ctx);
 dim3 scan_grid(const psk_ctx *ctx, uint64_t M, int G, int unroll, bool lut = false);
-int setup_results_rows(psk_ctx *ctx, ScanArgs &a, dim3 grid, uint64_t rows_per_block, int set);
+uint64_t result_seg_cap(dim3 grid, uint64_t rows_per_block);
+int bind_results(psk_ctx *ctx, ScanSink &s, uint64_t seg_cap, int set);
+int setup_results_rows(psk_ctx *ctx, ScanSink &s, dim3 grid, uint64_t rows_per_block, int set);
 int setup_results(psk_ctx *ctx, ScanArgs &a, dim3 grid, int G, int unroll, int set, int threads = SC_THREADS);
 int pick_result_set(psk_ctx *ctx, int *set_out, bool keep_results = false);
 int fetch_counts(psk_ctx *ctx, int set);

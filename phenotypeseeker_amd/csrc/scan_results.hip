@@ -20,39 +20,57 @@ int group_lanes(const ScanArgs &a)
 // result arrays (SoA) inside ctx->res: row u64 | stat f64 | p f64 | mx f64 | my f64 | nw i32, each
 // SC_NSEG * seg_cap entries; seg_cap bounds the rows the blocks of one segment can visit
 // (rows_per_block: the most rows one workgroup of the launch visits)
-int setup_results_rows(psk_ctx *ctx, ScanArgs &a, dim3 grid, uint64_t rows_per_block, int set)
+uint64_t result_seg_cap(dim3 grid, uint64_t rows_per_block)
 {
     const uint64_t blocks_per_seg = ((uint64_t)grid.x + SC_NSEG - 1) / SC_NSEG;
-    uint64_t seg_cap = blocks_per_seg * rows_per_block;
-    if (seg_cap < 64) seg_cap = 64;
+    const uint64_t seg_cap = blocks_per_seg * rows_per_block;
+    return seg_cap < 64 ? 64 : seg_cap;
+}
+
+// Result set `set` with segments of seg_cap entries, as a kernel addresses it.  The layout is worked out when the set's
+// buffer is reserved or seg_cap changes (the buffer only ever grows, and only here); a scan of the same shape copies it.
+int bind_results(psk_ctx *ctx, ScanSink &s, uint64_t seg_cap, int set)
+{
     if (seg_cap >= (1ull << 32)) return psk_fail(ctx, PSK_ERANGE, "result segment too large");
-    const uint64_t cap = seg_cap * SC_NSEG;
-    DevBuf &rb = ctx->slot[set].res;
-    PSK_TRY(dev_reserve(ctx, rb, cap * 44 + 64));
-    uint8_t *b = rb.as<uint8_t>();
-    a.res_row = reinterpret_cast<uint64_t *>(b);
-    a.res_stat = reinterpret_cast<double *>(b + cap * 8);
-    a.res_p = reinterpret_cast<double *>(b + cap * 16);
-    a.res_mx = reinterpret_cast<double *>(b + cap * 24);
-    a.res_my = reinterpret_cast<double *>(b + cap * 32);
-    a.res_nw = reinterpret_cast<int32_t *>(b + cap * 40);
-    if (!ctx->res_count.p) {  // counters re-arm themselves at the end of every scan: zeroed once
-        PSK_TRY(dev_reserve(ctx, ctx->res_count, (SC_NSEG * SC_CNT_STRIDE + 2 * SC_NSEG) * 4));
-        PSK_HIP(ctx, hipMemsetAsync(ctx->res_count.p, 0, (SC_NSEG * SC_CNT_STRIDE + 2 * SC_NSEG) * 4, ctx->stream));
+    ScanSlot &sl = ctx->slot[set];
+    if (!sl.sink_valid || sl.sink.seg_cap != (uint32_t)seg_cap) {
+        sl.sink_valid = false;
+        const uint64_t cap = seg_cap * SC_NSEG;
+        DevBuf &rb = sl.res;
+        PSK_TRY(dev_reserve(ctx, rb, cap * 44 + 64));
+        uint8_t *b = rb.as<uint8_t>();
+        ScanSink &a = sl.sink;
+        a.res_row = reinterpret_cast<uint64_t *>(b);
+        a.res_stat = reinterpret_cast<double *>(b + cap * 8);
+        a.res_p = reinterpret_cast<double *>(b + cap * 16);
+        a.res_mx = reinterpret_cast<double *>(b + cap * 24);
+        a.res_my = reinterpret_cast<double *>(b + cap * 32);
+        a.res_nw = reinterpret_cast<int32_t *>(b + cap * 40);
+        if (!ctx->res_count.p) {  // counters re-arm themselves at the end of every scan: zeroed once
+            PSK_TRY(dev_reserve(ctx, ctx->res_count, (SC_NSEG * SC_CNT_STRIDE + 2 * SC_NSEG) * 4));
+            PSK_HIP(ctx, hipMemsetAsync(ctx->res_count.p, 0, (SC_NSEG * SC_CNT_STRIDE + 2 * SC_NSEG) * 4, ctx->stream));
+        }
+        if (!ctx->cnt_pinned) {
+            PSK_HIP(ctx, hipHostMalloc(&ctx->cnt_pinned, 2 * SC_NSEG * 4, hipHostMallocDefault));
+            void *hc = nullptr;
+            PSK_HIP(ctx, hipHostGetDevicePointer(&hc, ctx->cnt_pinned, 0));
+            ctx->cnt_pinned_dev = static_cast<uint32_t *>(hc);
+        }
+        a.counter = ctx->res_count.as<uint32_t>();
+        a.final_counts = a.counter + SC_NSEG * SC_CNT_STRIDE + set * SC_NSEG;  // one compact array per result set
+        a.host_counts = ctx->cnt_pinned_dev + set * SC_NSEG;
+        a.seg_cap = (uint32_t)seg_cap;
+        sl.sink_valid = true;
     }
-    if (!ctx->cnt_pinned) {
-        PSK_HIP(ctx, hipHostMalloc(&ctx->cnt_pinned, 2 * SC_NSEG * 4, hipHostMallocDefault));
-        void *hc = nullptr;
-        PSK_HIP(ctx, hipHostGetDevicePointer(&hc, ctx->cnt_pinned, 0));
-        ctx->cnt_pinned_dev = static_cast<uint32_t *>(hc);
-    }
-    a.counter = ctx->res_count.as<uint32_t>();
-    a.final_counts = a.counter + SC_NSEG * SC_CNT_STRIDE + set * SC_NSEG;  // one compact array per result set
-    a.host_counts = ctx->cnt_pinned_dev + set * SC_NSEG;
-    a.seg_cap = (uint32_t)seg_cap;
-    ctx->slot[set].seg_cap = seg_cap;
+    s = sl.sink;
+    sl.seg_cap = seg_cap;
     if (set == ctx->res_set) ctx->results_valid = false;  // the last ended scan's results are about to go
     return PSK_OK;
+}
+
+int setup_results_rows(psk_ctx *ctx, ScanSink &s, dim3 grid, uint64_t rows_per_block, int set)
+{
+    return bind_results(ctx, s, result_seg_cap(grid, rows_per_block), set);
 }
 
 int setup_results(psk_ctx *ctx, ScanArgs &a, dim3 grid, int G, int unroll, int set, int threads)
@@ -61,7 +79,7 @@ int setup_results(psk_ctx *ctx, ScanArgs &a, dim3 grid, int G, int unroll, int s
     const uint64_t n_steps = (a.M + rpw - 1) / rpw;
     const uint64_t total_waves = (uint64_t)grid.x * (threads / 64);
     const uint64_t iters = (n_steps + total_waves * unroll - 1) / (total_waves * unroll);
-    return setup_results_rows(ctx, a, grid, (threads / 64) * iters * unroll * rpw, set);
+    return setup_results_rows(ctx, a.sink, grid, (threads / 64) * iters * unroll * rpw, set);
 }
 
 // per-segment counts of the scan that wrote result set `set`, as its kernels left them in pinned host memory (after

@@ -87,7 +87,7 @@ __global__ __launch_bounds__(LUT ? SC_LUT_THREADS : SC_THREADS) void ttest_scan_
         else row_moments<NM, HALF>(sc_row_ptr<HALF>(P, r), P.cpr, (cdptr)P.tab, mo);
         if (!act) return;
         const double nx = WT ? mo[0] : (double)r_nw, sx = mo[NM - 2], qx = mo[NM - 1];
-        const double ny = P.W1 - nx, sy = P.W0 - sx, qy = P.thr - qx;  // totals: W1 = sum w, W0 = sum w*u, thr = sum w*u^2
+        const double ny = P.W1 - nx, sy = P.W0 - sx, qy = P.cut.thr - qx;  // totals: W1 = sum w, W0 = sum w*u, thr = sum w*u^2
         if (F32) {
             // the sums are f32 sums, off by at most e0 (sum w; 0 with unit weights: the popcount), e1 (sum w u), e2 (sum w u^2):
             // an UPPER bound of |t| -- the largest difference of the means over the smallest standard error the bounds
@@ -104,7 +104,7 @@ __global__ __launch_bounds__(LUT ? SC_LUT_THREADS : SC_THREADS) void ttest_scan_
                 const double sem = vx / (nxh - 1.0) + vy / (nyh - 1.0);
                 cand = !(sem > 0.0) || !(dmax / sqrt(sem) <= P.tcrit);
             }
-            if (cand) append_candidate(P, r, r_nw);
+            if (cand) append_candidate(P.sink, r, r_nw);
             return;
         }
         const double dx = sx / nx, dy = sy / ny;              // group means minus mu
@@ -117,12 +117,12 @@ __global__ __launch_bounds__(LUT ? SC_LUT_THREADS : SC_THREADS) void ttest_scan_
         // sums differ from the sample-order ones) cannot pass.  Candidates are stored as (row, n_with) only:
         // ttest_finalize_kernel sums their moments again in the reference's order and decides (keeps erfc /
         // incomplete-beta code, and its ~90 VGPRs, out of this kernel).
-        if (!(fabs(tstat) + 2.0 * P.eref / sqrt(semsum) <= P.tcrit)) append_candidate(P, r, r_nw);   // eref: see ScanArgs; NaN: the exact pass drops it
+        if (!(fabs(tstat) + 2.0 * P.eref / sqrt(semsum) <= P.tcrit)) append_candidate(P.sink, r, r_nw);   // eref: see ScanArgs; NaN: the exact pass drops it
     };
 
     auto on_row = [&](uint64_t row, const uint32_t (&cnt)[1], bool lead) {
         const int n_w = (int)cnt[0], n_wo = P.nvalid - (int)cnt[0];
-        const bool freq_ok = (row < P.M) && !(n_w < P.min_samples || n_wo < 2 || n_w > P.max_samples);
+        const bool freq_ok = (row < P.M) && !(n_w < P.cut.min_samples || n_wo < 2 || n_w > P.cut.max_samples);
         Q.n = queue_rows(freq_ok && lead, row, make_int2(n_w, 0), Q.row, Q.val, Q.n, lane);
     };
     stream_rows<G, LUT>(P, mk, Q, on_row, process);
@@ -145,15 +145,15 @@ __global__ __launch_bounds__(SC_FIN_THREADS) void ttest_finalize_kernel(const Sc
     __shared__ uint32_t s_out;
     __shared__ double2 s_tab[SC_FIN_BLK * 128];   // pass 1: {weight, weight * value}, pass 2: {weight, value} of the samples of the current block (broadcast reads)
     const uint32_t seg = blockIdx.x;
-    const uint32_t c = P.counter[seg * SC_CNT_STRIDE];
-    const uint64_t base = (uint64_t)seg * P.seg_cap;
+    const uint32_t c = P.sink.counter[seg * SC_CNT_STRIDE];
+    const uint64_t base = (uint64_t)seg * P.sink.seg_cap;
     if (threadIdx.x == 0) s_out = 0;
     __syncthreads();
     for (uint32_t s0 = 0; s0 < c; s0 += SC_FIN_THREADS) {
         const uint32_t i = s0 + threadIdx.x;
         const bool valid = i < c;
-        const uint64_t row = valid ? P.res_row[base + i] : 0;
-        const int32_t nw = valid ? P.res_nw[base + i] : 0;
+        const uint64_t row = valid ? P.sink.res_row[base + i] : 0;
+        const int32_t nw = valid ? P.sink.res_nw[base + i] : 0;
         const bool wave_any = __any(valid);
         const u32x4 *rp = P.half ? sc_row_ptr<true>(P, row) : sc_row_ptr<false>(P, row);
         // One lane walks its candidate's 2 x n_samples dependent additions (rocprof, r03: 82 us at 1,024 samples whatever the
@@ -219,23 +219,23 @@ __global__ __launch_bounds__(SC_FIN_THREADS) void ttest_finalize_kernel(const Sc
             const double z1 = (sem1 / semsum) * (sem1 / semsum) / (nx - 1.0);
             const double z2 = (sem2 / semsum) * (sem2 / semsum) / (ny - 1.0);
             p = dev_t_two_sided_p(tstat, 1.0 / (z1 + z2));
-            keep = p < P.pcut_bonf;
+            keep = p < P.cut.pcut_bonf;
         }
         uint32_t tot;
         const uint32_t pos = psk_block_excl_scan_u32<SC_FIN_THREADS>(keep ? 1u : 0u, &tot, scan_lds);  // barriers inside
         const uint32_t out = s_out;
         if (keep) {
             const uint64_t o = base + out + pos;  // <= base + i: compaction only moves entries down
-            P.res_row[o] = row; P.res_stat[o] = tstat; P.res_p[o] = p; P.res_mx[o] = mx; P.res_my[o] = my; P.res_nw[o] = nw;
+            P.sink.res_row[o] = row; P.sink.res_stat[o] = tstat; P.sink.res_p[o] = p; P.sink.res_mx[o] = mx; P.sink.res_my[o] = my; P.sink.res_nw[o] = nw;
         }
         __syncthreads();
         if (threadIdx.x == 0) s_out = out + tot;
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        P.counter[seg * SC_CNT_STRIDE] = 0;  // re-armed for the next scan
-        P.final_counts[seg] = s_out;
-        P.host_counts[seg] = s_out;
+        P.sink.counter[seg * SC_CNT_STRIDE] = 0;  // re-armed for the next scan
+        P.sink.final_counts[seg] = s_out;
+        P.sink.host_counts[seg] = s_out;
     }
 }
 
@@ -310,13 +310,13 @@ template <bool WT>
 __global__ __launch_bounds__(256) void ttest_means_kernel(const ScanArgs P)
 {
     const uint32_t seg = blockIdx.x;
-    const uint32_t c = min(P.final_counts[seg], P.seg_cap);   // (an overflowed segment is refused by fetch_counts)
-    const uint64_t base = (uint64_t)seg * P.seg_cap;
+    const uint32_t c = min(P.sink.final_counts[seg], P.sink.seg_cap);   // (an overflowed segment is refused by fetch_counts)
+    const uint64_t base = (uint64_t)seg * P.sink.seg_cap;
     const double2 *raw = reinterpret_cast<const double2 *>(P.raw);   // {weight, value}; NA: {0, 0}
     const int words = P.half ? 1 : 2 * P.cpr;
     for (uint32_t i = threadIdx.x; i < c; i += blockDim.x) {
-        const uint64_t row = P.res_row[base + i];
-        const int nw = P.res_nw[base + i];
+        const uint64_t row = P.sink.res_row[base + i];
+        const int nw = P.sink.res_nw[base + i];
         const uint64_t *rp = reinterpret_cast<const uint64_t *>(P.bits) + row * (uint64_t)words;
         NpSum sx, sy, wx, wy;
         np_begin(sx, nw);
@@ -331,8 +331,8 @@ __global__ __launch_bounds__(256) void ttest_means_kernel(const ScanArgs P)
                 else { np_add(sy, t.y * t.x); if (WT) np_add(wy, t.x); }
             }
         }
-        P.res_mx[base + i] = sx.tot / (WT ? wx.tot : (double)nw);
-        P.res_my[base + i] = sy.tot / (WT ? wy.tot : (double)(P.nvalid - nw));
+        P.sink.res_mx[base + i] = sx.tot / (WT ? wx.tot : (double)nw);
+        P.sink.res_my[base + i] = sy.tot / (WT ? wy.tot : (double)(P.nvalid - nw));
     }
 }
 
@@ -567,12 +567,12 @@ extern "C" int psk_ttest_scan(psk_ctx *ctx, const double *pheno, const uint8_t *
     a.tab = ctx->phe.as<double>();
     a.raw = a.tab + T.raw_off;
     a.nvalid = T.nvalid;
-    a.min_samples = min_samples;
-    a.max_samples = max_samples;
-    a.pcut = pvalue_cutoff;
-    a.pcut_bonf = pvalue_cutoff / (double)n_kmers_global;
-    a.W1 = T.tot_w; a.W0 = T.tot_wu; a.thr = T.tot_wuu;  // totals over the non-NA samples (shifted values)
-    a.tcrit = welch_tcrit(a.pcut_bonf);
+    a.cut.min_samples = min_samples;
+    a.cut.max_samples = max_samples;
+    a.cut.pcut = pvalue_cutoff;
+    a.cut.pcut_bonf = pvalue_cutoff / (double)n_kmers_global;
+    a.W1 = T.tot_w; a.W0 = T.tot_wu; a.cut.thr = T.tot_wuu;  // totals over the non-NA samples (shifted values)
+    a.tcrit = welch_tcrit(a.cut.pcut_bonf);
     int set = 0;
     PSK_TRY(pick_result_set(ctx, &set));
     a.eref = 4.0 * (double)N * 1.1102230246251565e-16 * T.max_abs_v * T.scale;   // in the kernel's (shifted, scaled) units
