@@ -10,6 +10,7 @@
 #include <atomic>
 
 #include "count_plan.h"
+#include "gz_plan.h"
 #include "psk_internal.h"
 #include "stage_pipeline.h"
 

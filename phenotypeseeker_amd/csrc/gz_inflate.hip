@@ -17,7 +17,7 @@
 //                         chunk's start, counting the text and the matches it would write.  (A false positive of step 1
 //                         never coincides with anything: the host's walk along the links from the true start of the
 //                         member drops it, and the chunk before it simply runs on.)
-//   3. host               the chain of chunks of every file, their places in the text; further members (cat a.gz b.gz:
+//   3. host (gz_plan.h)   the chain of chunks of every file, their places in the text; further members (cat a.gz b.gz:
 //                         one more round of step 2 per member the search did not happen on; BGZF members are found by
 //                         their BSIZE fields without any search); ISIZE checked.
 //   4. gz_decode_kernel<true>    the same decode, now writing: literals as 16-bit symbols where they belong, matches as
@@ -35,6 +35,7 @@
 // -- what glistmaker does --, and so does a member the device declines (a block that runs on for megabytes without a dynamic
 // header, more members than the rounds allowed here, corrupt data: zlib then words the error).
 #include "dev_utils.h"
+#include "gz_plan.h"
 #include "psk_internal.h"
 
 #include <sys/mman.h>
@@ -50,10 +51,6 @@
 #include <vector>
 
 namespace {
-
-constexpr uint64_t GZ_NONE = ~0ull;
-constexpr int GZ_FINAL = -1, GZ_ERROR = -2, GZ_OVERRUN = -3, GZ_STOP = -5;
-constexpr int GZ_WIN = 32768;
 
 // ---- the bit stream: 32-bit aligned loads into a 64-bit buffer, at least 32 valid bits after need32() ------------
 struct BitIn {
@@ -1158,68 +1155,7 @@ __global__ __launch_bounds__(256) void gz_guard_check_kernel(GzGuardBands g, uin
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------
-struct GzMemberHead {
-    size_t deflate_at = 0;   // offset of the DEFLATE data in the file
-    uint32_t bsize = 0;      // BGZF: length of the whole member (0: not a BGZF member)
-};
-
-// RFC 1952 2.3; false: no gzip member starts at `at`
-bool gz_parse_member_header(const uint8_t *d, size_t n, size_t at, GzMemberHead *h)
-{
-    if (at + 18 > n || d[at] != 0x1f || d[at + 1] != 0x8b || d[at + 2] != 8) return false;
-    const uint8_t flg = d[at + 3];
-    if (flg & 0xe0) return false;
-    size_t p = at + 10;
-    h->bsize = 0;
-    if (flg & 4) {
-        if (p + 2 > n) return false;
-        const size_t xlen = d[p] | (d[p + 1] << 8);
-        p += 2;
-        if (p + xlen > n) return false;
-        for (size_t q = p; q + 4 <= p + xlen;) {
-            const size_t sl = d[q + 2] | (d[q + 3] << 8);
-            if (d[q] == 'B' && d[q + 1] == 'C' && sl == 2 && q + 6 <= p + xlen) h->bsize = (uint32_t)(d[q + 4] | (d[q + 5] << 8)) + 1;
-            q += 4 + sl;
-        }
-        p += xlen;
-    }
-    if (flg & 8) {
-        while (p < n && d[p]) p++;
-        p++;
-    }
-    if (flg & 16) {
-        while (p < n && d[p]) p++;
-        p++;
-    }
-    if (flg & 2) p += 2;
-    if (p + 8 > n) return false;
-    h->deflate_at = p;
-    return true;
-}
-
-uint32_t gz_le32(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
-
-struct GzChunk {
-    int file;
-    uint64_t start_bit;   // in the device image (GZ_NONE until found)
-    uint64_t seek_from, seek_to;   // bits: where gz_find_kernel looks (seek_from == seek_to: the start is known)
-    bool true_start;
-    // results of the counting pass
-    uint64_t out_len = 0, n_rec = 0, end_bit = 0;
-    int32_t link = GZ_ERROR;
-    bool counted = false;
-};
-
-struct GzFile {
-    const uint8_t *data;
-    size_t size;
-    uint64_t at;          // offset of the image in the device buffer
-    bool bgzf = false;
-    bool device_ok = true;
-    std::vector<int> chain;      // its chunks in stream order
-    uint64_t out_off = 0, out_len = 0;
-    int nul_slot = -1;    // its entry of the writing pass's per-file tables
-};
+// (what needs no device -- the chunks, the candidate starts, the walk along the links, the layout of the text -- is gz_plan.h)
 
 // zlib, every member of the file (what gzip.decompress and glistmaker's reader do); false: *err says why not
 bool gz_host_inflate(const uint8_t *d, size_t n, std::vector<uint8_t> &out, std::string *err)
@@ -1263,18 +1199,464 @@ bool gz_host_inflate(const uint8_t *d, size_t n, std::vector<uint8_t> &out, std:
     return true;
 }
 
-}  // namespace
-
-// Where the images of a group lie in its device buffer (16-byte aligned, at least 16 zero bytes behind each); returns its size.
-uint64_t gz_image_layout(int n, const size_t *sizes, uint64_t *at)
+// zlib over the files `which` names, one file a thread of a pool of host_threads (the first error, in file order, is the call's)
+int gz_host_route(psk_ctx *ctx, const uint8_t *const *data, const size_t *sizes, const std::vector<int> &which, int host_threads, std::vector<GzInflated> &res)
 {
-    uint64_t total = 0;
-    for (int i = 0; i < n; i++) {
-        at[i] = total;
-        total += (sizes[i] + 16 + 15) & ~(size_t)15;
-    }
-    return total + 64;
+    const int nw = (int)which.size();
+    std::atomic<int> next(0), bad(0);
+    std::vector<std::string> errs((size_t)nw);
+    auto work = [&]() {
+        for (;;) {
+            const int j = next.fetch_add(1);
+            if (j >= nw) return;
+            GzInflated &r = res[(size_t)which[(size_t)j]];
+            if (!gz_host_inflate(data[which[(size_t)j]], sizes[which[(size_t)j]], r.host, &errs[(size_t)j])) {
+                bad = 1;
+                r.error = errs[(size_t)j];   // (every file is tried: psk_gz_inflate reports per file)
+                r.host.clear();
+            }
+            r.len = r.host.size();
+        }
+    };
+    std::vector<std::thread> pool;
+    const int nt = host_threads < 1 ? 1 : (host_threads > 32 ? 32 : host_threads);
+    for (int t = 1; t < nt && t < nw; t++) pool.emplace_back(work);
+    work();
+    for (auto &t : pool) t.join();
+    if (bad)
+        for (int j = 0; j < nw; j++)
+            if (!errs[(size_t)j].empty()) return psk_fail(ctx, PSK_EINVAL, "%s", errs[(size_t)j].c_str());
+    return PSK_OK;
 }
+
+// The device tables of one pass, carved out of tab_buf: typed columns, each rounded up to 256 bytes.  The pass's inputs come
+// first -- only they have a host image (`stage`) and are uploaded --, what the kernels write lies behind inputs_end().
+template <class T>
+struct GzCol {
+    size_t off = 0, n = 0;
+};
+struct GzTables {
+    std::vector<uint8_t> &stage;
+    size_t bytes = 0, in_bytes = 0;
+    uint8_t *base = nullptr;
+    explicit GzTables(std::vector<uint8_t> &s) : stage(s) {}
+    template <class T> GzCol<T> add(size_t n)
+    {
+        const GzCol<T> c{bytes, n};
+        bytes += (n * sizeof(T) + 255) & ~(size_t)255;
+        return c;
+    }
+    void inputs_end() { in_bytes = bytes; }
+    int reserve(psk_ctx *ctx, DevBuf &tab_buf)   // every column has been added: from here on host() and dev() hold
+    {
+        PSK_TRY(dev_reserve(ctx, tab_buf, bytes));
+        base = tab_buf.as<uint8_t>();
+        stage.assign(in_bytes, 0);
+        return PSK_OK;
+    }
+    template <class T> T *host(GzCol<T> c) { return reinterpret_cast<T *>(stage.data() + c.off); }
+    template <class T> T *dev(GzCol<T> c) const { return reinterpret_cast<T *>(base + c.off); }
+    int upload(psk_ctx *ctx, hipStream_t st)
+    {
+        PSK_HIP(ctx, hipMemcpyAsync(base, stage.data(), in_bytes, hipMemcpyHostToDevice, st));
+        return PSK_OK;
+    }
+    template <class T> int fetch(psk_ctx *ctx, hipStream_t st, GzCol<T> c, std::vector<T> &to) const   // (queued: the caller waits)
+    {
+        to.resize(c.n);
+        PSK_HIP(ctx, hipMemcpyAsync(to.data(), dev(c), c.n * sizeof(T), hipMemcpyDeviceToHost, st));
+        return PSK_OK;
+    }
+};
+
+// what the counting and the writing pass have in common: per chunk its start, its file's end, the member-start flag; the results
+struct GzDecodeCols {
+    GzCol<uint64_t> start, end;
+    GzCol<uint8_t> is_true;
+    GzCol<uint64_t> out_len, n_rec, end_bit;
+    GzCol<int32_t> link;
+    GzCol<uint16_t> long_syms;
+    void inputs(GzTables &t, size_t m)
+    {
+        start = t.add<uint64_t>(m);
+        end = t.add<uint64_t>(m);
+        is_true = t.add<uint8_t>(m);
+    }
+    void outputs(GzTables &t, size_t m)
+    {
+        out_len = t.add<uint64_t>(m);
+        n_rec = t.add<uint64_t>(m);
+        end_bit = t.add<uint64_t>(m);
+        link = t.add<int32_t>(m);
+        long_syms = t.add<uint16_t>(m * 320);
+    }
+    void fill(GzTables &t, const GzPlan &p, const std::vector<int> &which) const
+    {
+        for (size_t j = 0; j < which.size(); j++) {
+            const GzChunk &c = p.ch[(size_t)which[j]];
+            const GzFile &f = p.files[(size_t)c.file];
+            t.host(start)[j] = f.device_ok ? c.start_bit : GZ_NONE;
+            t.host(end)[j] = f.at + f.size;
+            t.host(is_true)[j] = c.true_start ? 1 : 0;
+        }
+    }
+    // the arguments both passes share; the pass adds its own
+    GzDecodeArgs args(const GzTables &t, const uint8_t *comp, size_t m) const
+    {
+        GzDecodeArgs a;
+        std::memset(&a, 0, sizeof a);
+        a.comp = comp;
+        a.start_bit = t.dev(start);
+        a.end_byte = t.dev(end);
+        a.true_start = t.dev(is_true);
+        a.long_syms = t.dev(long_syms);
+        a.out_len = t.dev(out_len);
+        a.n_rec = t.dev(n_rec);
+        a.end_bit = t.dev(end_bit);
+        a.link = t.dev(link);
+        a.n = (int)m;
+        return a;
+    }
+};
+
+struct GzWriteCols {
+    GzDecodeCols d;
+    GzCol<uint64_t> stop, out_off, want_len, rec_off, want_rec;
+    GzCol<uint32_t> file_first, chunk_file;
+    GzCol<unsigned long long> nul;   // per file: where its text has its first NUL (in out_buf), ~0: nowhere
+    GzCol<uint8_t> no_window;
+    GzCol<uint64_t> m_begin, m_len;   // the CRC pass's
+    GzCol<uint32_t> m_acc;
+    GzCol<uint32_t> damaged;          // the guard check's
+};
+
+struct GzKnobs {
+    size_t lanes = 65536, chunk = 0;   // lanes: four waves on each of 256 CUs; chunk 0: from the lanes
+    int max_rounds = 24;
+    // how far ONE lane may decode without meeting a found start.  A lane decodes ~1.4 MB of compressed input a second (65,536 of them:
+    // 1.9 GB in 21 ms), so this is the bound on what a file with no dynamic block headers -- stored or fixed-code blocks only, or one
+    // crafted to look so -- can cost the call before zlib gets it: 1 MiB = 0.75 s (r05: 8 MiB = 6 s, and again in every round of a
+    // file of several such members).  Blocks of the usual encoders end far sooner (zlib: tens of KB; pigz 128 KB; libdeflate <= ~300 KB).
+    size_t max_span = 1 << 20;
+    int read(psk_ctx *ctx)
+    {
+        PSK_TRY(env_int(ctx, "PSK_GZ_LANES", 1, 1 << 30, &lanes));
+        PSK_TRY(env_int(ctx, "PSK_GZ_CHUNK", 0, 1ll << 40, &chunk));
+        PSK_TRY(env_int(ctx, "PSK_GZ_ROUNDS", 0, 1 << 20, &max_rounds));
+        return env_int(ctx, "PSK_GZ_MAX_SPAN", 0, 1ll << 40, &max_span);
+    }
+};
+
+// the PSK_TRACE line's milliseconds per phase (a lap waits for the stream: only when tracing)
+struct GzLaps {
+    bool on = false;
+    hipStream_t st = nullptr;
+    std::chrono::steady_clock::time_point last;
+    std::string phases;
+    void lap(const char *what)
+    {
+        if (!on) return;
+        (void)hipStreamSynchronize(st);
+        const auto now = std::chrono::steady_clock::now();
+        char buf[96];
+        std::snprintf(buf, sizeof buf, " %s %.1f", what, std::chrono::duration<double, std::milli>(now - last).count());
+        phases += buf;
+        last = now;
+    }
+};
+
+// the counters of gz_copy_kernel (PSK_GZ_STATS), freed on every way out
+struct GzCopyStats {
+    unsigned long long *d = nullptr;
+    ~GzCopyStats() { if (d) (void)hipFree(d); }
+};
+
+// One group on the device route: the steps of the header comment, in its order.
+struct GzGroup {
+    psk_ctx *ctx;
+    hipStream_t st;
+    DevBuf &comp_buf, &sym_buf, &rec_buf, &out_buf, &tab_buf;
+    GzKnobs knobs;
+    size_t chunk = 0;
+    GzPlan plan;
+    GzLaps laps;
+    int rounds = 0;
+    std::vector<uint8_t> stage;   // host image of a pass's input tables
+    const uint8_t *d_comp = nullptr;
+    // the writing pass
+    size_t guard = 0;
+    uint16_t *d_sym = nullptr;
+    uint8_t *d_text = nullptr;
+    uint2 *d_rec = nullptr;
+    GzGuardBands bands;
+    GzTables wt{stage};
+    GzWriteCols w;
+    GzDecodeArgs wa;
+    std::vector<unsigned long long> nul_at;
+    std::vector<uint32_t> crc_got;
+    std::vector<int32_t> w_link;
+    uint32_t guard_damage = 0;
+    bool check_crc = false;
+
+    int upload(bool images_uploaded);
+    int find();                               // step 1
+    int count_rounds();                       // steps 2 + 3
+    int reserve_text(const GzTextLayout &L);
+    int write_text(const GzTextLayout &L);    // steps 4 + 5
+    int check_sums(const GzTextLayout &L);    // step 6
+    int settle(const GzTextLayout &L);        // the guard bands; what the writing pass and the check sums say about each file
+    std::vector<int> results(std::vector<GzInflated> &res) const;
+};
+
+int GzGroup::upload(bool images_uploaded)
+{
+    if (!images_uploaded) {   // (the counting calls upload each image as soon as it is read: gz_image_layout says where)
+        PSK_TRY(dev_reserve(ctx, comp_buf, plan.comp_total));
+        PSK_HIP(ctx, hipMemsetAsync(comp_buf.p, 0, plan.comp_total, st));
+        for (const GzFile &f : plan.files)
+            if (f.device_ok && f.size) PSK_HIP(ctx, hipMemcpyAsync(comp_buf.as<uint8_t>() + f.at, f.data, f.size, hipMemcpyHostToDevice, st));
+    }
+    d_comp = comp_buf.as<uint8_t>();
+    laps.lap("upload");
+    return PSK_OK;
+}
+
+int GzGroup::find()
+{
+    std::vector<int> seek;
+    for (size_t c = 0; c < plan.ch.size(); c++)
+        if (plan.ch[c].seek_to > plan.ch[c].seek_from) seek.push_back((int)c);
+    if (!seek.empty()) {
+        const size_t m = seek.size();
+        GzTables t(stage);
+        const auto from = t.add<uint64_t>(m), to = t.add<uint64_t>(m), end = t.add<uint64_t>(m);
+        t.inputs_end();
+        const auto found = t.add<uint64_t>(m);
+        PSK_TRY(t.reserve(ctx, tab_buf));
+        for (size_t j = 0; j < m; j++) {
+            const GzChunk &c = plan.ch[(size_t)seek[j]];
+            t.host(from)[j] = c.seek_from;
+            t.host(to)[j] = c.seek_to;
+            t.host(end)[j] = plan.files[(size_t)c.file].at + plan.files[(size_t)c.file].size;
+        }
+        PSK_TRY(t.upload(ctx, st));
+        gz_find_kernel<<<dim3((unsigned)m), dim3(64), 0, st>>>(d_comp, t.dev(from), t.dev(to), t.dev(end), (int)m, t.dev(found));
+        PSK_HIP(ctx, hipGetLastError());
+        std::vector<uint64_t> got;
+        PSK_TRY(t.fetch(ctx, st, found, got));
+        PSK_HIP(ctx, hipStreamSynchronize(st));
+        for (size_t j = 0; j < m; j++) plan.ch[(size_t)seek[j]].start_bit = got[j];
+    }
+    laps.lap("find");
+    return PSK_OK;
+}
+
+// counting passes until every file's chain reaches its end
+int GzGroup::count_rounds()
+{
+    const uint64_t max_span_bits = (uint64_t)std::max<size_t>(chunk * 8, knobs.max_span) * 8;
+    GzCands cands;
+    std::vector<uint64_t> r_len, r_nrec, r_ebit;
+    std::vector<int32_t> r_link;
+    while (!plan.todo.empty()) {
+        if (++rounds > knobs.max_rounds) {
+            gz_decline_unfinished(plan);
+            break;
+        }
+        cands.rebuild(plan);
+        const size_t m = plan.todo.size();
+        GzTables t(stage);
+        GzDecodeCols d;
+        d.inputs(t, m);
+        const auto cand_from = t.add<uint32_t>(m), cand_to = t.add<uint32_t>(m);
+        const auto cand_bit = t.add<uint64_t>(cands.bit.size() + 1);
+        t.inputs_end();
+        d.outputs(t, m);
+        PSK_TRY(t.reserve(ctx, tab_buf));
+        d.fill(t, plan, plan.todo);
+        for (size_t j = 0; j < m; j++) {
+            const auto r = cands.range(plan.ch[(size_t)plan.todo[j]]);
+            t.host(cand_from)[j] = r.first;
+            t.host(cand_to)[j] = r.second;
+        }
+        if (!cands.bit.empty()) std::memcpy(t.host(cand_bit), cands.bit.data(), cands.bit.size() * 8);
+        PSK_TRY(t.upload(ctx, st));
+        GzDecodeArgs a = d.args(t, d_comp, m);
+        a.cand_bit = t.dev(cand_bit);
+        a.cand_from = t.dev(cand_from);
+        a.cand_to = t.dev(cand_to);
+        a.max_span_bits = max_span_bits;
+        PSK_HIP(ctx, hipMemsetAsync(a.link, 0xfe, m * 4, st));   // (a chunk without a start keeps a negative link)
+        gz_decode_kernel<false><<<dim3((unsigned)div_up((uint64_t)m, 64)), dim3(64), GZ_LDS_U16 * 2, st>>>(a);
+        PSK_HIP(ctx, hipGetLastError());
+        PSK_TRY(t.fetch(ctx, st, d.out_len, r_len));
+        PSK_TRY(t.fetch(ctx, st, d.n_rec, r_nrec));
+        PSK_TRY(t.fetch(ctx, st, d.end_bit, r_ebit));
+        PSK_TRY(t.fetch(ctx, st, d.link, r_link));
+        PSK_HIP(ctx, hipStreamSynchronize(st));
+        gz_apply_round(plan, cands, r_len.data(), r_nrec.data(), r_ebit.data(), r_link.data());
+        gz_walk_chains(plan);
+    }
+    laps.lap("count");
+    return PSK_OK;
+}
+
+// the text, symbol and match buffers, with the guard bands around them when asked for
+int GzGroup::reserve_text(const GzTextLayout &L)
+{
+    guard = env_flag("PSK_GZ_GUARD") ? GZ_GUARD : 0;
+    PSK_TRY(dev_reserve(ctx, sym_buf, L.total * 2 + 64 + 2 * guard));
+    PSK_TRY(dev_reserve(ctx, out_buf, L.total + 64 + 2 * guard));
+    PSK_TRY(dev_reserve(ctx, rec_buf, L.total_rec * 8 + 64 + 2 * guard));
+    // (the buffers proper start behind the leading band; the 64 bytes of slack the wide loads may touch stay in front of the trailing one)
+    d_sym = reinterpret_cast<uint16_t *>(sym_buf.as<uint8_t>() + guard);
+    d_text = out_buf.as<uint8_t>() + guard;
+    d_rec = reinterpret_cast<uint2 *>(rec_buf.as<uint8_t>() + guard);
+    if (guard) {
+        uint8_t *b[6] = {sym_buf.as<uint8_t>(), sym_buf.as<uint8_t>() + guard + L.total * 2 + 64, out_buf.as<uint8_t>(), out_buf.as<uint8_t>() + guard + L.total + 64,
+                         rec_buf.as<uint8_t>(), rec_buf.as<uint8_t>() + guard + L.total_rec * 8 + 64};
+        for (int q = 0; q < 6; q++) {
+            bands.band[q] = b[q];
+            PSK_HIP(ctx, hipMemsetAsync(b[q], GZ_GUARD_BYTE, guard, st));
+        }
+    }
+    laps.lap("buffers");
+    return PSK_OK;
+}
+
+int GzGroup::write_text(const GzTextLayout &L)
+{
+    const size_t m = L.order.size(), nf = L.file_first.size(), nm = L.m_begin.size();
+    w.d.inputs(wt, m);
+    w.stop = wt.add<uint64_t>(m);
+    w.out_off = wt.add<uint64_t>(m);
+    w.want_len = wt.add<uint64_t>(m);
+    w.rec_off = wt.add<uint64_t>(m);
+    w.want_rec = wt.add<uint64_t>(m);
+    w.file_first = wt.add<uint32_t>(nf);
+    w.chunk_file = wt.add<uint32_t>(m);
+    w.nul = wt.add<unsigned long long>(nf);
+    w.no_window = wt.add<uint8_t>(nf);
+    wt.inputs_end();
+    w.d.outputs(wt, m);
+    // (the tables of the check sums and of the guard check are reserved here, before the pass is queued: growing tab_buf
+    // behind it would take the tables the queued kernels read away)
+    w.m_begin = wt.add<uint64_t>(nm);
+    w.m_len = wt.add<uint64_t>(nm);
+    w.m_acc = wt.add<uint32_t>(nm);
+    w.damaged = wt.add<uint32_t>(1);
+    PSK_TRY(wt.reserve(ctx, tab_buf));
+    w.d.fill(wt, plan, L.order);
+    for (size_t j = 0; j < m; j++) {
+        const GzChunk &c = plan.ch[(size_t)L.order[j]];
+        wt.host(w.stop)[j] = c.link == GZ_FINAL ? GZ_NONE : c.end_bit;
+        wt.host(w.out_off)[j] = L.c_off[j];
+        wt.host(w.want_len)[j] = c.out_len;
+        wt.host(w.rec_off)[j] = L.c_rec[j];
+        wt.host(w.want_rec)[j] = c.n_rec;
+    }
+    std::memcpy(wt.host(w.file_first), L.file_first.data(), nf * 4);
+    for (size_t fi = 0; fi + 1 < nf; fi++)
+        for (uint32_t j = L.file_first[fi]; j < L.file_first[fi + 1]; j++) wt.host(w.chunk_file)[j] = (uint32_t)fi;
+    std::memset(wt.host(w.nul), 0xff, nf * 8);
+    std::memcpy(wt.host(w.no_window), L.members_only.data(), L.members_only.size());
+    PSK_TRY(wt.upload(ctx, st));
+    wa = w.d.args(wt, d_comp, m);
+    wa.stop_bit = wt.dev(w.stop);
+    wa.out_off = wt.dev(w.out_off);
+    wa.want_len = wt.dev(w.want_len);
+    wa.rec_off = wt.dev(w.rec_off);
+    wa.want_rec = wt.dev(w.want_rec);
+    wa.sym = d_sym;
+    wa.rec = d_rec;
+    gz_decode_kernel<true><<<dim3((unsigned)div_up((uint64_t)m, 64)), dim3(64), GZ_LDS_U16 * 2, st>>>(wa);
+    PSK_HIP(ctx, hipGetLastError());
+    GzCopyStats stats;
+    if (env_flag("PSK_GZ_STATS")) {
+        PSK_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&stats.d), 64));
+        PSK_HIP(ctx, hipMemsetAsync(stats.d, 0, 64, st));
+    }
+    gz_copy_kernel<<<dim3((unsigned)div_up((uint64_t)m, 4)), dim3(256), 0, st>>>(d_sym, d_rec, wa.rec_off, wa.want_rec, wa.n_rec, wa.link, wa.want_len, wa.out_off,
+                                                                               (int)m, stats.d);
+    PSK_HIP(ctx, hipGetLastError());
+    if (stats.d) {
+        unsigned long long hs[8];
+        PSK_HIP(ctx, hipStreamSynchronize(st));
+        PSK_HIP(ctx, hipMemcpy(hs, stats.d, 64, hipMemcpyDeviceToHost));
+        std::fprintf(stderr, "[psk] gz copy: %llu matches in %llu groups of 64, %llu with a source inside the group, %llu redirection hops, %llu matches left waiting, "
+                             "%llu rounds\n",
+                     (unsigned long long)L.total_rec, hs[0], hs[2], hs[3], hs[5], hs[1]);
+    }
+    gz_tails_kernel<<<dim3((unsigned)(nf - 1)), dim3(1024), 0, st>>>(d_sym, d_text, wa.out_off, wa.want_len, wt.dev(w.file_first), wt.dev(w.no_window), wt.dev(w.nul));
+    PSK_HIP(ctx, hipGetLastError());
+    gz_resolve_kernel<<<dim3((unsigned)m), dim3(256), 0, st>>>(d_sym, d_text, wa.out_off, wa.want_len, wt.dev(w.chunk_file), wt.dev(w.no_window), wt.dev(w.nul));
+    PSK_HIP(ctx, hipGetLastError());
+    return wt.fetch(ctx, st, w.nul, nul_at);
+}
+
+// the members' check sums, queued behind the text
+int GzGroup::check_sums(const GzTextLayout &L)
+{
+    const size_t nm = L.m_begin.size();
+    crc_got.assign(nm, 0);
+    check_crc = nm && !env_flag("PSK_GZ_NO_CRC");
+    if (!check_crc) return PSK_OK;
+    PSK_HIP(ctx, hipMemcpyAsync(wt.dev(w.m_begin), L.m_begin.data(), nm * 8, hipMemcpyHostToDevice, st));
+    PSK_HIP(ctx, hipMemcpyAsync(wt.dev(w.m_len), L.m_len.data(), nm * 8, hipMemcpyHostToDevice, st));
+    PSK_HIP(ctx, hipMemsetAsync(wt.dev(w.m_acc), 0, nm * 4, st));
+    const uint64_t span = L.total - GZ_WIN;   // (nothing but empty texts: no launch; the check sums of empty members are 0)
+    if (span)
+        gz_crc_kernel<<<dim3((unsigned)div_up(span, (uint64_t)256 * GZ_CRC_SEG)), dim3(256), 0, st>>>(d_text, wt.dev(w.m_begin), wt.dev(w.m_len), (int)nm,
+                                                                                                     (uint64_t)GZ_WIN, L.total, wt.dev(w.m_acc));
+    PSK_HIP(ctx, hipGetLastError());
+    return wt.fetch(ctx, st, w.m_acc, crc_got);
+}
+
+int GzGroup::settle(const GzTextLayout &L)
+{
+    PSK_TRY(wt.fetch(ctx, st, w.d.link, w_link));
+    if (guard) {
+        PSK_HIP(ctx, hipMemsetAsync(wt.dev(w.damaged), 0, 4, st));
+        gz_guard_check_kernel<<<dim3(16, 6), dim3(256), 0, st>>>(bands, wt.dev(w.damaged));
+        PSK_HIP(ctx, hipGetLastError());
+        PSK_HIP(ctx, hipMemcpyAsync(&guard_damage, wt.dev(w.damaged), 4, hipMemcpyDeviceToHost, st));
+    }
+    PSK_HIP(ctx, hipStreamSynchronize(st));
+    laps.lap("write + matches + markers + crc");
+    if (guard_damage)
+        return psk_fail(ctx, PSK_ESTATE, "gz inflate: %u bytes of the guard bands around the text / symbol / match buffers were overwritten", guard_damage);
+    for (size_t j = 0; j < w_link.size(); j++)
+        if (w_link[j] == GZ_ERROR)   // the second decode disagrees with the first: nothing of this file is trusted
+            plan.files[(size_t)plan.ch[(size_t)L.order[j]].file].device_ok = false;
+    if (check_crc)
+        for (size_t q = 0; q < L.m_crc.size(); q++)
+            if (crc_got[q] != L.m_crc[q]) plan.files[(size_t)L.m_file[q]].device_ok = false;   // zlib will say "incorrect data check"
+    return PSK_OK;
+}
+
+// res[i] of every file the device kept; returns the others
+std::vector<int> GzGroup::results(std::vector<GzInflated> &res) const
+{
+    std::vector<int> declined;
+    for (size_t i = 0; i < plan.files.size(); i++) {
+        const GzFile &f = plan.files[i];
+        GzInflated &r = res[i];
+        r.on_device = f.device_ok;
+        r.bgzf = f.bgzf;
+        r.chunks = (int)f.chain.size();
+        if (f.device_ok) {
+            r.off = f.out_off + guard;   // (relative to the buffer the caller holds: the leading band is in front)
+            r.len = f.out_len;
+            r.first_nul = r.len;
+            if (f.nul_slot >= 0 && (size_t)f.nul_slot < nul_at.size() && nul_at[(size_t)f.nul_slot] != ~0ull) r.first_nul = nul_at[(size_t)f.nul_slot] - f.out_off;
+        } else {
+            declined.push_back((int)i);
+        }
+    }
+    return declined;
+}
+
+}  // namespace
 
 // Whether a group is inflated on the device at all (else: zlib on host threads, nothing to upload).  The device route has a floor
 // of ~40 ms -- its serial passes over one DEFLATE block take that long whatever the number of blocks -- and then runs at ~10 GB/s of
@@ -1310,570 +1692,47 @@ int gz_inflate_group(psk_ctx *ctx, int n, const uint8_t *const *data, const size
     // `host_threads` threads (what glistmaker does per file).
     size_t comp_bytes = 0;
     for (int i = 0; i < n; i++) comp_bytes += sizes[i];
-    // zlib over the files `which` names, one file a thread of a pool of host_threads (the first error, in file order, is the call's)
-    auto host_route = [&](const std::vector<int> &which) -> int {
-        const int nw = (int)which.size();
-        std::atomic<int> next(0), bad(0);
-        std::vector<std::string> errs((size_t)nw);
-        auto work = [&]() {
-            for (;;) {
-                const int j = next.fetch_add(1);
-                if (j >= nw) return;
-                const int i = which[(size_t)j];
-                if (!gz_host_inflate(data[i], sizes[i], res[(size_t)i].host, &errs[(size_t)j])) {
-                    bad = 1;
-                    res[(size_t)i].error = errs[(size_t)j];   // (every file is tried: psk_gz_inflate reports per file)
-                    res[(size_t)i].host.clear();
-                }
-                res[(size_t)i].len = res[(size_t)i].host.size();
-            }
-        };
-        std::vector<std::thread> pool;
-        const int nt = host_threads < 1 ? 1 : (host_threads > 32 ? 32 : host_threads);
-        for (int t = 1; t < nt && t < nw; t++) pool.emplace_back(work);
-        work();
-        for (auto &t : pool) t.join();
-        if (bad)
-            for (int j = 0; j < nw; j++)
-                if (!errs[(size_t)j].empty()) return psk_fail(ctx, PSK_EINVAL, "%s", errs[(size_t)j].c_str());
-        return PSK_OK;
-    };
+    const bool trace = env_flag("PSK_TRACE");
     bool on_device = false;
     PSK_TRY(gz_group_on_device(ctx, n, sizes, host_only, host_threads, &on_device));
     if (!on_device) {
         std::vector<int> all((size_t)n);
         for (int i = 0; i < n; i++) all[(size_t)i] = i;
-        PSK_TRY(host_route(all));
-        if (env_flag("PSK_TRACE"))
+        PSK_TRY(gz_host_route(ctx, data, sizes, all, host_threads, res));
+        if (trace)
             std::fprintf(stderr, "[psk] gz inflate: %d files, %.1f MB compressed: zlib on at most %d host threads\n", n, comp_bytes / 1e6, host_threads < 1 ? 1 : host_threads);
         return PSK_OK;
     }
     PSK_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = on_stream ? on_stream : ctx->stream;
-    std::vector<GzFile> files((size_t)n);
-    std::vector<uint64_t> image_at((size_t)n);
-    const uint64_t comp_total = gz_image_layout(n, sizes, image_at.data());
-    for (int i = 0; i < n; i++) {
-        files[i].data = data[i];
-        files[i].size = sizes[i];
-        files[i].at = image_at[(size_t)i];
-    }
-    // ---- the chunks --------------------------------------------------------------------------------------------
-    size_t deflate_bytes = 0;
-    for (int i = 0; i < n; i++) deflate_bytes += sizes[i];
-    size_t want_lanes = 65536, chunk = 0;   // lanes: four waves on each of 256 CUs; chunk 0: from the lanes
-    PSK_TRY(env_int(ctx, "PSK_GZ_LANES", 1, 1 << 30, &want_lanes));
-    PSK_TRY(env_int(ctx, "PSK_GZ_CHUNK", 0, 1ll << 40, &chunk));
-    if (!chunk) chunk = std::min<size_t>(std::max<size_t>(deflate_bytes / want_lanes, 16 << 10), 4 << 20);   // (16 KB: less than a block of most encoders -- two cuts in one block find the same start and one of the two lanes idles, but a group that cannot fill the part anyway is cut at every block: 1.15 GB of FASTQ text 69 -> 51 ms)
-    chunk = (chunk + 3) & ~(size_t)3;
-    std::vector<GzChunk> ch;
-    std::vector<std::pair<int, int>> file_chunks((size_t)n);   // [first, last) of its regular chunks
-    for (int i = 0; i < n; i++) {
-        GzFile &f = files[i];
-        GzMemberHead h;
-        file_chunks[i] = {(int)ch.size(), (int)ch.size()};
-        if (!gz_parse_member_header(f.data, f.size, 0, &h)) {
-            f.device_ok = false;
-            continue;
-        }
-        if (h.bsize) {
-            // BGZF: every member says how long it is -- one chunk per member, nothing to search for
-            f.bgzf = true;
-            size_t at = 0;
-            bool ok = true;
-            while (at < f.size) {
-                GzMemberHead m;
-                if (!gz_parse_member_header(f.data, f.size, at, &m) || !m.bsize || at + m.bsize > f.size || m.deflate_at + 8 > at + m.bsize) {
-                    ok = false;
-                    break;
-                }
-                GzChunk c;
-                c.file = i;
-                c.start_bit = (f.at + m.deflate_at) * 8;
-                c.seek_from = c.seek_to = 0;
-                c.true_start = true;
-                ch.push_back(c);
-                at += m.bsize;
-            }
-            if (!ok) {
-                ch.resize((size_t)file_chunks[i].first);
-                f.bgzf = false;
-                f.device_ok = false;
-                continue;
-            }
-        } else {
-            const size_t d0 = h.deflate_at, d1 = f.size - 8;
-            for (size_t at = d0; at < d1 || at == d0; at += chunk) {
-                GzChunk c;
-                c.file = i;
-                c.true_start = at == d0;
-                c.start_bit = at == d0 ? (f.at + d0) * 8 : GZ_NONE;
-                c.seek_from = at == d0 ? 0 : (f.at + at) * 8;
-                c.seek_to = at == d0 ? 0 : (f.at + std::min(at + chunk, d1)) * 8;
-                ch.push_back(c);
-            }
-        }
-        file_chunks[i].second = (int)ch.size();
-    }
+    GzGroup g{ctx, on_stream ? on_stream : ctx->stream, comp_buf, sym_buf, rec_buf, out_buf, tab_buf};
+    PSK_TRY(g.knobs.read(ctx));
+    g.chunk = gz_chunk_bytes(comp_bytes, g.knobs.lanes, g.knobs.chunk);
+    g.plan = gz_plan_chunks(n, data, sizes, g.chunk);
     const auto t_begin = std::chrono::steady_clock::now();
-    const bool trace = env_flag("PSK_TRACE");
-    auto t_last = t_begin;
-    std::string phases;
-    auto lap = [&](const char *what) {
-        if (!trace) return;
-        (void)hipStreamSynchronize(st);
-        const auto now = std::chrono::steady_clock::now();
-        char buf[96];
-        std::snprintf(buf, sizeof buf, " %s %.1f", what, std::chrono::duration<double, std::milli>(now - t_last).count());
-        phases += buf;
-        t_last = now;
-    };
-    // ---- the images ---------------------------------------------------------------------------------------------
-    if (!images_uploaded) {   // (the counting calls upload each image as soon as it is read: gz_image_layout says where)
-        PSK_TRY(dev_reserve(ctx, comp_buf, comp_total));
-        PSK_HIP(ctx, hipMemsetAsync(comp_buf.p, 0, comp_total, st));
-        for (int i = 0; i < n; i++)
-            if (files[i].device_ok && sizes[i])
-                PSK_HIP(ctx, hipMemcpyAsync(comp_buf.as<uint8_t>() + files[i].at, data[i], sizes[i], hipMemcpyHostToDevice, st));
-    }
-    const uint8_t *d_comp = comp_buf.as<uint8_t>();
-    lap("upload");
-
-    // device tables of one pass over `m` chunks, carved out of tab_buf
-    auto carve = [&](size_t &off, size_t bytes) {
-        const size_t at = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return at;
-    };
-    std::vector<int> todo;   // chunks of the coming counting pass
-    for (size_t c = 0; c < ch.size(); c++) todo.push_back((int)c);
-    std::vector<uint8_t> stage;
-    int rounds = 0;
-    int max_rounds = 24;
-    PSK_TRY(env_int(ctx, "PSK_GZ_ROUNDS", 0, 1 << 20, &max_rounds));
-    // ---- step 1: the starts ---------------------------------------------------------------------------------------
-    {
-        std::vector<int> seek;
-        for (size_t c = 0; c < ch.size(); c++)
-            if (ch[c].seek_to > ch[c].seek_from) seek.push_back((int)c);
-        if (!seek.empty()) {
-            const size_t m = seek.size();
-            size_t off = 0;
-            const size_t o_from = carve(off, m * 8), o_to = carve(off, m * 8), o_end = carve(off, m * 8), o_found = carve(off, m * 8);
-            PSK_TRY(dev_reserve(ctx, tab_buf, off));
-            stage.assign(o_found, 0);
-            for (size_t j = 0; j < m; j++) {
-                const GzChunk &c = ch[(size_t)seek[j]];
-                reinterpret_cast<uint64_t *>(stage.data() + o_from)[j] = c.seek_from;
-                reinterpret_cast<uint64_t *>(stage.data() + o_to)[j] = c.seek_to;
-                reinterpret_cast<uint64_t *>(stage.data() + o_end)[j] = files[(size_t)c.file].at + files[(size_t)c.file].size;
-            }
-            uint8_t *t = tab_buf.as<uint8_t>();
-            PSK_HIP(ctx, hipMemcpyAsync(t, stage.data(), o_found, hipMemcpyHostToDevice, st));
-            gz_find_kernel<<<dim3((unsigned)m), dim3(64), 0, st>>>(d_comp, reinterpret_cast<const uint64_t *>(t + o_from),
-                                                                 reinterpret_cast<const uint64_t *>(t + o_to),
-                                                                 reinterpret_cast<const uint64_t *>(t + o_end), (int)m,
-                                                                 reinterpret_cast<uint64_t *>(t + o_found));
-            PSK_HIP(ctx, hipGetLastError());
-            std::vector<uint64_t> found(m);
-            PSK_HIP(ctx, hipMemcpyAsync(found.data(), t + o_found, m * 8, hipMemcpyDeviceToHost, st));
-            PSK_HIP(ctx, hipStreamSynchronize(st));
-            for (size_t j = 0; j < m; j++) ch[(size_t)seek[j]].start_bit = found[j];
-        }
-    }
-    lap("find");
-    // the starts a block end may coincide with: per file, ascending
-    std::vector<uint64_t> cand_bit;
-    std::vector<int> cand_chunk;
-    std::vector<std::pair<uint32_t, uint32_t>> file_cands((size_t)n);
-    auto rebuild_cands = [&]() {
-        cand_bit.clear();
-        cand_chunk.clear();
-        for (int i = 0; i < n; i++) {
-            std::vector<std::pair<uint64_t, int>> v;
-            for (size_t c = 0; c < ch.size(); c++)
-                if (ch[c].file == i && ch[c].start_bit != GZ_NONE) v.push_back({ch[c].start_bit, (int)c});
-            std::sort(v.begin(), v.end());
-            file_cands[(size_t)i].first = (uint32_t)cand_bit.size();
-            for (auto &e : v) {
-                cand_bit.push_back(e.first);
-                cand_chunk.push_back(e.second);
-            }
-            file_cands[(size_t)i].second = (uint32_t)cand_bit.size();
-        }
-    };
-    // ---- steps 2 + 3: counting passes until every file's chain reaches its end ----------------------------------------
-    // how far ONE lane may decode without meeting a found start.  A lane decodes ~1.4 MB of compressed input a second (65,536 of them:
-    // 1.9 GB in 21 ms), so this is the bound on what a file with no dynamic block headers -- stored or fixed-code blocks only, or one
-    // crafted to look so -- can cost the call before zlib gets it: 1 MiB = 0.75 s (r05: 8 MiB = 6 s, and again in every round of a
-    // file of several such members).  Blocks of the usual encoders end far sooner (zlib: tens of KB; pigz 128 KB; libdeflate <= ~300 KB).
-    size_t max_span = 1 << 20;
-    PSK_TRY(env_int(ctx, "PSK_GZ_MAX_SPAN", 0, 1ll << 40, &max_span));
-    const uint64_t max_span_bits = (uint64_t)std::max<size_t>(chunk * 8, max_span) * 8;
-    std::vector<int> next_chunk((size_t)n, -1);   // per file: the chunk its chain follows next (-1: the chain has reached the end)
-    for (int i = 0; i < n; i++) next_chunk[(size_t)i] = files[(size_t)i].device_ok && file_chunks[(size_t)i].second > file_chunks[(size_t)i].first ? file_chunks[(size_t)i].first : -1;
-    while (!todo.empty()) {
-        if (++rounds > max_rounds) {
-            for (int c : todo) files[(size_t)ch[(size_t)c].file].device_ok = false;
-            break;
-        }
-        rebuild_cands();
-        const size_t m = todo.size();
-        size_t off = 0;
-        const size_t o_start = carve(off, m * 8), o_end = carve(off, m * 8), o_true = carve(off, m), o_cf = carve(off, m * 4), o_ct = carve(off, m * 4),
-                     o_cand = carve(off, cand_bit.size() * 8 + 8);
-        const size_t o_in_end = off;
-        const size_t o_len = carve(off, m * 8), o_nrec = carve(off, m * 8), o_ebit = carve(off, m * 8), o_link = carve(off, m * 4),
-                     o_long = carve(off, m * 640);
-        PSK_TRY(dev_reserve(ctx, tab_buf, off));
-        stage.assign(o_in_end, 0);
-        for (size_t j = 0; j < m; j++) {
-            const GzChunk &c = ch[(size_t)todo[j]];
-            const GzFile &f = files[(size_t)c.file];
-            reinterpret_cast<uint64_t *>(stage.data() + o_start)[j] = f.device_ok ? c.start_bit : GZ_NONE;
-            reinterpret_cast<uint64_t *>(stage.data() + o_end)[j] = f.at + f.size;
-            stage[o_true + j] = c.true_start ? 1 : 0;
-            // its candidates: those of its file that start after it
-            const auto &fc = file_cands[(size_t)c.file];
-            const uint32_t from = (uint32_t)(std::upper_bound(cand_bit.begin() + fc.first, cand_bit.begin() + fc.second, c.start_bit) - cand_bit.begin());
-            reinterpret_cast<uint32_t *>(stage.data() + o_cf)[j] = c.start_bit == GZ_NONE ? fc.second : from;
-            reinterpret_cast<uint32_t *>(stage.data() + o_ct)[j] = fc.second;
-        }
-        if (!cand_bit.empty()) std::memcpy(stage.data() + o_cand, cand_bit.data(), cand_bit.size() * 8);
-        uint8_t *t = tab_buf.as<uint8_t>();
-        PSK_HIP(ctx, hipMemcpyAsync(t, stage.data(), o_in_end, hipMemcpyHostToDevice, st));
-        GzDecodeArgs a;
-        std::memset(&a, 0, sizeof a);
-        a.comp = d_comp;
-        a.start_bit = reinterpret_cast<const uint64_t *>(t + o_start);
-        a.end_byte = reinterpret_cast<const uint64_t *>(t + o_end);
-        a.true_start = t + o_true;
-        a.cand_bit = reinterpret_cast<const uint64_t *>(t + o_cand);
-        a.cand_from = reinterpret_cast<const uint32_t *>(t + o_cf);
-        a.cand_to = reinterpret_cast<const uint32_t *>(t + o_ct);
-        a.max_span_bits = max_span_bits;
-        a.long_syms = reinterpret_cast<uint16_t *>(t + o_long);
-        a.out_len = reinterpret_cast<uint64_t *>(t + o_len);
-        a.n_rec = reinterpret_cast<uint64_t *>(t + o_nrec);
-        a.end_bit = reinterpret_cast<uint64_t *>(t + o_ebit);
-        a.link = reinterpret_cast<int32_t *>(t + o_link);
-        a.n = (int)m;
-        PSK_HIP(ctx, hipMemsetAsync(t + o_link, 0xfe, m * 4, st));   // (a chunk without a start keeps a negative link)
-        gz_decode_kernel<false><<<dim3((unsigned)div_up((uint64_t)m, 64)), dim3(64), GZ_LDS_U16 * 2, st>>>(a);
-        PSK_HIP(ctx, hipGetLastError());
-        std::vector<uint64_t> r_len(m), r_ebit(m), r_nrec(m);
-        std::vector<int32_t> r_link(m);
-        PSK_HIP(ctx, hipMemcpyAsync(r_len.data(), t + o_len, m * 8, hipMemcpyDeviceToHost, st));
-        PSK_HIP(ctx, hipMemcpyAsync(r_nrec.data(), t + o_nrec, m * 8, hipMemcpyDeviceToHost, st));
-        PSK_HIP(ctx, hipMemcpyAsync(r_ebit.data(), t + o_ebit, m * 8, hipMemcpyDeviceToHost, st));
-        PSK_HIP(ctx, hipMemcpyAsync(r_link.data(), t + o_link, m * 4, hipMemcpyDeviceToHost, st));
-        PSK_HIP(ctx, hipStreamSynchronize(st));
-        for (size_t j = 0; j < m; j++) {
-            GzChunk &c = ch[(size_t)todo[j]];
-            if (c.start_bit == GZ_NONE || !files[(size_t)c.file].device_ok) continue;
-            c.counted = true;
-            c.out_len = r_len[j];
-            c.n_rec = r_nrec[j];
-            c.end_bit = r_ebit[j];
-            c.link = r_link[j] >= 0 ? cand_chunk[(size_t)r_link[j]] : r_link[j];
-        }
-        todo.clear();
-        // the walk along the links
-        for (int i = 0; i < n; i++) {
-            GzFile &f = files[(size_t)i];
-            while (f.device_ok && next_chunk[(size_t)i] >= 0) {
-                const int cidx = next_chunk[(size_t)i];
-                GzChunk &c = ch[(size_t)cidx];
-                if (!c.counted) break;   // in `todo`: the next round
-                f.chain.push_back(cidx);
-                if (c.link >= 0) {
-                    if (ch[(size_t)c.link].true_start) {
-                        // a block that ends, without being the last of its member, where another member's data begin: no
-                        // stream zlib accepts does that (a crafted BSIZE / member header does): zlib words the error
-                        f.device_ok = false;
-                        break;
-                    }
-                    next_chunk[(size_t)i] = c.link;
-                    continue;
-                }
-                if (c.link != GZ_FINAL) {
-                    f.device_ok = false;   // an error, or a block that ran on and on: zlib decides what it is
-                    break;
-                }
-                // the member's trailer; another member behind it?
-                const uint64_t trailer = (c.end_bit + 7) / 8 - f.at;
-                if (trailer + 8 > f.size) {
-                    f.device_ok = false;
-                    break;
-                }
-                size_t next = (size_t)trailer + 8;
-                {
-                    // ISIZE of the member that just ended: the bytes since its true start
-                    uint64_t member = 0;
-                    for (size_t q = f.chain.size(); q-- > 0;) {
-                        member += ch[(size_t)f.chain[q]].out_len;
-                        if (ch[(size_t)f.chain[q]].true_start) break;
-                    }
-                    if ((uint32_t)member != gz_le32(f.data + trailer + 4)) {
-                        f.device_ok = false;
-                        break;
-                    }
-                }
-                while (next < f.size && f.data[next] == 0) next++;   // padding (gzip.decompress skips it as well)
-                if (next >= f.size) {
-                    next_chunk[(size_t)i] = -1;
-                    break;
-                }
-                if (f.bgzf) {
-                    // the next member is the next chunk of the file
-                    next_chunk[(size_t)i] = cidx + 1 < file_chunks[(size_t)i].second ? cidx + 1 : -1;
-                    if (next_chunk[(size_t)i] < 0) f.device_ok = false;
-                    continue;
-                }
-                GzMemberHead h;
-                if (!gz_parse_member_header(f.data, f.size, next, &h)) {
-                    f.device_ok = false;
-                    break;
-                }
-                // a member in the middle of the file: it starts a chain of its own (a chunk whose found start this is
-                // becomes its first link; else one more chunk, counted in the next round)
-                const uint64_t sbit = (f.at + h.deflate_at) * 8;
-                int have = -1;
-                for (int q = file_chunks[(size_t)i].first; q < (int)ch.size(); q++)
-                    if (ch[(size_t)q].file == i && ch[(size_t)q].start_bit == sbit) have = q;
-                if (have >= 0) {
-                    ch[(size_t)have].true_start = true;   // (what it counted stays right: a valid stream has no match reaching back here)
-                    next_chunk[(size_t)i] = have;
-                    continue;
-                }
-                GzChunk extra;
-                extra.file = i;
-                extra.start_bit = sbit;
-                extra.seek_from = extra.seek_to = 0;
-                extra.true_start = true;
-                ch.push_back(extra);
-                todo.push_back((int)ch.size() - 1);
-                next_chunk[(size_t)i] = (int)ch.size() - 1;
-                break;
-            }
-        }
-    }
-    lap("count");
-    // ---- the layout of the text -----------------------------------------------------------------------------------
-    uint64_t total = GZ_WIN;   // (room before the first file: a marker of a corrupt stream reads inside the buffer)
-    std::vector<int> order;    // the chunks of the writing pass, file by file, in stream order
-    std::vector<uint32_t> file_first;
-    std::vector<uint64_t> c_off, c_rec, m_begin, m_len;   // (m_*: the members, in the order of the text buffer)
-    std::vector<uint32_t> m_crc;
-    std::vector<int> m_file;
-    uint64_t total_rec = 0;
-    // a file's chain is members one after the other -- first chunk a member's start, none in the middle of a member (a chunk
-    // that was linked to BEFORE a later walk found a member starting there), the last chunk the end of a member: anything else
-    // is declined here, so that every member below has a beginning AND a length and the check sums are never skipped
-    for (int i = 0; i < n; i++) {
-        GzFile &f = files[(size_t)i];
-        if (!f.device_ok) continue;
-        bool open = false, ok = !f.chain.empty();
-        for (int c : f.chain) {
-            const GzChunk &k = ch[(size_t)c];
-            if (k.true_start == open) ok = false;   // a start inside a member, or a member that does not begin with one
-            open = k.link != GZ_FINAL;
-        }
-        if (!ok || open) f.device_ok = false;
-    }
-    for (int i = 0; i < n; i++) {
-        GzFile &f = files[(size_t)i];
-        if (!f.device_ok) continue;
-        total = (total + 63) & ~63ull;
-        f.out_off = total;
-        f.nul_slot = (int)file_first.size();
-        file_first.push_back((uint32_t)order.size());
-        for (int c : f.chain) {
-            const GzChunk &k = ch[(size_t)c];
-            order.push_back(c);
-            c_off.push_back(total);
-            if (k.true_start) m_begin.push_back(total);
-            total += k.out_len;
-            c_rec.push_back(total_rec);
-            total_rec += k.n_rec;
-            if (k.link == GZ_FINAL) {   // the member's trailer: CRC-32, ISIZE
-                m_len.push_back(total - m_begin.back());
-                m_crc.push_back(gz_le32(f.data + ((k.end_bit + 7) / 8 - f.at)));
-                m_file.push_back(i);
-            }
-        }
-        f.out_len = total - f.out_off;
-    }
-    file_first.push_back((uint32_t)order.size());
-    total = (total + 63) & ~63ull;
-    const size_t m = order.size();
-    std::vector<unsigned long long> nul_at;   // per file of the writing pass: where its text has its first NUL (in out_buf), ~0: nowhere
-    const size_t guard = env_flag("PSK_GZ_GUARD") ? GZ_GUARD : 0;
-    uint32_t guard_damage = 0;
-    if (m) {
-        PSK_TRY(dev_reserve(ctx, sym_buf, total * 2 + 64 + 2 * guard));
-        PSK_TRY(dev_reserve(ctx, out_buf, total + 64 + 2 * guard));
-        PSK_TRY(dev_reserve(ctx, rec_buf, total_rec * 8 + 64 + 2 * guard));
-        // (the buffers proper start behind the leading band; the 64 bytes of slack the wide loads may touch stay in front of the trailing one)
-        uint16_t *const d_sym = reinterpret_cast<uint16_t *>(sym_buf.as<uint8_t>() + guard);
-        uint8_t *const d_text = out_buf.as<uint8_t>() + guard;
-        uint2 *const d_rec = reinterpret_cast<uint2 *>(rec_buf.as<uint8_t>() + guard);
-        GzGuardBands bands;
-        if (guard) {
-            uint8_t *b[6] = {sym_buf.as<uint8_t>(), sym_buf.as<uint8_t>() + guard + total * 2 + 64, out_buf.as<uint8_t>(), out_buf.as<uint8_t>() + guard + total + 64,
-                             rec_buf.as<uint8_t>(), rec_buf.as<uint8_t>() + guard + total_rec * 8 + 64};
-            for (int q = 0; q < 6; q++) {
-                bands.band[q] = b[q];
-                PSK_HIP(ctx, hipMemsetAsync(b[q], GZ_GUARD_BYTE, guard, st));
-            }
-        }
-        lap("buffers");
-        size_t off = 0;
-        const size_t o_start = carve(off, m * 8), o_end = carve(off, m * 8), o_true = carve(off, m), o_stop = carve(off, m * 8), o_off = carve(off, m * 8),
-                     o_want = carve(off, m * 8), o_roff = carve(off, m * 8), o_wrec = carve(off, m * 8), o_ff = carve(off, file_first.size() * 4),
-                     o_cfile = carve(off, m * 4), o_nul = carve(off, file_first.size() * 8), o_nowin = carve(off, file_first.size());
-        const size_t o_in_end = off;
-        const size_t o_len = carve(off, m * 8), o_nrec = carve(off, m * 8), o_ebit = carve(off, m * 8), o_link = carve(off, m * 4),
-                     o_long = carve(off, m * 640);
-        const size_t o_members = carve(off, 2 * ((m_begin.size() * 8 + 255) & ~(size_t)255) + m_begin.size() * 4 + 256);
-        const size_t o_guard = carve(off, 256);
-        PSK_TRY(dev_reserve(ctx, tab_buf, off));
-        stage.assign(o_in_end, 0);
-        for (size_t j = 0; j < m; j++) {
-            const GzChunk &c = ch[(size_t)order[j]];
-            const GzFile &f = files[(size_t)c.file];
-            reinterpret_cast<uint64_t *>(stage.data() + o_start)[j] = c.start_bit;
-            reinterpret_cast<uint64_t *>(stage.data() + o_end)[j] = f.at + f.size;
-            stage[o_true + j] = c.true_start ? 1 : 0;
-            reinterpret_cast<uint64_t *>(stage.data() + o_stop)[j] = c.link == GZ_FINAL ? GZ_NONE : c.end_bit;
-            reinterpret_cast<uint64_t *>(stage.data() + o_off)[j] = c_off[j];
-            reinterpret_cast<uint64_t *>(stage.data() + o_want)[j] = c.out_len;
-            reinterpret_cast<uint64_t *>(stage.data() + o_roff)[j] = c_rec[j];
-            reinterpret_cast<uint64_t *>(stage.data() + o_wrec)[j] = c.n_rec;
-        }
-        std::memcpy(stage.data() + o_ff, file_first.data(), file_first.size() * 4);
-        for (size_t fi = 0; fi + 1 < file_first.size(); fi++)
-            for (uint32_t j = file_first[fi]; j < file_first[fi + 1]; j++) reinterpret_cast<uint32_t *>(stage.data() + o_cfile)[j] = (uint32_t)fi;
-        std::memset(stage.data() + o_nul, 0xff, file_first.size() * 8);
-        for (size_t fi = 0; fi + 1 < file_first.size(); fi++) {
-            bool members_only = true;
-            for (uint32_t j = file_first[fi]; j < file_first[fi + 1]; j++) members_only = members_only && ch[(size_t)order[j]].true_start;
-            stage[o_nowin + fi] = members_only ? 1 : 0;
-        }
-        uint8_t *t = tab_buf.as<uint8_t>();
-        PSK_HIP(ctx, hipMemcpyAsync(t, stage.data(), o_in_end, hipMemcpyHostToDevice, st));
-        GzDecodeArgs a;
-        std::memset(&a, 0, sizeof a);
-        a.comp = d_comp;
-        a.start_bit = reinterpret_cast<const uint64_t *>(t + o_start);
-        a.end_byte = reinterpret_cast<const uint64_t *>(t + o_end);
-        a.true_start = t + o_true;
-        a.stop_bit = reinterpret_cast<const uint64_t *>(t + o_stop);
-        a.out_off = reinterpret_cast<const uint64_t *>(t + o_off);
-        a.want_len = reinterpret_cast<const uint64_t *>(t + o_want);
-        a.rec_off = reinterpret_cast<const uint64_t *>(t + o_roff);
-        a.want_rec = reinterpret_cast<const uint64_t *>(t + o_wrec);
-        a.sym = d_sym;
-        a.rec = d_rec;
-        a.long_syms = reinterpret_cast<uint16_t *>(t + o_long);
-        a.out_len = reinterpret_cast<uint64_t *>(t + o_len);
-        a.n_rec = reinterpret_cast<uint64_t *>(t + o_nrec);
-        a.end_bit = reinterpret_cast<uint64_t *>(t + o_ebit);
-        a.link = reinterpret_cast<int32_t *>(t + o_link);
-        a.n = (int)m;
-        gz_decode_kernel<true><<<dim3((unsigned)div_up((uint64_t)m, 64)), dim3(64), GZ_LDS_U16 * 2, st>>>(a);
-        PSK_HIP(ctx, hipGetLastError());
-        const uint64_t *d_off = reinterpret_cast<const uint64_t *>(t + o_off), *d_len = reinterpret_cast<const uint64_t *>(t + o_want);
-        unsigned long long *d_stats = nullptr;
-        if (env_flag("PSK_GZ_STATS")) {
-            PSK_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&d_stats), 64));
-            PSK_HIP(ctx, hipMemsetAsync(d_stats, 0, 64, st));
-        }
-        gz_copy_kernel<<<dim3((unsigned)div_up((uint64_t)m, 4)), dim3(256), 0, st>>>(d_sym, d_rec, a.rec_off, a.want_rec, a.n_rec, a.link,
-                                                                                   a.want_len, d_off, (int)m, d_stats);
-        PSK_HIP(ctx, hipGetLastError());
-        if (d_stats) {
-            unsigned long long hs[8];
-            PSK_HIP(ctx, hipStreamSynchronize(st));
-            PSK_HIP(ctx, hipMemcpy(hs, d_stats, 64, hipMemcpyDeviceToHost));
-            (void)hipFree(d_stats);
-            std::fprintf(stderr, "[psk] gz copy: %llu matches in %llu groups of 64, %llu with a source inside the group, %llu redirection hops, %llu matches left waiting, "
-                                 "%llu rounds\n",
-                         (unsigned long long)total_rec, hs[0], hs[2], hs[3], hs[5], hs[1]);
-        }
-        unsigned long long *d_nul = reinterpret_cast<unsigned long long *>(t + o_nul);
-        gz_tails_kernel<<<dim3((unsigned)(file_first.size() - 1)), dim3(1024), 0, st>>>(d_sym, d_text, d_off, d_len,
-                                                                                     reinterpret_cast<const uint32_t *>(t + o_ff), t + o_nowin, d_nul);
-        PSK_HIP(ctx, hipGetLastError());
-        gz_resolve_kernel<<<dim3((unsigned)m), dim3(256), 0, st>>>(d_sym, d_text, d_off, d_len,
-                                                                   reinterpret_cast<const uint32_t *>(t + o_cfile), t + o_nowin, d_nul);
-        PSK_HIP(ctx, hipGetLastError());
-        nul_at.resize(file_first.size());
-        PSK_HIP(ctx, hipMemcpyAsync(nul_at.data(), d_nul, file_first.size() * 8, hipMemcpyDeviceToHost, st));
-        // the members' check sums (the tables go behind the writing pass's: tab_buf is grown before the pass, not here)
-        std::vector<uint32_t> crc_got(m_begin.size(), 0);
-        if (m_begin.size() != m_len.size() || m_len.size() != m_crc.size())
-            return psk_fail(ctx, PSK_ESTATE, "gz inflate: %zu member starts, %zu member ends (internal error)", m_begin.size(), m_len.size());
-        const bool check_crc = !m_begin.empty() && !env_flag("PSK_GZ_NO_CRC");
-        if (check_crc) {
-            const size_t nm = m_begin.size();
-            uint8_t *mt = tab_buf.as<uint8_t>() + o_members;
-            PSK_HIP(ctx, hipMemcpyAsync(mt, m_begin.data(), nm * 8, hipMemcpyHostToDevice, st));
-            PSK_HIP(ctx, hipMemcpyAsync(mt + ((nm * 8 + 255) & ~(size_t)255), m_len.data(), nm * 8, hipMemcpyHostToDevice, st));
-            uint32_t *d_acc = reinterpret_cast<uint32_t *>(mt + 2 * ((nm * 8 + 255) & ~(size_t)255));
-            PSK_HIP(ctx, hipMemsetAsync(d_acc, 0, nm * 4, st));
-            const uint64_t span = total - GZ_WIN;   // (nothing but empty texts: no launch; the check sums of empty members are 0)
-            if (span)
-                gz_crc_kernel<<<dim3((unsigned)div_up(span, (uint64_t)256 * GZ_CRC_SEG)), dim3(256), 0, st>>>(
-                d_text, reinterpret_cast<const uint64_t *>(mt), reinterpret_cast<const uint64_t *>(mt + ((nm * 8 + 255) & ~(size_t)255)), (int)nm,
-                (uint64_t)GZ_WIN, total, d_acc);
-            PSK_HIP(ctx, hipGetLastError());
-            PSK_HIP(ctx, hipMemcpyAsync(crc_got.data(), d_acc, nm * 4, hipMemcpyDeviceToHost, st));
-        }
-        std::vector<int32_t> r_link(m);
-        PSK_HIP(ctx, hipMemcpyAsync(r_link.data(), t + o_link, m * 4, hipMemcpyDeviceToHost, st));
-        if (guard) {
-            uint32_t *d_damaged = reinterpret_cast<uint32_t *>(t + o_guard);
-            PSK_HIP(ctx, hipMemsetAsync(d_damaged, 0, 4, st));
-            gz_guard_check_kernel<<<dim3(16, 6), dim3(256), 0, st>>>(bands, d_damaged);
-            PSK_HIP(ctx, hipGetLastError());
-            PSK_HIP(ctx, hipMemcpyAsync(&guard_damage, d_damaged, 4, hipMemcpyDeviceToHost, st));
-        }
-        PSK_HIP(ctx, hipStreamSynchronize(st));
-        lap("write + matches + markers + crc");
-        if (guard_damage)
-            return psk_fail(ctx, PSK_ESTATE, "gz inflate: %u bytes of the guard bands around the text / symbol / match buffers were overwritten", guard_damage);
-        for (size_t j = 0; j < m; j++)
-            if (r_link[j] == GZ_ERROR)   // the second decode disagrees with the first: nothing of this file is trusted
-                files[(size_t)ch[(size_t)order[j]].file].device_ok = false;
-        if (check_crc)
-            for (size_t q = 0; q < m_crc.size(); q++)
-                if (crc_got[q] != m_crc[q]) files[(size_t)m_file[q]].device_ok = false;   // zlib will say "incorrect data check"
+    g.laps.on = trace;
+    g.laps.st = g.st;
+    g.laps.last = t_begin;
+    PSK_TRY(g.upload(images_uploaded));
+    PSK_TRY(g.find());
+    PSK_TRY(g.count_rounds());
+    gz_keep_whole_members(g.plan);
+    const GzTextLayout L = gz_layout_text(g.plan);
+    if (!L.members_whole())
+        return psk_fail(ctx, PSK_ESTATE, "gz inflate: %zu member starts, %zu member ends (internal error)", L.m_begin.size(), L.m_len.size());
+    if (!L.order.empty()) {
+        PSK_TRY(g.reserve_text(L));
+        PSK_TRY(g.write_text(L));
+        PSK_TRY(g.check_sums(L));
+        PSK_TRY(g.settle(L));
     }
     if (device_ms) *device_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-    std::vector<int> declined_files;
-    for (int i = 0; i < n; i++) {
-        const GzFile &f = files[(size_t)i];
-        GzInflated &r = res[(size_t)i];
-        r.on_device = f.device_ok;
-        r.bgzf = f.bgzf;
-        r.chunks = (int)f.chain.size();
-        if (f.device_ok) {
-            r.off = f.out_off + guard;   // (relative to the buffer the caller holds: the leading band is in front)
-            r.len = f.out_len;
-            r.first_nul = r.len;
-            if (f.nul_slot >= 0 && (size_t)f.nul_slot < nul_at.size() && nul_at[(size_t)f.nul_slot] != ~0ull) r.first_nul = nul_at[(size_t)f.nul_slot] - f.out_off;
-        } else {
-            declined_files.push_back(i);
-        }
-    }
     // what the device declined goes through zlib on the call's host threads, like a group the device never saw (a
     // run of read sets from an encoder the device route declines -- fixed-Huffman or stored blocks only -- paid one thread)
-    const int declined = (int)declined_files.size();
-    if (declined) PSK_TRY(host_route(declined_files));
+    const std::vector<int> declined = g.results(res);
+    if (!declined.empty()) PSK_TRY(gz_host_route(ctx, data, sizes, declined, host_threads, res));
     if (trace)
-        std::fprintf(stderr, "[psk] gz inflate: %d files, %zu chunks of %zu KB, %d counting round(s), %d declined (zlib on the host); ms:%s\n", n, ch.size(),
-                     chunk >> 10, rounds, declined, phases.c_str());
+        std::fprintf(stderr, "[psk] gz inflate: %d files, %zu chunks of %zu KB, %d counting round(s), %d declined (zlib on the host); ms:%s\n", n, g.plan.ch.size(),
+                     g.chunk >> 10, g.rounds, (int)declined.size(), g.laps.phases.c_str());
     return PSK_OK;
 }
 

@@ -322,7 +322,7 @@ void gz_release(psk_ctx *ctx);   // both, waited for (psk_free)
 int gz_inflate_group(psk_ctx *ctx, int n, const uint8_t *const *data, const size_t *sizes, DevBuf &comp_buf, DevBuf &sym_buf, DevBuf &rec_buf, DevBuf &out_buf,
                      DevBuf &tab_buf, std::vector<GzInflated> &res, double *device_ms, bool host_only = false, int host_threads = 8,
                      hipStream_t on_stream = nullptr, bool images_uploaded = false);
-uint64_t gz_image_layout(int n, const size_t *sizes, uint64_t *at);
+// (gz_image_layout, where the images of a group lie in its device buffer: gz_plan.h)
 int gz_group_on_device(psk_ctx *ctx, int n, const size_t *sizes, bool host_only, int host_threads, bool *on);
 
 // r06: pinned host buffers outlive their context in a process-wide cache (api.hip).  Unpinning is slow -- the 20 slots of the batch
