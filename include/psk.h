@@ -244,6 +244,20 @@ int psk_cx_plan(int n1, int n0, int n_samples, int min_samples, int max_samples,
  * segments).  batch_rows may be NULL.  Host code: no context, no device. */
 int psk_cx_side_shape(uint64_t n_ov, int cpr, uint64_t cap_blocks, uint32_t *blocks, uint64_t *rows_per_block,
                       uint32_t *batch_rows);
+/* What a chi2 scan's parameters leave of the side matrix, by popcount: bit pc (0 ... 255) of feas[4] is set exactly when a
+ * row with pc of the n_samples valid samples present can have a 2 x 2 table that passes the frequency filter and
+ * psk_chi2_pretest -- its a + c lies in [max(0, pc - n_na), min(pc, n1 + n0)], n_na = n_samples - n1 - n0, and for each
+ * sum the two tables at the ends of a's range decide.  n_samples <= 256.  Host code: no context, no device. */
+int psk_cx_pc_plan(int n1, int n0, int n_samples, int min_samples, int max_samples, double thr, uint64_t *feas /* [4] */);
+/* The launch shape of the popcount-filtered side-matrix kernel (chi2_scan_kernel_cx_side_pc): as psk_cx_side_shape, with
+ * one row per lane -- *batch_rows = 64 x the kernel's unroll, whatever the row's width. */
+int psk_cx_pc_shape(uint64_t n_ov, uint64_t cap_blocks, uint32_t *blocks, uint64_t *rows_per_block, uint32_t *batch_rows);
+/* The side-matrix filter of the last chi2 scan launched or repeated on the context: *filtered = 1 when it ran the
+ * popcount-filtered kernel (a side-kernel plan, PSK_CX_PC_FILTER not 0, fewer feasible rows than overflow rows),
+ * *rows_feasible = the overflow rows whose popcount psk_cx_pc_plan leaves (all of them when the plan was not asked:
+ * no side-kernel plan, or the knob off), *rows_overflow = the rows of the side matrix; all 0 for a scan that did not
+ * take the exception-coded path.  Measurement and tests only.  Any pointer may be NULL. */
+int psk_last_scan_filter(const psk_ctx *ctx, int *filtered, uint64_t *rows_feasible, uint64_t *rows_overflow);
 /* The plan of the last chi2 scan launched or repeated on the context: *encoded = 1 when it took the exception-coded path
  * (else the other two are 0), *class_mask as psk_cx_plan gives it, *slots_skipped = 1 when the launch read only the side
  * matrix of overflow rows.  Measurement and tests only.  Any pointer may be NULL. */

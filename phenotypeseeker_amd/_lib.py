@@ -68,6 +68,9 @@ _SIGNATURES = {
     "psk_chi2_pretest": (c.c_int, [c.c_double] * 5),
     "psk_cx_plan": (c.c_int, [c.c_int] * 5 + [c.c_double, c.POINTER(c.c_uint32), _u64p]),
     "psk_cx_side_shape": (c.c_int, [c.c_uint64, c.c_int, c.c_uint64, c.POINTER(c.c_uint32), _u64p, c.POINTER(c.c_uint32)]),
+    "psk_cx_pc_plan": (c.c_int, [c.c_int] * 5 + [c.c_double, _u64p]),
+    "psk_cx_pc_shape": (c.c_int, [c.c_uint64, c.c_uint64, c.POINTER(c.c_uint32), _u64p, c.POINTER(c.c_uint32)]),
+    "psk_last_scan_filter": (c.c_int, [c.c_void_p, c.POINTER(c.c_int), _u64p, _u64p]),
     "psk_last_scan_plan": (c.c_int, [c.c_void_p, c.POINTER(c.c_int), c.POINTER(c.c_uint32), c.POINTER(c.c_int)]),
     "psk_last_scan_ms": (c.c_double, [c.c_void_p]),
     "psk_rescan_timed": (c.c_int, [c.c_void_p, c.c_int, c.POINTER(c.c_double)]),

@@ -25,6 +25,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <vector>
 
 namespace {
 
@@ -377,6 +378,117 @@ __global__ __launch_bounds__(SC_THREADS) void chi2_scan_kernel_cx_side(const CxS
 #endif
 }
 
+// ---- the side matrix through its popcounts: the rows a scan's parameters cannot rule out --------------------------
+// A row's table (a, c) has a + c within n_na of its popcount, and for a fixed a + c the pre-test is decided at the two
+// ends of a's range (cx_pc_plan), so a popcount none of whose sums passes the filter and the pre-test rules the row out
+// before it is read: the encoder's 2-byte popcount (cx_ov_pc) is all the kernel loads of it.  A lane owns a row: lane l
+// of a wave loads the popcounts of rows b * 64 U + 64 j + l, j = 0 .. U - 1, back to back (128 contiguous bytes per wave
+// instruction, 64 U rows per round), then walks j; a row whose bit of `feas` is set -- a live row -- loads its own CPR
+// chunks, counts them against the mask words (scalars from the arguments: no shuffle) and takes SideRows::evaluate's
+// path from there: frequency filter and chi2_pretest in line, the exact decision as one copy per batch.  A row that is
+// not live is left out by that predicate alone.  Batches go to the waves grid-stride with the next batch's popcounts
+// in flight, as in chi2_scan_kernel_cx_side.
+#ifndef PSK_CX_PC_NT
+#define PSK_CX_PC_NT 0   // nontemporal hint on the popcount loads
+#endif
+#ifndef PSK_CX_PC_GRID_MULT
+#define PSK_CX_PC_GRID_MULT 8   // workgroups per CU when PSK_GRID_MULT is unset
+#endif
+struct CxSidePcArgs {
+    CxSideArgs s;
+    const uint16_t *ov_pc;       // popcount of every side-matrix row over the valid samples
+    uint64_t feas[4];            // bit pc: a row of that popcount can be a candidate
+};
+static_assert(sizeof(CxSidePcArgs) <= 256, "chi2_scan_kernel_cx_side_pc's arguments are meant to stay small");
+
+template <int CPR>
+struct PcRows {
+    static constexpr int U = CX_PC_UNROLL;
+    const u32x4 *ov;
+    const uint32_t *ov_row;
+    const uint16_t *ov_pc;
+    uint64_t n_ov;
+    uint64_t f0, f1, f2, f3;               // feas
+    uint64_t m1[2 * CPR], m0[2 * CPR];     // the mask words of a row's chunks
+    int lane;
+
+    __device__ __forceinline__ PcRows(const CxSidePcArgs &X)
+        : ov(X.s.ov), ov_row(X.s.ov_row), ov_pc(X.ov_pc), n_ov(X.s.n_ov), f0(X.feas[0]), f1(X.feas[1]), f2(X.feas[2]), f3(X.feas[3])
+    {
+        lane = threadIdx.x & 63;
+#pragma unroll
+        for (int i = 0; i < 2 * CPR; i++) { m1[i] = X.s.m1[i]; m0[i] = X.s.m0[i]; }
+    }
+    __device__ __forceinline__ uint64_t n_batches() const { return (n_ov + 64 * U - 1) / (64 * U); }
+    __device__ __forceinline__ uint64_t row(uint64_t b, int j) const { return (b * U + j) * 64 + lane; }
+    __device__ __forceinline__ void load(uint32_t (&pc)[U], uint64_t b) const
+    {
+#pragma unroll
+        for (int j = 0; j < U; j++) {
+            const uint64_t r = row(b, j);
+            pc[j] = r < n_ov ? (PSK_CX_PC_NT ? __builtin_nontemporal_load(&ov_pc[r]) : ov_pc[r]) : 0u;
+        }
+    }
+    __device__ __forceinline__ void evaluate(const uint32_t (&pc)[U], uint64_t b, const ScanCuts &K, const ScanSink &S) const
+    {
+        uint32_t ac[U], pend = 0;   // a | c << 16 of the batch's live rows; bit j: row j passed the filter and the pre-test
+#pragma unroll
+        for (int j = 0; j < U; j++) {
+            const uint64_t r = row(b, j);
+            const uint32_t w = pc[j] >> 6;
+            // the 4-way select as masks: a chain of selects of the four words is turned into a table on the stack
+            const uint64_t word = (w == 0 ? f0 : 0ull) | (w == 1 ? f1 : 0ull) | (w == 2 ? f2 : 0ull) | (w == 3 ? f3 : 0ull);
+            const bool live = r < n_ov && ((word >> (pc[j] & 63u)) & 1ull);
+            uint32_t a = 0, c = 0;
+            if (live) {
+#pragma unroll
+                for (int g = 0; g < CPR; g++) {
+                    const u32x4 x = PSK_CX_SIDE_NT ? __builtin_nontemporal_load(&ov[r * CPR + g]) : ov[r * CPR + g];
+                    const uint64_t xa = ((uint64_t)x.y << 32) | x.x, xb = ((uint64_t)x.w << 32) | x.z;
+                    a += __popcll(xa & m1[2 * g]) + __popcll(xb & m1[2 * g + 1]);
+                    c += __popcll(xa & m0[2 * g]) + __popcll(xb & m0[2 * g + 1]);
+                }
+            }
+            // chi2_scan_kernel MODE 0's on_row
+            const int n_w = (int)(a + c);
+            const int n_wo = (K.n1 - (int)a) + (K.n0 - (int)c);
+            const bool freq_ok = live && !(n_w < K.min_samples || n_wo < 2 || n_w > K.max_samples);
+            const double A = (double)a, B = (double)(K.n1 - (int)a), C = (double)c, D = (double)(K.n0 - (int)c);
+            ac[j] = a | (c << 16);
+            if (freq_ok && chi2_pretest(A, B, C, D, K.thr)) pend |= 1u << j;
+        }
+        while (pend) {   // the exact decision, one copy of it (SideRows::evaluate)
+            const int j = __builtin_ctz(pend);
+            pend &= pend - 1;
+            uint32_t v = ac[0];
+#pragma unroll
+            for (int i = 1; i < U; i++) v = j == i ? ac[i] : v;
+            chi2_evaluate(K, S, ov_row[row(b, j)], (int)(v & 0xffffu), (int)(v >> 16));
+        }
+    }
+};
+
+template <int CPR>
+__global__ __launch_bounds__(SC_THREADS) void chi2_scan_kernel_cx_side_pc(const CxSidePcArgs X)
+{
+    const PcRows<CPR> R(X);
+    const uint64_t stride = (uint64_t)gridDim.x * CX_SIDE_WAVES;
+    const uint64_t n_batches = R.n_batches();
+    uint64_t b = (uint64_t)blockIdx.x * CX_SIDE_WAVES + (threadIdx.x >> 6);
+    uint32_t pa[CX_PC_UNROLL], pb[CX_PC_UNROLL];
+    if (b < n_batches) R.load(pa, b);
+    while (b < n_batches) {
+        if (b + stride < n_batches) R.load(pb, b + stride);
+        R.evaluate(pa, b, X.s.cut, X.s.sink);
+        b += stride;
+        if (!(b < n_batches)) break;
+        if (b + stride < n_batches) R.load(pa, b + stride);
+        R.evaluate(pb, b, X.s.cut, X.s.sink);
+        b += stride;
+    }
+    publish_segment_once(X.s.sink);
+}
+
 // Second pass of the weighted chi2 scan: one workgroup per result segment, one candidate per lane.  The 2 x 2 table is
 // summed again exactly as the reference does it (modeling.py:809-823: every sample in order adds its weight to ONE of
 // the four cells; here the other three get + 0.0, and a weight times 1.0 or 0.0 is exact, so one fma per cell IS that
@@ -514,6 +626,36 @@ void cx_plan(int n1, int n0, int n_samples, int min_samples, int max_samples, do
     }
 }
 
+// What a scan's parameters leave of the side matrix, by popcount.  Bit pc of feas (pc <= 255: a side-matrix row has
+// CX_MAX_E < pc < n_samples - CX_MAX_E) is set exactly when a row of that popcount over the valid samples can have a
+// candidate table: its s = a + c is pc less its present NA samples, s in [max(0, pc - n_na), min(pc, n1 + n0)]; the
+// frequency filter depends on s alone; and with s fixed det = (n1 + n0) a - n1 s, so chi2_pretest's left side is convex
+// in a while its right side does not depend on a -- some table of that s passes exactly when one at a = max(0, s - n0)
+// or a = min(s, n1) does.  (Everything in the left side is an integer below 2^53: exact, so "convex" holds in the
+// doubles.)  Two pre-tests per s, n1 + n0 + 1 values of s.
+void cx_pc_plan(int n1, int n0, int n_samples, int min_samples, int max_samples, double thr, uint64_t feas[4])
+{
+    const int T = n1 + n0, n_na = n_samples - T;
+    std::vector<int> ok_upto(T + 2, 0);   // ok_upto[s + 1]: sums <= s that pass
+    for (int s = 0; s <= T; s++) {
+        const bool freq_ok = !(s < min_samples || T - s < 2 || s > max_samples);
+        bool ok = false;
+        if (freq_ok) {
+            const int ends[2] = {std::max(0, s - n0), std::min(s, n1)};
+            for (int e = 0; e < 2 && !ok; e++) {
+                const int a = ends[e], c = s - a;
+                ok = chi2_pretest((double)a, (double)(n1 - a), (double)c, (double)(n0 - c), thr);
+            }
+        }
+        ok_upto[s + 1] = ok_upto[s] + (ok ? 1 : 0);
+    }
+    feas[0] = feas[1] = feas[2] = feas[3] = 0;
+    for (int pc = 0; pc < 256; pc++) {
+        const int lo = std::max(0, pc - n_na), hi = std::min(pc, T);
+        if (lo <= hi && ok_upto[hi + 1] - ok_upto[lo] > 0) feas[pc >> 6] |= 1ull << (pc & 63);
+    }
+}
+
 // Workgroups of the two parts in proportion to their bytes, under scan_grid's cap; x.slot_blocks = the first part's,
 // x.ov_blocks the second's.  With no feasible class (x.class_mask == 0) the slots get none and the side matrix the whole
 // cap.  At least SC_NSEG workgroups: every result segment needs one to publish its count and re-arm its counter.
@@ -544,6 +686,8 @@ dim3 cx_grid(const psk_ctx *ctx, CxScanArgs &x, int cpr)
 
 // most workgroups of chi2_scan_kernel_cx_side: PSK_GRID_MULT per CU when set, else the kernel's own multiple
 uint64_t cx_side_grid_cap(const psk_ctx *ctx) { return (uint64_t)(ctx->n_cu > 0 ? ctx->n_cu : 256) * (ctx->grid_mult ? ctx->grid_mult : PSK_CX_SIDE_GRID_MULT); }
+// ... and of chi2_scan_kernel_cx_side_pc
+uint64_t cx_pc_grid_cap(const psk_ctx *ctx) { return (uint64_t)(ctx->n_cu > 0 ? ctx->n_cu : 256) * (ctx->grid_mult ? ctx->grid_mult : PSK_CX_PC_GRID_MULT); }
 
 // the most rows one workgroup of chi2_scan_kernel_cx visits
 uint64_t cx_rows_per_block(const CxScanArgs &x, int cpr)
@@ -560,8 +704,8 @@ uint64_t cx_rows_per_block(const CxScanArgs &x, int cpr)
 // One chi2 scan as the host launches it: the dense kernels' arguments, and the exception-coded path when it runs
 struct Chi2Launch {
     CxScanArgs x;      // x.s: every form's arguments; the rest: chi2_scan_kernel_cx's
-    CxSideArgs side;   // chi2_scan_kernel_cx_side's, when the plan says so (side_kernel)
-    bool compact = false, side_kernel = false;
+    CxSidePcArgs side;   // chi2_scan_kernel_cx_side's (side.s) when the plan says so (side_kernel); all of it: ..._side_pc's (filtered)
+    bool compact = false, side_kernel = false, filtered = false;
     int mode = 0;      // of the dense kernels (pick_chi2_mode)
     int cpr = 0;
     dim3 grid;
@@ -570,9 +714,14 @@ struct Chi2Launch {
 void launch_chi2_any(psk_ctx *ctx, const Chi2Launch &L, TimedBy ev)
 {
     const ScanArgs &a = L.x.s;
+    if (L.compact && L.side_kernel && L.filtered) {
+        if (L.cpr == 1) launch_timed(chi2_scan_kernel_cx_side_pc<1>, L.grid, SC_THREADS, 0, ctx->stream, ev, L.side);
+        else launch_timed(chi2_scan_kernel_cx_side_pc<2>, L.grid, SC_THREADS, 0, ctx->stream, ev, L.side);
+        return;
+    }
     if (L.compact && L.side_kernel) {
-        if (L.cpr == 1) launch_timed(chi2_scan_kernel_cx_side<1>, L.grid, SC_THREADS, 0, ctx->stream, ev, L.side);
-        else launch_timed(chi2_scan_kernel_cx_side<2>, L.grid, SC_THREADS, 0, ctx->stream, ev, L.side);
+        if (L.cpr == 1) launch_timed(chi2_scan_kernel_cx_side<1>, L.grid, SC_THREADS, 0, ctx->stream, ev, L.side.s);
+        else launch_timed(chi2_scan_kernel_cx_side<2>, L.grid, SC_THREADS, 0, ctx->stream, ev, L.side.s);
         return;
     }
     if (L.compact) {
@@ -643,8 +792,11 @@ static int fill_chi2_args(psk_ctx *ctx, Chi2Launch &CL, int set, bool build_tabl
         x.n_ov = ctx->cx_n_ov;
         int side_on = 1;   // read per scan: A/B runs and tests in one build
         PSK_TRY(env_choice(ctx, "PSK_CX_SIDE_KERNEL", {0, 1}, &side_on));
+        int pc_on = 1;
+        PSK_TRY(env_choice(ctx, "PSK_CX_PC_FILTER", {0, 1}, &pc_on));
         CxPlanKey key;
         key.M = a.M; key.n_ov = x.n_ov; key.cap = scan_grid_cap(ctx); key.side_cap = cx_side_grid_cap(ctx);
+        key.pc_cap = cx_pc_grid_cap(ctx); key.pc_filter = pc_on;
         memcpy(&key.thr_bits, &a.cut.thr, 8);
         key.n1 = a.cut.n1; key.n0 = a.cut.n0; key.n_samples = ctx->n_samples;
         key.min_samples = a.cut.min_samples; key.max_samples = a.cut.max_samples; key.side_kernel = side_on;
@@ -654,7 +806,24 @@ static int fill_chi2_args(psk_ctx *ctx, Chi2Launch &CL, int set, bool build_tabl
             cx_plan(a.cut.n1, a.cut.n0, ctx->n_samples, a.cut.min_samples, a.cut.max_samples, a.cut.thr, &pl.class_mask, pl.corner);
             pl.side = side_on && pl.class_mask == 0;
             uint64_t rows_per_block;
-            if (pl.side) {
+            pl.filtered = false;
+            pl.rows_feasible = x.n_ov;
+            pl.feas[0] = pl.feas[1] = pl.feas[2] = pl.feas[3] = ~0ull;
+            if (pl.side && pc_on) {
+                cx_pc_plan(a.cut.n1, a.cut.n0, ctx->n_samples, a.cut.min_samples, a.cut.max_samples, a.cut.thr, pl.feas);
+                pl.rows_feasible = 0;
+                for (size_t pc = 0; pc < ctx->cx_pc_hist.size() && pc < 256; pc++)
+                    if ((pl.feas[pc >> 6] >> (pc & 63)) & 1ull) pl.rows_feasible += ctx->cx_pc_hist[pc];
+                pl.filtered = pl.rows_feasible < x.n_ov;
+#ifdef PSK_CX_PC_FORCE   // A/B builds: the filtered form whatever the count (the all-feasible comparison of the r15 table)
+                pl.filtered = true;
+#endif
+            }
+            if (pl.filtered) {
+                const cx_side_shape_t sh = cx_pc_shape(x.n_ov, key.pc_cap);
+                pl.grid = sh.blocks; pl.slot_blocks = 0; pl.ov_blocks = sh.blocks;
+                rows_per_block = sh.rows_per_block;
+            } else if (pl.side) {
                 const cx_side_shape_t sh = cx_side_shape(x.n_ov, CL.cpr, key.side_cap);
                 pl.grid = sh.blocks; pl.slot_blocks = 0; pl.ov_blocks = sh.blocks;
                 rows_per_block = sh.rows_per_block;
@@ -672,12 +841,17 @@ static int fill_chi2_args(psk_ctx *ctx, Chi2Launch &CL, int set, bool build_tabl
         x.slot_blocks = pl.slot_blocks; x.ov_blocks = pl.ov_blocks;
         CL.grid = dim3(pl.grid);
         CL.side_kernel = pl.side;
+        CL.filtered = pl.filtered;
         ctx->cx_last_plan = true;
+        ctx->cx_last_filtered = pl.filtered;
+        ctx->cx_last_rows_feasible = pl.rows_feasible;
         ctx->cx_last_class_mask = pl.class_mask;
         ctx->cx_last_skipped = pl.slot_blocks == 0;
         PSK_TRY(bind_results(ctx, a.sink, pl.seg_cap, set));
         if (pl.side) {
-            CxSideArgs &sd = CL.side;
+            CxSideArgs &sd = CL.side.s;
+            CL.side.ov_pc = ctx->cx_ov_pc.as<uint16_t>();
+            memcpy(CL.side.feas, pl.feas, sizeof(CL.side.feas));
             sd.ov = x.ov; sd.ov_row = x.ov_row; sd.n_ov = x.n_ov;
             memcpy(sd.m1, a.m1_inl, sizeof(sd.m1));
             memcpy(sd.m0, a.m0_inl, sizeof(sd.m0));
@@ -847,6 +1021,32 @@ extern "C" int psk_cx_side_shape(uint64_t n_ov, int cpr, uint64_t cap_blocks, ui
     *blocks = sh.blocks;
     *rows_per_block = sh.rows_per_block;
     if (batch_rows) *batch_rows = sh.batch_rows;
+    return PSK_OK;
+}
+
+extern "C" int psk_cx_pc_plan(int n1, int n0, int n_samples, int min_samples, int max_samples, double thr, uint64_t *feas)
+{
+    if (n1 < 0 || n0 < 0 || n_samples < 0 || n_samples > CX_MAX_SAMPLES || n1 + n0 > n_samples || !feas) return PSK_EINVAL;
+    cx_pc_plan(n1, n0, n_samples, min_samples, max_samples, thr, feas);
+    return PSK_OK;
+}
+
+extern "C" int psk_cx_pc_shape(uint64_t n_ov, uint64_t cap_blocks, uint32_t *blocks, uint64_t *rows_per_block, uint32_t *batch_rows)
+{
+    if (cap_blocks < 1 || cap_blocks > 0xffffffffull || !blocks || !rows_per_block) return PSK_EINVAL;
+    const cx_side_shape_t sh = cx_pc_shape(n_ov, cap_blocks);
+    *blocks = sh.blocks;
+    *rows_per_block = sh.rows_per_block;
+    if (batch_rows) *batch_rows = sh.batch_rows;
+    return PSK_OK;
+}
+
+extern "C" int psk_last_scan_filter(const psk_ctx *ctx, int *filtered, uint64_t *rows_feasible, uint64_t *rows_overflow)
+{
+    if (!ctx) return PSK_EINVAL;
+    if (filtered) *filtered = ctx->cx_last_plan && ctx->cx_last_filtered ? 1 : 0;
+    if (rows_feasible) *rows_feasible = ctx->cx_last_plan ? ctx->cx_last_rows_feasible : 0;
+    if (rows_overflow) *rows_overflow = ctx->cx_last_plan ? ctx->cx_n_ov : 0;
     return PSK_OK;
 }
 

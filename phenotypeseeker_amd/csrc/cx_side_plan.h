@@ -38,3 +38,28 @@ inline cx_side_shape_t cx_side_shape(uint64_t n_ov, int cpr, uint64_t cap_blocks
     s.rows_per_block = passes * CX_SIDE_WAVES * s.batch_rows;
     return s;
 }
+
+// ---- the popcount-filtered sweep (chi2_scan_kernel_cx_side_pc) -----------------------------------------------------
+// A row is one lane: a wave step covers 64 rows and a batch CX_PC_UNROLL steps -- the 2-byte popcounts a wave loads
+// before it looks at any row.  Batches are dealt to the waves grid-stride exactly as above.
+#ifndef PSK_CX_PC_UNROLL
+#define PSK_CX_PC_UNROLL 8
+#endif
+constexpr int CX_PC_UNROLL = PSK_CX_PC_UNROLL;       // 2-byte loads in flight per lane and register set
+static_assert(CX_PC_UNROLL == 4 || CX_PC_UNROLL == 8, "a batch is 256 or 512 rows");
+
+inline cx_side_shape_t cx_pc_shape(uint64_t n_ov, uint64_t cap_blocks)
+{
+    const uint64_t batch_rows = 64 * (uint64_t)CX_PC_UNROLL;
+    const uint64_t batches = (n_ov + batch_rows - 1) / batch_rows;
+    uint64_t blocks = (batches + CX_SIDE_WAVES - 1) / CX_SIDE_WAVES;
+    if (blocks > cap_blocks) blocks = cap_blocks;
+    if (blocks < CX_SIDE_NSEG) blocks = CX_SIDE_NSEG;
+    const uint64_t waves = blocks * CX_SIDE_WAVES;
+    const uint64_t passes = (batches + waves - 1) / waves;   // batches of wave 0, the most any wave takes
+    cx_side_shape_t s;
+    s.blocks = (uint32_t)blocks;
+    s.batch_rows = (uint32_t)batch_rows;
+    s.rows_per_block = passes * CX_SIDE_WAVES * batch_rows;
+    return s;
+}

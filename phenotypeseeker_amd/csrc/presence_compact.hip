@@ -9,10 +9,14 @@
 //
 // Two passes over the dense matrix: the first counts the overflow rows of every workgroup (whose exclusive scan places
 // them), the host decides from the total whether to keep a copy (CX_MAX_SHARE, CX_MAX_OVF_DIV), the second writes slots and side matrix.
-// PSK_TRACE=1 prints the decision and the time of the build.
+// Beside each side-matrix row the encoder keeps its popcount (cx_ov_pc, u16) and, on the host, how many rows have each
+// popcount (cx_pc_hist): a scan's parameters rule out whole popcounts (cx_pc_plan, assoc_scan.hip), and the scan then
+// reads 2 bytes of such a row instead of the row.
+// PSK_TRACE=1 prints the decision, the time of the build and the popcounts' non-zero range.
 #include "dev_utils.h"
 #include "psk_internal.h"
 
+#include <algorithm>
 #include <chrono>
 
 namespace {
@@ -54,7 +58,8 @@ __global__ __launch_bounds__(CX_THREADS) void cx_count_kernel(const uint64_t *__
 // offs: exclusive scan of cx_count_kernel's counts (same grid)
 __global__ __launch_bounds__(CX_THREADS) void cx_encode_kernel(const uint64_t *__restrict__ bits, uint64_t M, int wpr, int n,
                                                               const uint32_t *__restrict__ offs, uint64_t *__restrict__ slots,
-                                                              uint64_t *__restrict__ ov, uint32_t *__restrict__ ov_row)
+                                                              uint64_t *__restrict__ ov, uint32_t *__restrict__ ov_row,
+                                                              uint16_t *__restrict__ ov_pc)
 {
     __shared__ uint32_t s_wave[CX_THREADS / 64];
     const uint64_t r = (uint64_t)blockIdx.x * CX_THREADS + threadIdx.x;
@@ -71,6 +76,7 @@ __global__ __launch_bounds__(CX_THREADS) void cx_encode_kernel(const uint64_t *_
         const uint64_t j = (uint64_t)offs[blockIdx.x] + pos;
         for (int c = 0; c < wpr; c++) ov[j * wpr + c] = w[c];
         ov_row[j] = (uint32_t)r;
+        ov_pc[j] = (uint16_t)pc;
         slots[r] = CX_HDR_OVF;
         return;
     }
@@ -89,6 +95,22 @@ __global__ __launch_bounds__(CX_THREADS) void cx_encode_kernel(const uint64_t *_
     slots[r] = slot;
 }
 
+// hist[pc] += rows of that popcount: a histogram per workgroup in LDS, then one global atomic per non-empty bin
+constexpr int CX_HIST_BINS = CX_MAX_SAMPLES + 1;
+__global__ __launch_bounds__(CX_THREADS) void cx_pc_hist_kernel(const uint16_t *__restrict__ ov_pc, uint64_t n_ov, uint32_t *__restrict__ hist)
+{
+    __shared__ uint32_t s_hist[CX_HIST_BINS];
+    for (int i = threadIdx.x; i < CX_HIST_BINS; i += CX_THREADS) s_hist[i] = 0;
+    __syncthreads();
+    for (uint64_t j = (uint64_t)blockIdx.x * CX_THREADS + threadIdx.x; j < n_ov; j += (uint64_t)gridDim.x * CX_THREADS) {
+        const uint32_t pc = ov_pc[j];
+        atomicAdd(&s_hist[pc < CX_HIST_BINS ? pc : CX_HIST_BINS - 1], 1u);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < CX_HIST_BINS; i += CX_THREADS)
+        if (s_hist[i]) atomicAdd(&hist[i], s_hist[i]);
+}
+
 }  // namespace
 
 void compact_release(psk_ctx *ctx)
@@ -96,6 +118,8 @@ void compact_release(psk_ctx *ctx)
     dev_release(ctx->cx_slots);
     dev_release(ctx->cx_ov);
     dev_release(ctx->cx_ov_row);
+    dev_release(ctx->cx_ov_pc);
+    ctx->cx_pc_hist.clear();
     ctx->cx_valid = false;
     ctx->cx_n_ov = 0;
     ctx->cx_plan.valid = false;
@@ -114,7 +138,7 @@ int compact_encode(psk_ctx *ctx)
     }
     const auto t0 = std::chrono::steady_clock::now();
     const uint64_t nb = div_up(M, CX_THREADS);
-    PSK_TRY(dev_reserve(ctx, ctx->flags, nb * 4));
+    PSK_TRY(dev_reserve(ctx, ctx->flags, std::max<uint64_t>(nb, CX_HIST_BINS) * 4));   // the counts, then the histogram
     PSK_TRY(dev_reserve(ctx, ctx->misc, 64));
     uint32_t *cnt = ctx->flags.as<uint32_t>(), *d_total = ctx->misc.as<uint32_t>() + 6;
     const uint64_t *bits = ctx->bits.as<uint64_t>();
@@ -135,9 +159,22 @@ int compact_encode(psk_ctx *ctx)
     PSK_TRY(dev_reserve(ctx, ctx->cx_slots, (M + 1) / 2 * 16));
     PSK_TRY(dev_reserve(ctx, ctx->cx_ov, (n_ov ? n_ov : 1) * (uint64_t)wpr * 8));
     PSK_TRY(dev_reserve(ctx, ctx->cx_ov_row, (n_ov ? n_ov : 1) * 4ull));
+    PSK_TRY(dev_reserve(ctx, ctx->cx_ov_pc, (n_ov ? n_ov : 1) * 2ull));
     cx_encode_kernel<<<(unsigned)nb, CX_THREADS, 0, ctx->stream>>>(bits, M, wpr, n, cnt, ctx->cx_slots.as<uint64_t>(),
-                                                                  ctx->cx_ov.as<uint64_t>(), ctx->cx_ov_row.as<uint32_t>());
+                                                                  ctx->cx_ov.as<uint64_t>(), ctx->cx_ov_row.as<uint32_t>(),
+                                                                  ctx->cx_ov_pc.as<uint16_t>());
     PSK_HIP(ctx, hipGetLastError());
+    // the rows of each popcount, once per matrix (the encode kernel is done with the counts: same stream)
+    uint32_t hist[CX_HIST_BINS];
+    PSK_HIP(ctx, hipMemsetAsync(cnt, 0, sizeof(hist), ctx->stream));
+    if (n_ov) {
+        const uint64_t hb = std::min<uint64_t>(div_up(n_ov, CX_THREADS * 16), 1024);
+        cx_pc_hist_kernel<<<(unsigned)hb, CX_THREADS, 0, ctx->stream>>>(ctx->cx_ov_pc.as<uint16_t>(), n_ov, cnt);
+        PSK_HIP(ctx, hipGetLastError());
+    }
+    PSK_HIP(ctx, hipMemcpyAsync(hist, cnt, sizeof(hist), hipMemcpyDeviceToHost, ctx->stream));
+    PSK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->cx_pc_hist.assign(hist, hist + n + 1);
     ctx->cx_n_ov = n_ov;
     ctx->cx_valid = true;
     if (trace) {
@@ -145,6 +182,11 @@ int compact_encode(psk_ctx *ctx)
         fprintf(stderr, "[psk] compact rows: %.3f ms, %.1f MB of slots + %.1f MB of overflow rows (%llu of %llu) = %.3f of the dense bytes\n",
                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), M * 8 / 1e6,
                 n_ov * (wpr * 8.0 + 4) / 1e6, (unsigned long long)n_ov, (unsigned long long)M, enc / dense);
+        int lo = n + 1, hi = -1;
+        for (int pc = 0; pc <= n; pc++)
+            if (ctx->cx_pc_hist[pc]) { lo = std::min(lo, pc); hi = pc; }
+        if (hi < 0) fprintf(stderr, "[psk] compact rows: no overflow row, empty popcount histogram\n");
+        else fprintf(stderr, "[psk] compact rows: overflow rows have popcounts %d ... %d\n", lo, hi);
     }
     return PSK_OK;
 }

@@ -129,13 +129,13 @@ struct ScanSlot {
 // the result segments' size come to for `key`, which names everything they are a function of -- none of it derived from
 // WHICH samples are cases.  A scan with another key recomputes; a new matrix or encoded copy drops the plan.
 struct CxPlanKey {
-    uint64_t M = 0, n_ov = 0, cap = 0, side_cap = 0, thr_bits = 0;
-    int n1 = 0, n0 = 0, n_samples = 0, min_samples = 0, max_samples = 0, side_kernel = 0;
+    uint64_t M = 0, n_ov = 0, cap = 0, side_cap = 0, pc_cap = 0, thr_bits = 0;
+    int n1 = 0, n0 = 0, n_samples = 0, min_samples = 0, max_samples = 0, side_kernel = 0, pc_filter = 0;
     bool operator==(const CxPlanKey &o) const
     {
-        return M == o.M && n_ov == o.n_ov && cap == o.cap && side_cap == o.side_cap && thr_bits == o.thr_bits && n1 == o.n1 &&
-               n0 == o.n0 && n_samples == o.n_samples && min_samples == o.min_samples && max_samples == o.max_samples &&
-               side_kernel == o.side_kernel;
+        return M == o.M && n_ov == o.n_ov && cap == o.cap && side_cap == o.side_cap && pc_cap == o.pc_cap && thr_bits == o.thr_bits &&
+               n1 == o.n1 && n0 == o.n0 && n_samples == o.n_samples && min_samples == o.min_samples && max_samples == o.max_samples &&
+               side_kernel == o.side_kernel && pc_filter == o.pc_filter;
     }
 };
 struct CxPlan {
@@ -144,8 +144,13 @@ struct CxPlan {
     uint32_t class_mask = 0;
     uint64_t corner[2] = {0, 0};
     bool side = false;               // launched as chi2_scan_kernel_cx_side (no feasible class, PSK_CX_SIDE_KERNEL on)
-    uint32_t grid = 0, slot_blocks = 0, ov_blocks = 0;
+    uint32_t grid = 0, slot_blocks = 0, ov_blocks = 0;   // filtered: grid = ov_blocks = cx_pc_shape's workgroups
     uint64_t seg_cap = 0;            // entries per result segment
+    // the popcounts a side-matrix row must have for some table of it to be a candidate (cx_pc_plan), and how many rows
+    // have one (the encoder's histogram): with fewer than all, chi2_scan_kernel_cx_side_pc reads only those (filtered)
+    uint64_t feas[4] = {0, 0, 0, 0};
+    bool filtered = false;
+    uint64_t rows_feasible = 0;
 };
 
 struct psk_ctx {
@@ -221,11 +226,14 @@ struct psk_ctx {
     // exception-coded copy of `bits` for the unweighted chi2 scan (presence_compact.hip): one 8-byte slot per row, and the
     // rows with more than CX_MAX_E exceptions as dense rows of a side matrix with their row ids.  cx_valid = false: none
     DevBuf cx_slots, cx_ov, cx_ov_row;
+    DevBuf cx_ov_pc;                 // u16 per side-matrix row: its popcount over the valid samples
+    std::vector<uint64_t> cx_pc_hist;   // [n_samples + 1] side-matrix rows of each popcount (host copy, made by the encoder)
     bool cx_valid = false;
     uint64_t cx_n_ov = 0;
     // the plan of the last chi2 scan set up (cx_plan, assoc_scan.hip): did it take the exception-coded path, which header
     // classes were feasible, and was the slot stream left unread (psk_last_scan_plan)
-    bool cx_last_plan = false, cx_last_skipped = false;
+    bool cx_last_plan = false, cx_last_skipped = false, cx_last_filtered = false;
+    uint64_t cx_last_rows_feasible = 0;
     uint32_t cx_last_class_mask = 0;
     CxPlan cx_plan;                  // dropped wherever the matrix or its encoded copy changes (compact_release, compact_encode, psk_begin)
 

@@ -370,6 +370,14 @@ class PskContext:
                     "psk_last_scan_plan")
         return bool(enc.value), mask.value, bool(skipped.value)
 
+    def last_scan_filter(self):
+        """(the last chi2 scan ran the popcount-filtered side-matrix kernel, overflow rows whose popcount its plan
+        leaves, overflow rows): psk_last_scan_filter"""
+        filt, feas, n_ov = ctypes.c_int(), ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(self._lib.psk_last_scan_filter(self._h, ctypes.byref(filt), ctypes.byref(feas), ctypes.byref(n_ov)),
+                    "psk_last_scan_filter")
+        return bool(filt.value), feas.value, n_ov.value
+
     def last_scan_ms(self):
         return self._lib.psk_last_scan_ms(self._h)
 
@@ -593,3 +601,14 @@ def frame_sequence(data):
     if n < 0:
         raise PskError("psk_frame_sequence failed: %d" % n)
     return out[:n].tobytes()
+
+
+def cx_pc_plan(n1, n0, n_samples, min_samples, max_samples, thr):
+    """The popcounts (a set of ints below 256) a side-matrix row may have for a chi2 scan with these parameters to keep
+    it (psk_cx_pc_plan: host code, no device)."""
+    lib = _lib.load()
+    feas = (ctypes.c_uint64 * 4)()
+    rc = lib.psk_cx_pc_plan(n1, n0, n_samples, min_samples, max_samples, thr, feas)
+    if rc < 0:
+        raise PskError("psk_cx_pc_plan failed: %d" % rc)
+    return {pc for pc in range(256) if (feas[pc >> 6] >> (pc & 63)) & 1}
