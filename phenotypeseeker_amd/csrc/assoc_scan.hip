@@ -1,4 +1,8 @@
-// a4-a7: per-k-mer association scans over the bit-packed presence matrix -- the chi2 scans.
+// a4-a7: the chi2 scan KERNELS over the bit-packed presence matrix, and nothing else: every chi2 kernel, the weighted
+// finalize pass, their device helpers, their compile-time tuning macros, and the launch functions that instantiate them
+// (launch_chi2_any, chi2_launch.h, is how chi2_driver.hip reaches them).  What the host decides about a scan is
+// chi2_plan.h; the driver and the exported calls are chi2_driver.hip.  bench.py quotes a committed HBM traffic figure only
+// for the sha256 of THIS file, the scan kernel's source: host-side edits live elsewhere and leave the figure standing.
 //
 // chi2_scan_kernel   replaces phenotypes.get_kmers_tested / conduct_chi_squared_test and helpers
 //                    (modeling.py:677-714, :759-858)
@@ -18,14 +22,10 @@
 // Exactness: the 2x2 table is integer (unit weights), and the statistic is evaluated with the
 // reference's own operation order in IEEE double (this file is compiled with -ffp-contract=off),
 // so round(chi2, 2) and "%.2E" % p come out string-identical.  The expensive exact evaluation only
-// runs on rows that a division-free test T*(ad-bc)^2 >= thr*R1*R0*K1*K0*(1-1e-9) cannot rule out.
-#include "scan_common.h"
-#include "cx_side_plan.h"
-
-#include <algorithm>
-#include <cmath>
-#include <cstdlib>
-#include <vector>
+// runs on rows that a division-free test T*(ad-bc)^2 >= thr*R1*R0*K1*K0*(1-1e-9) cannot rule out
+// (chi2_candidate, chi2_plan.h: the rule as the dense kernel and the host's plans call it; the exception-coded kernels
+// below restate it by hand).
+#include "chi2_launch.h"
 
 namespace {
 
@@ -42,17 +42,6 @@ __device__ __forceinline__ double chi2_exact(double A, double B, double C, doubl
     d = C - e2; stat += (d * d) / e2;
     d = D - e3; stat += (d * d) / e3;
     return stat;
-}
-
-// the division-free pre-test of a unit-weight 2 x 2 table: chi2 = T (AD - BC)^2 / (R1 R0 K1 K0) cannot be ruled out
-// against thr.  Host and device evaluate it in the same IEEE double operations (-ffp-contract=off): the host's corner
-// table of the exception-coded scan (cx_plan) decides bit for bit what the dense kernel decides.
-__host__ __device__ __forceinline__ bool chi2_pretest(double A, double B, double C, double D, double thr)
-{
-    const double R1 = A + B, R0 = C + D, K1 = A + C, K0 = B + D, T = R1 + R0;
-    const double det = A * D - B * C;
-    const double lhs = T * det * det, rhs = thr * R1 * R0 * K1 * K0;
-    return !(lhs < rhs * (1.0 - 1e-9));  // NaN compares false -> a candidate
 }
 
 // The chi2 decision, once: statistic, p and the keep rule from the four cells.  The scan kernels append what is kept to
@@ -79,11 +68,13 @@ __device__ __forceinline__ void chi2_decide(const ScanArgs &P, uint64_t row, dou
     if (chi2_keep(P.cut, A, B, C, D, stat, p)) chi2_store(P.sink, reserve_slot(P.sink), row, stat, p, n_w);
 }
 
-// chi2_scan_kernel MODE 0 from the two class counts of a row
-__device__ __forceinline__ void chi2_evaluate(const ScanCuts &K, const ScanSink &S, uint64_t row, int a, int c)
+// chi2_scan_kernel MODE 0 from the two class counts of a row (I: int, or uint32_t where they come as popcounts -- the
+// conversions are then the candidate rule's own)
+template <class I>
+__device__ __forceinline__ void chi2_evaluate(const ScanCuts &K, const ScanSink &S, uint64_t row, I a, I c)
 {
     double stat, p;
-    if (chi2_keep(K, (double)a, (double)(K.n1 - a), (double)c, (double)(K.n0 - c), stat, p)) chi2_store(S, reserve_slot(S), row, stat, p, a + c);
+    if (chi2_keep(K, (double)a, (double)(K.n1 - (int)a), (double)c, (double)(K.n0 - (int)c), stat, p)) chi2_store(S, reserve_slot(S), row, stat, p, (int)(a + c));
 }
 
 // MODE 0: unit weights, the exact evaluation in line -- the usual case, where almost no row passes the pre-test.
@@ -152,20 +143,17 @@ __global__ __launch_bounds__(LUT ? SC_LUT_THREADS : SC_THREADS) void chi2_scan_k
 
     auto on_row = [&](uint64_t row, const uint32_t (&cnt)[2], bool lead) {
         const uint32_t a = cnt[0], c = cnt[1];
-        const int n_w = (int)(a + c);
-        const int n_wo = (P.cut.n1 - (int)a) + (P.cut.n0 - (int)c);
-        const bool freq_ok = (row < P.M) && !(n_w < P.cut.min_samples || n_wo < 2 || n_w > P.cut.max_samples);
         if (WEIGHTED) {
-            Q.n = queue_rows(freq_ok && lead, row, make_int2(n_w, 0), Q.row, Q.val, Q.n, lane);
+            const bool freq_ok = chi2_freq_ok(P.cut, a, c, row < P.M);
+            Q.n = queue_rows(freq_ok && lead, row, make_int2((int)(a + c), 0), Q.row, Q.val, Q.n, lane);
             return;
         }
-        const double A = (double)a, B = (double)(P.cut.n1 - (int)a), C = (double)c, D = (double)(P.cut.n0 - (int)c);
-        const bool cand = freq_ok && lead && chi2_pretest(A, B, C, D, P.cut.thr);
+        const bool cand = chi2_candidate(P.cut, a, c, row < P.M, lead);
         if (MODE == 2) {
             Q.n = queue_rows(cand, row, make_int2((int)a, (int)c), Q.row, Q.val, Q.n, lane);
             return;
         }
-        if (cand) chi2_decide(P, row, A, B, C, D, n_w);
+        if (cand) chi2_evaluate(P.cut, P.sink, row, a, c);
     };
     if constexpr (QUEUED) stream_rows<G, LUT>(P, mk, Q, on_row, process);
     else stream_rows<G, LUT>(P, mk, Q, on_row, NoQueue());
@@ -177,33 +165,36 @@ __global__ __launch_bounds__(LUT ? SC_LUT_THREADS : SC_THREADS) void chi2_scan_k
 // whether the exceptions are the present or the absent samples; the class table in LDS (1 = case, 0x100 = control, 0 = NA)
 // summed over the e indices gives (a', c') with a', c' <= 7, hence (a, c) = (a', c') or (n1 - a', n0 - c').  A slot row's
 // table therefore lies in one of the two 8 x 8 corners of the (a, c) plane, and whether it is a candidate -- frequency
-// filter and the division-free pre-test -- is one bit of the two corner words the host filled for this scan (cx_plan: the
-// same double operations as chi2_pretest); candidates take chi2_scan_kernel's MODE 0 path (chi2_exact, exp, keep rule), so
+// filter and the division-free pre-test -- is one bit of the two corner words the host filled for this scan (cx_plan, through
+// chi2_candidate, the dense kernel's rule); candidates take chi2_scan_kernel's MODE 0 path (chi2_exact, exp, keep rule), so
 // stat and p are the dense kernel's bits.  A header class (e, base) none of whose reachable corner points is a candidate
 // is dropped on the header byte (X.class_mask); when NO class is feasible -- every Bonferroni cut-off of a real run: a row
 // of at most 7 exceptions cannot reach the statistic -- the host launches no slot workgroup and the slots are not read.
 // The rows with more than CX_MAX_E exceptions are a side matrix of dense rows that the last workgroups of the SAME launch
-// scan as chi2_scan_kernel's MODE 0 does (CPR 16-byte chunks per row, one lane each; frequency filter and chi2_pretest
-// in line), reporting their original row ids: a second launch would add a kernel boundary to every step.
-#ifndef PSK_CX_UNROLL
-#define PSK_CX_UNROLL 4
-#endif
+// scan as chi2_scan_kernel's MODE 0 does (CPR 16-byte chunks per row, one lane each; the candidate rule
+// restated by hand, see SideRows), reporting their original row ids: a second launch would add a kernel boundary to every step.
 #ifndef PSK_CX_NT
 #define PSK_CX_NT 0   // plain loads: 57.4 us against 60.7 us with the nontemporal hint at config 2
 #endif
 #ifndef PSK_CX_SIDE_NT
 #define PSK_CX_SIDE_NT 1   // nontemporal hint on the side matrix: lower in five of six pairs of the r13 table (docs/NOTEBOOK.md), also re-read launch after launch
 #endif
-#ifndef PSK_CX_SIDE_GRID_MULT
-#define PSK_CX_SIDE_GRID_MULT 8   // workgroups per CU of chi2_scan_kernel_cx_side when PSK_GRID_MULT is unset (r13 table: 8 before 4 and the one-batch grid)
+#ifndef PSK_CX_PC_NT
+#define PSK_CX_PC_NT 0   // nontemporal hint on the popcount loads
 #endif
-constexpr int CX_UNROLL = PSK_CX_UNROLL;   // 16-byte loads in flight per lane
-static_assert(CX_SIDE_WAVES * 64 == SC_THREADS && CX_SIDE_NSEG == SC_NSEG, "cx_side_plan.h restates the launch constants");
+// (the unrolls and grid multiples, which the launch shapes depend on, are chi2_plan.h's)
 
 // The rows of the side matrix, once: UNR wave steps of 64 / CPR rows from step s0 on, one lane per 16-byte chunk.
 // load() issues the batch's loads; evaluate() is chi2_scan_kernel MODE 0's on_row on what came back -- popcounts against
-// the lane's mask words, the sum over the row's CPR lanes, frequency filter and chi2_pretest in line, then the exact
-// decision -- and reports a survivor under its original row id.  Both are called by whole waves (the CPR = 2 shuffle).
+// the lane's mask words, the sum over the row's CPR lanes, the candidate rule, then the exact decision -- and reports a
+// survivor under its original row id.  Both are called by whole waves (the CPR = 2 shuffle).
+// The candidate rule is RESTATED BY HAND here and in PcRows: the same operations in the same order as chi2_candidate
+// (chi2_plan.h), but nothing structural ties them to it -- the GPU tests that cross these kernels with the dense one bit
+// for bit are what holds them together.  Called through the function, and with the tail and the sweep loop shared
+// between the two structs, the compiler gave these kernels other registers than the parent's where a refactor has to leave
+// them equal (chi2_scan_kernel_cx_side_pc<2>: 101 VGPRs against 99, 6 SGPR spills against 4; ..._cx_side<2>: 92 against
+// 96), so both were taken back.  Timed against the parent (docs/NOTEBOOK.md, round 16): ..._cx_side_pc<2> 7.3-7.4 us against
+// 7.0 in each of six alternated pairs, which is below the three-spreads threshold; the other forms no different.
 template <int CPR, int UNR, bool NT>
 struct SideRows {
     static constexpr int RPW = 64 / CPR;   // rows per wave step
@@ -242,7 +233,7 @@ struct SideRows {
                 a += __shfl_xor(a, 1, 64);
                 c += __shfl_xor(c, 1, 64);
             }
-            // chi2_scan_kernel MODE 0's on_row
+            // by hand what chi2_candidate(K, a, c, r < n_ov, g == 0) does (see above)
             const int n_w = (int)(a + c);
             const int n_wo = (K.n1 - (int)a) + (K.n0 - (int)c);
             const bool freq_ok = (r < n_ov) && !(n_w < K.min_samples || n_wo < 2 || n_w > K.max_samples);
@@ -262,18 +253,6 @@ struct SideRows {
             chi2_evaluate(K, S, ov_row[r], (int)(v & 0xffffu), (int)(v >> 16));
         }
     }
-};
-
-struct CxScanArgs {
-    ScanArgs s;                  // the scan: unit weights, masks inline
-    const u32x4 *slots;          // two slots per 16 bytes
-    const u32x4 *ov;             // overflow rows, dense, cpr chunks each, ascending
-    const uint32_t *ov_row;      // ... their row ids
-    uint64_t n_ov;
-    uint32_t slot_blocks;        // workgroups [0, slot_blocks) stream the slots (none when no class is feasible),
-    uint32_t ov_blocks;          // the next ov_blocks the overflow rows; any beyond only publish their segment
-    uint32_t class_mask;         // bit (header & 15): some reachable table of that e and base is a candidate (cx_plan)
-    uint64_t corner[2];          // [base] bit a' * 8 + c': the table (a', c') / (n1 - a', n0 - c') is a candidate
 };
 
 template <int CPR>
@@ -343,23 +322,13 @@ __global__ __launch_bounds__(SC_THREADS) void chi2_scan_kernel_cx(const CxScanAr
 // of arguments every form's.  Here the arguments are what the rows need, there is no LDS, and the grid is what stays
 // resident (cx_side_shape): every wave walks its batches grid-stride and has the next batch's loads in flight while it
 // evaluates the current one (two register sets, swapped by unrolling the loop twice).
-struct CxSideArgs {
-    const u32x4 *ov;
-    const uint32_t *ov_row;
-    uint64_t n_ov;
-    uint64_t m1[4], m0[4];       // the mask words of the row's (at most two) chunks
-    ScanCuts cut;
-    ScanSink sink;
-};
-static_assert(sizeof(CxSideArgs) <= 256, "chi2_scan_kernel_cx_side's arguments are meant to stay small");
-
 template <int CPR>
 __global__ __launch_bounds__(SC_THREADS) void chi2_scan_kernel_cx_side(const CxSideArgs X)
 {
     const SideRows<CPR, CX_SIDE_UNROLL, PSK_CX_SIDE_NT != 0> R(X.ov, X.ov_row, X.n_ov, X.m1, X.m0);
-    const uint64_t stride = (uint64_t)gridDim.x * CX_SIDE_WAVES * CX_SIDE_UNROLL;
+    const uint64_t stride = (uint64_t)gridDim.x * CX_WAVES * CX_SIDE_UNROLL;
     const uint64_t n_steps = R.n_steps();
-    uint64_t s0 = ((uint64_t)blockIdx.x * CX_SIDE_WAVES + (threadIdx.x >> 6)) * CX_SIDE_UNROLL;
+    uint64_t s0 = ((uint64_t)blockIdx.x * CX_WAVES + (threadIdx.x >> 6)) * CX_SIDE_UNROLL;
     u32x4 xa[CX_SIDE_UNROLL], xb[CX_SIDE_UNROLL];
     if (s0 < n_steps) R.load(xa, s0);
     while (s0 < n_steps) {
@@ -385,22 +354,9 @@ __global__ __launch_bounds__(SC_THREADS) void chi2_scan_kernel_cx_side(const CxS
 // of a wave loads the popcounts of rows b * 64 U + 64 j + l, j = 0 .. U - 1, back to back (128 contiguous bytes per wave
 // instruction, 64 U rows per round), then walks j; a row whose bit of `feas` is set -- a live row -- loads its own CPR
 // chunks, counts them against the mask words (scalars from the arguments: no shuffle) and takes SideRows::evaluate's
-// path from there: frequency filter and chi2_pretest in line, the exact decision as one copy per batch.  A row that is
+// path from there: the candidate rule in line, the exact decision as one copy per batch.  A row that is
 // not live is left out by that predicate alone.  Batches go to the waves grid-stride with the next batch's popcounts
 // in flight, as in chi2_scan_kernel_cx_side.
-#ifndef PSK_CX_PC_NT
-#define PSK_CX_PC_NT 0   // nontemporal hint on the popcount loads
-#endif
-#ifndef PSK_CX_PC_GRID_MULT
-#define PSK_CX_PC_GRID_MULT 8   // workgroups per CU when PSK_GRID_MULT is unset
-#endif
-struct CxSidePcArgs {
-    CxSideArgs s;
-    const uint16_t *ov_pc;       // popcount of every side-matrix row over the valid samples
-    uint64_t feas[4];            // bit pc: a row of that popcount can be a candidate
-};
-static_assert(sizeof(CxSidePcArgs) <= 256, "chi2_scan_kernel_cx_side_pc's arguments are meant to stay small");
-
 template <int CPR>
 struct PcRows {
     static constexpr int U = CX_PC_UNROLL;
@@ -449,7 +405,7 @@ struct PcRows {
                     c += __popcll(xa & m0[2 * g]) + __popcll(xb & m0[2 * g + 1]);
                 }
             }
-            // chi2_scan_kernel MODE 0's on_row
+            // by hand what chi2_candidate(K, a, c, live) does (see SideRows)
             const int n_w = (int)(a + c);
             const int n_wo = (K.n1 - (int)a) + (K.n0 - (int)c);
             const bool freq_ok = live && !(n_w < K.min_samples || n_wo < 2 || n_w > K.max_samples);
@@ -472,9 +428,9 @@ template <int CPR>
 __global__ __launch_bounds__(SC_THREADS) void chi2_scan_kernel_cx_side_pc(const CxSidePcArgs X)
 {
     const PcRows<CPR> R(X);
-    const uint64_t stride = (uint64_t)gridDim.x * CX_SIDE_WAVES;
+    const uint64_t stride = (uint64_t)gridDim.x * CX_WAVES;
     const uint64_t n_batches = R.n_batches();
-    uint64_t b = (uint64_t)blockIdx.x * CX_SIDE_WAVES + (threadIdx.x >> 6);
+    uint64_t b = (uint64_t)blockIdx.x * CX_WAVES + (threadIdx.x >> 6);
     uint32_t pa[CX_PC_UNROLL], pb[CX_PC_UNROLL];
     if (b < n_batches) R.load(pa, b);
     while (b < n_batches) {
@@ -583,478 +539,26 @@ void launch_chi2(int mode, int G, dim3 grid, hipStream_t st, TimedBy ev, const S
     else launch_chi2_form<0>(G, grid, 0, st, ev, a);
 }
 
-// Kernel form of a chi2 scan.  Unit weights: MODE 2 (queued candidates) when many rows are expected to pass the
-// pre-test -- the last chi2 scan of this matrix kept more than 0.1 % of the rows, or, with no history, the keep rule
-// itself lets that many through under the null hypothesis (p < cut holds for a fraction `cut` of unassociated rows).
-// PSK_CHI2_MODE=0|2 forces one (A/B runs).
-int pick_chi2_mode(psk_ctx *ctx, bool weighted, double pcut, double pcut_bonf, int omit_B, int *mode)
-{
-    double expect = pcut_bonf;
-    if (omit_B && pcut > expect) expect = pcut;
-    *mode = weighted ? 1 : ctx->dense_hint >= 0 ? (ctx->dense_hint ? 2 : 0) : expect > 1e-3 ? 2 : 0;
-    return weighted ? PSK_OK : env_choice(ctx, "PSK_CHI2_MODE", {0, 2}, mode);   // read per scan: tests cross the two forms in one process
-}
-
-// ---- exception-coded path: the per-scan plan and the launch shape ----
-// What a scan's parameters leave of the slot rows.  corner[base] bit a' * 8 + c' (a', c' <= 7): the table of a slot row
-// with a' case and c' control exceptions -- (a', c') when the exceptions are the present samples (base 0), (n1 - a',
-// n0 - c') when they are the absent ones (base 1) -- passes chi2_scan_kernel's frequency filter and chi2_pretest (the same
-// double operations); 0 where a' > n1 or c' > n0: no row has such a table.  class_mask bit (e | base << 3): a row of e
-// exceptions can have a table whose bit is set.  Its a' + c' is e less its exceptions among the NA samples, of which
-// there are n_samples - n1 - n0.  (n1 = 0, n0 = 0: the pre-test lets every NaN table through, the filter alone decides.)
-void cx_plan(int n1, int n0, int n_samples, int min_samples, int max_samples, double thr, uint32_t *class_mask, uint64_t corner[2])
-{
-    corner[0] = corner[1] = 0;
-    for (int base = 0; base < 2; base++)
-        for (int ap = 0; ap <= CX_MAX_E && ap <= n1; ap++)
-            for (int cp = 0; cp <= CX_MAX_E && cp <= n0; cp++) {
-                const int ai = base ? n1 - ap : ap, ci = base ? n0 - cp : cp;
-                const int n_w = ai + ci, n_wo = (n1 - ai) + (n0 - ci);
-                const bool freq_ok = !(n_w < min_samples || n_wo < 2 || n_w > max_samples);
-                const double A = (double)ai, B = (double)(n1 - ai), C = (double)ci, D = (double)(n0 - ci);
-                if (freq_ok && chi2_pretest(A, B, C, D, thr)) corner[base] |= 1ull << (ap * 8 + cp);
-            }
-    const int n_na = n_samples - n1 - n0;
-    *class_mask = 0;
-    for (int h = 0; h < 16; h++) {
-        const int e = h & 7, base = h >> 3;
-        bool ok = false;
-        for (int ap = 0; ap <= e && !ok; ap++)
-            for (int cp = 0; ap + cp <= e && !ok; cp++)
-                ok = ap + cp >= e - n_na && ((corner[base] >> (ap * 8 + cp)) & 1ull);
-        if (ok) *class_mask |= 1u << h;
-    }
-}
-
-// What a scan's parameters leave of the side matrix, by popcount.  Bit pc of feas (pc <= 255: a side-matrix row has
-// CX_MAX_E < pc < n_samples - CX_MAX_E) is set exactly when a row of that popcount over the valid samples can have a
-// candidate table: its s = a + c is pc less its present NA samples, s in [max(0, pc - n_na), min(pc, n1 + n0)]; the
-// frequency filter depends on s alone; and with s fixed det = (n1 + n0) a - n1 s, so chi2_pretest's left side is convex
-// in a while its right side does not depend on a -- some table of that s passes exactly when one at a = max(0, s - n0)
-// or a = min(s, n1) does.  (Everything in the left side is an integer below 2^53: exact, so "convex" holds in the
-// doubles.)  Two pre-tests per s, n1 + n0 + 1 values of s.
-void cx_pc_plan(int n1, int n0, int n_samples, int min_samples, int max_samples, double thr, uint64_t feas[4])
-{
-    const int T = n1 + n0, n_na = n_samples - T;
-    std::vector<int> ok_upto(T + 2, 0);   // ok_upto[s + 1]: sums <= s that pass
-    for (int s = 0; s <= T; s++) {
-        const bool freq_ok = !(s < min_samples || T - s < 2 || s > max_samples);
-        bool ok = false;
-        if (freq_ok) {
-            const int ends[2] = {std::max(0, s - n0), std::min(s, n1)};
-            for (int e = 0; e < 2 && !ok; e++) {
-                const int a = ends[e], c = s - a;
-                ok = chi2_pretest((double)a, (double)(n1 - a), (double)c, (double)(n0 - c), thr);
-            }
-        }
-        ok_upto[s + 1] = ok_upto[s] + (ok ? 1 : 0);
-    }
-    feas[0] = feas[1] = feas[2] = feas[3] = 0;
-    for (int pc = 0; pc < 256; pc++) {
-        const int lo = std::max(0, pc - n_na), hi = std::min(pc, T);
-        if (lo <= hi && ok_upto[hi + 1] - ok_upto[lo] > 0) feas[pc >> 6] |= 1ull << (pc & 63);
-    }
-}
-
-// Workgroups of the two parts in proportion to their bytes, under scan_grid's cap; x.slot_blocks = the first part's,
-// x.ov_blocks the second's.  With no feasible class (x.class_mask == 0) the slots get none and the side matrix the whole
-// cap.  At least SC_NSEG workgroups: every result segment needs one to publish its count and re-arm its counter.
-dim3 cx_grid(const psk_ctx *ctx, CxScanArgs &x, int cpr)
-{
-    const uint64_t wpb = SC_THREADS / 64;
-    const uint64_t n_pairs = (x.s.M + 1) / 2, ov_rpw = 64 / cpr;
-    uint64_t bs = x.class_mask ? ((n_pairs + 64 * CX_UNROLL - 1) / (64 * CX_UNROLL) + wpb - 1) / wpb : 0;
-    uint64_t bo = (((x.n_ov + ov_rpw - 1) / ov_rpw + CX_UNROLL - 1) / CX_UNROLL + wpb - 1) / wpb;
-    const uint64_t cap = scan_grid_cap(ctx);
-    if (!x.class_mask) bo = std::min(bo, cap);
-    else if (bs + bo > cap) {
-        const double slot_bytes = 16.0 * n_pairs, ov_bytes = 16.0 * cpr * x.n_ov;
-        const uint64_t s = (uint64_t)(cap * slot_bytes / (slot_bytes + ov_bytes) + 0.5);
-        bs = std::min(bs, std::max<uint64_t>(s, 1));
-        bo = std::min(bo, cap - bs);
-        if (x.n_ov && bo == 0) { bo = 1; bs = std::max<uint64_t>(bs - 1, 1); }
-    }
-    uint64_t total = bs + bo;
-    if (total < SC_NSEG) {
-        if (x.class_mask) bs = SC_NSEG - bo;   // (more slot workgroups than slot work: they find p0 >= n_pairs)
-        total = SC_NSEG;
-    }
-    x.slot_blocks = (uint32_t)bs;
-    x.ov_blocks = (uint32_t)bo;
-    return dim3((unsigned)total);
-}
-
-// most workgroups of chi2_scan_kernel_cx_side: PSK_GRID_MULT per CU when set, else the kernel's own multiple
-uint64_t cx_side_grid_cap(const psk_ctx *ctx) { return (uint64_t)(ctx->n_cu > 0 ? ctx->n_cu : 256) * (ctx->grid_mult ? ctx->grid_mult : PSK_CX_SIDE_GRID_MULT); }
-// ... and of chi2_scan_kernel_cx_side_pc
-uint64_t cx_pc_grid_cap(const psk_ctx *ctx) { return (uint64_t)(ctx->n_cu > 0 ? ctx->n_cu : 256) * (ctx->grid_mult ? ctx->grid_mult : PSK_CX_PC_GRID_MULT); }
-
-// the most rows one workgroup of chi2_scan_kernel_cx visits
-uint64_t cx_rows_per_block(const CxScanArgs &x, int cpr)
-{
-    const uint64_t wpb = SC_THREADS / 64;
-    const uint64_t n_pairs = (x.s.M + 1) / 2, ov_rpw = 64 / cpr;
-    const uint64_t ws = (uint64_t)x.slot_blocks * wpb, wo = (uint64_t)x.ov_blocks * wpb;
-    const uint64_t cs = (n_pairs + 64 - 1) / 64, co = (x.n_ov + ov_rpw - 1) / ov_rpw;   // wave steps
-    const uint64_t rs = ws ? (cs + ws * CX_UNROLL - 1) / (ws * CX_UNROLL) * wpb * CX_UNROLL * 128 : 0;
-    const uint64_t ro = wo ? (co + wo * CX_UNROLL - 1) / (wo * CX_UNROLL) * wpb * CX_UNROLL * ov_rpw : 0;
-    return std::max(rs, ro);
-}
-
-// One chi2 scan as the host launches it: the dense kernels' arguments, and the exception-coded path when it runs
-struct Chi2Launch {
-    CxScanArgs x;      // x.s: every form's arguments; the rest: chi2_scan_kernel_cx's
-    CxSidePcArgs side;   // chi2_scan_kernel_cx_side's (side.s) when the plan says so (side_kernel); all of it: ..._side_pc's (filtered)
-    bool compact = false, side_kernel = false, filtered = false;
-    int mode = 0;      // of the dense kernels (pick_chi2_mode)
-    int cpr = 0;
-    dim3 grid;
-};
+}  // namespace
 
 void launch_chi2_any(psk_ctx *ctx, const Chi2Launch &L, TimedBy ev)
 {
-    const ScanArgs &a = L.x.s;
-    if (L.compact && L.side_kernel && L.filtered) {
-        if (L.cpr == 1) launch_timed(chi2_scan_kernel_cx_side_pc<1>, L.grid, SC_THREADS, 0, ctx->stream, ev, L.side);
-        else launch_timed(chi2_scan_kernel_cx_side_pc<2>, L.grid, SC_THREADS, 0, ctx->stream, ev, L.side);
-        return;
+    const hipStream_t st = ctx->stream;
+    switch (L.form) {
+    case Chi2Form::CxSidePc:
+        if (L.cpr == 1) launch_timed(chi2_scan_kernel_cx_side_pc<1>, L.grid, SC_THREADS, 0, st, ev, L.side);
+        else launch_timed(chi2_scan_kernel_cx_side_pc<2>, L.grid, SC_THREADS, 0, st, ev, L.side);
+        break;
+    case Chi2Form::CxSide:
+        if (L.cpr == 1) launch_timed(chi2_scan_kernel_cx_side<1>, L.grid, SC_THREADS, 0, st, ev, L.side.s);
+        else launch_timed(chi2_scan_kernel_cx_side<2>, L.grid, SC_THREADS, 0, st, ev, L.side.s);
+        break;
+    case Chi2Form::CxMixed:
+        if (L.cpr == 1) launch_timed(chi2_scan_kernel_cx<1>, L.grid, SC_THREADS, 0, st, ev, L.x);
+        else launch_timed(chi2_scan_kernel_cx<2>, L.grid, SC_THREADS, 0, st, ev, L.x);
+        break;
+    case Chi2Form::Dense:
+        launch_chi2(L.mode, group_lanes(L.x.s), L.grid, st, ev, L.x.s);
+        break;
     }
-    if (L.compact && L.side_kernel) {
-        if (L.cpr == 1) launch_timed(chi2_scan_kernel_cx_side<1>, L.grid, SC_THREADS, 0, ctx->stream, ev, L.side.s);
-        else launch_timed(chi2_scan_kernel_cx_side<2>, L.grid, SC_THREADS, 0, ctx->stream, ev, L.side.s);
-        return;
-    }
-    if (L.compact) {
-        if (L.cpr == 1) launch_timed(chi2_scan_kernel_cx<1>, L.grid, SC_THREADS, 0, ctx->stream, ev, L.x);
-        else launch_timed(chi2_scan_kernel_cx<2>, L.grid, SC_THREADS, 0, ctx->stream, ev, L.x);
-        return;
-    }
-    launch_chi2(L.mode, group_lanes(a), L.grid, ctx->stream, ev, a);
-}
-
-int run_chi2(psk_ctx *ctx, const Chi2Launch &L, int reps, double *ms_total, double *ms_each = nullptr)
-{
-    *ms_total = 0;
-    for (int r = 0; r < reps; r++) {
-        launch_chi2_any(ctx, L, {ctx->ev0, ctx->ev1});
-        PSK_HIP(ctx, hipGetLastError());
-        PSK_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the kernel has written the counts to pinned memory
-        float ms = 0;
-        PSK_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-        *ms_total += ms;
-        if (ms_each) ms_each[r] = ms;
-    }
-    return PSK_OK;
-}
-
-}  // namespace
-
-// The arguments of the last chi2 scan (ctx->last) for result set `set`.  Unit weights on a matrix with an exception-coded
-// copy run chi2_scan_kernel_cx over it, unless PSK_SCAN_DENSE=1 (read per call: A/B runs and tests in one build).
-// build_tables: a new scan, whose weight table has just been uploaded (a repeated scan finds its table in place).
-static int fill_chi2_args(psk_ctx *ctx, Chi2Launch &CL, int set, bool build_tables)
-{
-    const ScanParams &L = ctx->last;
-    CL.x.s = ScanArgs();
-    ScanArgs &a = CL.x.s;
-    a.bits = reinterpret_cast<const u32x4 *>(ctx->bits.p);
-    a.M = ctx->n_kmers;
-    const int mw = mask_words(ctx);
-    a.cpr = mw / 2;
-    a.half = ctx->wpr == 1;
-    a.m1 = ctx->mask1.as<uint64_t>();
-    a.m0 = a.m1 + mw;
-    a.tab = reinterpret_cast<const double *>(a.m1 + 2 * (size_t)mw);  // [sample][w if pheno 1 | w if pheno 0]
-    a.inline_masks = L.inline_masks;
-    if (L.inline_masks) { memcpy(a.m1_inl, L.m1, sizeof(a.m1_inl)); memcpy(a.m0_inl, L.m0, sizeof(a.m0_inl)); }
-    a.cut.min_samples = L.min_samples;
-    a.cut.max_samples = L.max_samples;
-    a.cut.pcut = L.pvalue_cutoff;
-    a.cut.pcut_bonf = L.pvalue_cutoff / (double)L.n_kmers_global;
-    a.cut.omit_B = L.omit_B;
-    double pmax = a.cut.pcut_bonf;
-    if (L.omit_B && a.cut.pcut > pmax) pmax = a.cut.pcut;
-    if (pmax >= 1.0) a.cut.thr = 0.0;
-    else if (pmax <= 0.0) a.cut.thr = INFINITY;
-    else a.cut.thr = -2.0 * log(pmax);
-    a.W1 = L.W1; a.W0 = L.W0;
-    a.cut.n1 = L.n1; a.cut.n0 = L.n0;
-    ScanShape sh;   // weighted: class-weight sums from a table in LDS (e0 = class 1, e1 = class 0)
-    PSK_TRY(setup_table_scan(ctx, a, L.weighted ? a.tab : nullptr, 2, L.W1, L.W0, 0.0, build_tables, &sh));
-    CL.compact = ctx->cx_valid && !L.weighted && L.inline_masks && !env_flag("PSK_SCAN_DENSE");
-    ctx->cx_last_plan = false;
-    if (CL.compact) {
-        CxScanArgs &x = CL.x;
-        CL.cpr = a.cpr;
-        x.slots = ctx->cx_slots.as<u32x4>();
-        x.ov = ctx->cx_ov.as<u32x4>();
-        x.ov_row = ctx->cx_ov_row.as<uint32_t>();
-        x.n_ov = ctx->cx_n_ov;
-        int side_on = 1;   // read per scan: A/B runs and tests in one build
-        PSK_TRY(env_choice(ctx, "PSK_CX_SIDE_KERNEL", {0, 1}, &side_on));
-        int pc_on = 1;
-        PSK_TRY(env_choice(ctx, "PSK_CX_PC_FILTER", {0, 1}, &pc_on));
-        CxPlanKey key;
-        key.M = a.M; key.n_ov = x.n_ov; key.cap = scan_grid_cap(ctx); key.side_cap = cx_side_grid_cap(ctx);
-        key.pc_cap = cx_pc_grid_cap(ctx); key.pc_filter = pc_on;
-        memcpy(&key.thr_bits, &a.cut.thr, 8);
-        key.n1 = a.cut.n1; key.n0 = a.cut.n0; key.n_samples = ctx->n_samples;
-        key.min_samples = a.cut.min_samples; key.max_samples = a.cut.max_samples; key.side_kernel = side_on;
-        CxPlan &pl = ctx->cx_plan;
-        if (!pl.valid || !(pl.key == key)) {
-            pl.valid = false;
-            cx_plan(a.cut.n1, a.cut.n0, ctx->n_samples, a.cut.min_samples, a.cut.max_samples, a.cut.thr, &pl.class_mask, pl.corner);
-            pl.side = side_on && pl.class_mask == 0;
-            uint64_t rows_per_block;
-            pl.filtered = false;
-            pl.rows_feasible = x.n_ov;
-            pl.feas[0] = pl.feas[1] = pl.feas[2] = pl.feas[3] = ~0ull;
-            if (pl.side && pc_on) {
-                cx_pc_plan(a.cut.n1, a.cut.n0, ctx->n_samples, a.cut.min_samples, a.cut.max_samples, a.cut.thr, pl.feas);
-                pl.rows_feasible = 0;
-                for (size_t pc = 0; pc < ctx->cx_pc_hist.size() && pc < 256; pc++)
-                    if ((pl.feas[pc >> 6] >> (pc & 63)) & 1ull) pl.rows_feasible += ctx->cx_pc_hist[pc];
-                pl.filtered = pl.rows_feasible < x.n_ov;
-#ifdef PSK_CX_PC_FORCE   // A/B builds: the filtered form whatever the count (the all-feasible comparison of the r15 table)
-                pl.filtered = true;
-#endif
-            }
-            if (pl.filtered) {
-                const cx_side_shape_t sh = cx_pc_shape(x.n_ov, key.pc_cap);
-                pl.grid = sh.blocks; pl.slot_blocks = 0; pl.ov_blocks = sh.blocks;
-                rows_per_block = sh.rows_per_block;
-            } else if (pl.side) {
-                const cx_side_shape_t sh = cx_side_shape(x.n_ov, CL.cpr, key.side_cap);
-                pl.grid = sh.blocks; pl.slot_blocks = 0; pl.ov_blocks = sh.blocks;
-                rows_per_block = sh.rows_per_block;
-            } else {
-                x.class_mask = pl.class_mask;
-                pl.grid = cx_grid(ctx, x, CL.cpr).x;
-                pl.slot_blocks = x.slot_blocks; pl.ov_blocks = x.ov_blocks;
-                rows_per_block = cx_rows_per_block(x, CL.cpr);
-            }
-            pl.seg_cap = result_seg_cap(dim3(pl.grid), rows_per_block);
-            pl.key = key;
-            pl.valid = true;
-        }
-        x.class_mask = pl.class_mask; x.corner[0] = pl.corner[0]; x.corner[1] = pl.corner[1];
-        x.slot_blocks = pl.slot_blocks; x.ov_blocks = pl.ov_blocks;
-        CL.grid = dim3(pl.grid);
-        CL.side_kernel = pl.side;
-        CL.filtered = pl.filtered;
-        ctx->cx_last_plan = true;
-        ctx->cx_last_filtered = pl.filtered;
-        ctx->cx_last_rows_feasible = pl.rows_feasible;
-        ctx->cx_last_class_mask = pl.class_mask;
-        ctx->cx_last_skipped = pl.slot_blocks == 0;
-        PSK_TRY(bind_results(ctx, a.sink, pl.seg_cap, set));
-        if (pl.side) {
-            CxSideArgs &sd = CL.side.s;
-            CL.side.ov_pc = ctx->cx_ov_pc.as<uint16_t>();
-            memcpy(CL.side.feas, pl.feas, sizeof(CL.side.feas));
-            sd.ov = x.ov; sd.ov_row = x.ov_row; sd.n_ov = x.n_ov;
-            memcpy(sd.m1, a.m1_inl, sizeof(sd.m1));
-            memcpy(sd.m0, a.m0_inl, sizeof(sd.m0));
-            sd.cut = a.cut;
-            sd.sink = a.sink;
-        }
-        return PSK_OK;
-    }
-    PSK_TRY(pick_chi2_mode(ctx, L.weighted, a.cut.pcut, a.cut.pcut_bonf, a.cut.omit_B, &CL.mode));
-    CL.grid = sh.grid;
-    return setup_results(ctx, a, CL.grid, group_lanes(a), sh.unroll, set, sh.threads);
-}
-
-// Launches the scan and returns without waiting; psk_scan_end collects it.  Lets a caller queue other work (the
-// survivor exchange of the previous scan) while the kernel streams the matrix.
-static int chi2_scan_launch(psk_ctx *ctx, const int8_t *pheno, const double *weights, int min_samples, int max_samples,
-                            double pvalue_cutoff, int omit_B, uint64_t n_kmers_global, bool keep_results)
-{
-    if (!ctx) return PSK_EINVAL;
-    if (ctx->n_in_flight >= 2) return psk_fail(ctx, PSK_ESTATE, "two scans are in flight (psk_scan_end first)");
-    if (!ctx->have_presence) return psk_fail(ctx, PSK_ESTATE, "no presence matrix (psk_build_presence first)");
-    if (!pheno) return psk_fail(ctx, PSK_EINVAL, "null phenotype vector");
-    if (n_kmers_global == 0) n_kmers_global = ctx->n_kmers ? ctx->n_kmers : 1;
-    PSK_HIP(ctx, hipSetDevice(ctx->device));
-    const int N = ctx->n_samples, wpr = mask_words(ctx);   // masks and tables: whole 16-byte chunks, also for 8-byte rows
-    // one pinned staging block [m1 | m0 | w1 | w0] and ONE stream-ordered upload (weights only when given)
-    const size_t n_mask = 2 * (size_t)wpr, n_w = 2 * (size_t)wpr * 64;
-    const size_t stage_bytes = (n_mask + n_w) * 8;
-    int set = 0;
-    PSK_TRY(pick_result_set(ctx, &set, keep_results));
-    if (2 * stage_bytes > ctx->scan_pinned_cap) {  // one staging block per result set: an upload may still be queued
-        if (ctx->n_in_flight) PSK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->scan_pinned) (void)hipHostFree(ctx->scan_pinned);
-        ctx->scan_pinned = nullptr;
-        ctx->scan_pinned_cap = 0;
-        PSK_HIP(ctx, hipHostMalloc(&ctx->scan_pinned, 2 * stage_bytes, hipHostMallocDefault));
-        ctx->scan_pinned_cap = 2 * stage_bytes;
-    }
-    uint64_t *m1 = reinterpret_cast<uint64_t *>(static_cast<uint8_t *>(ctx->scan_pinned) + set * stage_bytes), *m0 = m1 + wpr;
-    double *w = reinterpret_cast<double *>(m1 + n_mask);
-    memset(m1, 0, weights ? stage_bytes : n_mask * 8);
-    double W1 = 0, W0 = 0;
-    int n1 = 0, n0 = 0;
-    for (int i = 0; i < N; i++) {
-        const double wi = weights ? weights[i] : 1.0;
-        if (pheno[i] == 1) { m1[i >> 6] |= 1ull << (i & 63); if (weights) w[2 * (size_t)i] = wi; W1 += wi; n1++; }
-        else if (pheno[i] == 0) { m0[i >> 6] |= 1ull << (i & 63); if (weights) w[2 * (size_t)i + 1] = wi; W0 += wi; n0++; }
-    }
-    // up to 1024 samples: the masks ride in the kernel arguments and an unweighted scan uploads nothing
-    ctx->last.inline_masks = wpr <= SC_INL_WORDS ? 1 : 0;
-    if (ctx->last.inline_masks) {
-        memset(ctx->last.m1, 0, sizeof(ctx->last.m1));
-        memset(ctx->last.m0, 0, sizeof(ctx->last.m0));
-        memcpy(ctx->last.m1, m1, (size_t)wpr * 8);
-        memcpy(ctx->last.m0, m0, (size_t)wpr * 8);
-    }
-    PSK_TRY(dev_reserve(ctx, ctx->mask1, stage_bytes));
-    if (weights || !ctx->last.inline_masks)
-        PSK_HIP(ctx, hipMemcpyAsync(ctx->mask1.p, m1, weights ? stage_bytes : n_mask * 8, hipMemcpyHostToDevice, ctx->stream));
-
-    ctx->last.valid = true;
-    ctx->last.weighted = weights != nullptr;
-    ctx->last.min_samples = min_samples;
-    ctx->last.max_samples = max_samples;
-    ctx->last.pvalue_cutoff = pvalue_cutoff;
-    ctx->last.omit_B = omit_B ? 1 : 0;
-    ctx->last.n_kmers_global = n_kmers_global;
-    ctx->last.n1 = n1; ctx->last.n0 = n0; ctx->last.W1 = W1; ctx->last.W0 = W0;
-    Chi2Launch CL;
-    PSK_TRY(fill_chi2_args(ctx, CL, set, true));
-    ctx->last_scan_kind = 1;
-    if (ctx->n_kmers) {
-        ScanSlot &sl = ctx->slot[set];
-        launch_chi2_any(ctx, CL, {sl.ev0, sl.ev1});   // the events ride on the dispatch: one command per scan
-        PSK_HIP(ctx, hipGetLastError());
-        sl.in_flight = true;
-        sl.seq = ++ctx->scan_seq;
-        ctx->n_in_flight++;
-    } else {  // nothing to scan: an empty result, at once
-        ctx->n_pass = 0;
-        ctx->seg_counts.assign(SC_NSEG, 0);
-        ctx->res_set = set;
-        ctx->results_valid = true;
-    }
-    return PSK_OK;
-}
-
-extern "C" int psk_chi2_scan_begin(psk_ctx *ctx, const int8_t *pheno, const double *weights, int min_samples,
-                                   int max_samples, double pvalue_cutoff, int omit_B, uint64_t n_kmers_global)
-{
-    return chi2_scan_launch(ctx, pheno, weights, min_samples, max_samples, pvalue_cutoff, omit_B, n_kmers_global, true);
-}
-
-extern "C" int psk_scan_end(psk_ctx *ctx, uint64_t *n_pass)
-{
-    if (!ctx) return PSK_EINVAL;
-    if (ctx->n_in_flight) {  // the oldest scan in flight
-        PSK_HIP(ctx, hipSetDevice(ctx->device));
-        int set = ctx->slot[0].in_flight ? 0 : 1;
-        if (ctx->slot[0].in_flight && ctx->slot[1].in_flight && ctx->slot[1].seq < ctx->slot[0].seq) set = 1;
-        ScanSlot &sl = ctx->slot[set];
-        PSK_HIP(ctx, hipEventSynchronize(sl.ev1));  // its kernels have written the counts to pinned memory
-        sl.in_flight = false;
-        ctx->n_in_flight--;
-        float ms = 0;
-        PSK_HIP(ctx, hipEventElapsedTime(&ms, sl.ev0, sl.ev1));
-        ctx->last_scan_ms = ms;
-        PSK_TRY(fetch_counts(ctx, set));
-        ctx->dense_hint = ctx->n_pass * 1000 > ctx->n_kmers ? 1 : 0;  // only chi2 scans come through here
-    }
-    if (n_pass) *n_pass = ctx->n_pass;
-    return PSK_OK;
-}
-
-extern "C" int psk_chi2_scan(psk_ctx *ctx, const int8_t *pheno, const double *weights, int min_samples,
-                             int max_samples, double pvalue_cutoff, int omit_B, uint64_t n_kmers_global,
-                             uint64_t *n_pass)
-{
-    if (ctx && ctx->n_in_flight) return psk_fail(ctx, PSK_ESTATE, "a scan is in flight (psk_scan_end first)");
-    PSK_TRY(chi2_scan_launch(ctx, pheno, weights, min_samples, max_samples, pvalue_cutoff, omit_B, n_kmers_global, false));
-    return psk_scan_end(ctx, n_pass);
-}
-
-
-static int rescan(psk_ctx *ctx, int reps, double *mean_ms, double *ms_each)
-{
-    if (!ctx) return PSK_EINVAL;
-    if (ctx->n_in_flight) return psk_fail(ctx, PSK_ESTATE, "a scan is in flight (psk_scan_end first)");
-    if (!ctx->have_presence || !ctx->last.valid || ctx->last_scan_kind != 1)
-        return psk_fail(ctx, PSK_ESTATE, "no chi2 scan to repeat");
-    if (reps < 1) return psk_fail(ctx, PSK_EINVAL, "reps must be >= 1");
-    PSK_HIP(ctx, hipSetDevice(ctx->device));
-    int set = 0;
-    PSK_TRY(pick_result_set(ctx, &set));
-    Chi2Launch CL;
-    PSK_TRY(fill_chi2_args(ctx, CL, set, false));
-    double ms = 0;
-    PSK_TRY(run_chi2(ctx, CL, reps, &ms, ms_each));
-    ctx->last_scan_ms = ms / reps;
-    PSK_TRY(fetch_counts(ctx, set));
-    if (mean_ms) *mean_ms = ms / reps;
-    return PSK_OK;
-}
-
-extern "C" int psk_rescan_timed(psk_ctx *ctx, int reps, double *mean_ms) { return rescan(ctx, reps, mean_ms, nullptr); }
-
-extern "C" int psk_rescan_times(psk_ctx *ctx, int reps, double *ms_each)
-{
-    if (ctx && !ms_each) return psk_fail(ctx, PSK_EINVAL, "null output array");
-    return rescan(ctx, reps, nullptr, ms_each);
-}
-
-extern "C" int psk_chi2_pretest(double A, double B, double C, double D, double thr) { return chi2_pretest(A, B, C, D, thr) ? 1 : 0; }
-
-extern "C" int psk_cx_plan(int n1, int n0, int n_samples, int min_samples, int max_samples, double thr, uint32_t *class_mask,
-                           uint64_t *corner)
-{
-    if (n1 < 0 || n0 < 0 || n_samples < 0 || n1 + n0 > n_samples || !class_mask || !corner) return PSK_EINVAL;
-    cx_plan(n1, n0, n_samples, min_samples, max_samples, thr, class_mask, corner);
-    return PSK_OK;
-}
-
-extern "C" int psk_cx_side_shape(uint64_t n_ov, int cpr, uint64_t cap_blocks, uint32_t *blocks, uint64_t *rows_per_block, uint32_t *batch_rows)
-{
-    if ((cpr != 1 && cpr != 2) || cap_blocks < 1 || cap_blocks > 0xffffffffull || !blocks || !rows_per_block) return PSK_EINVAL;
-    const cx_side_shape_t sh = cx_side_shape(n_ov, cpr, cap_blocks);
-    *blocks = sh.blocks;
-    *rows_per_block = sh.rows_per_block;
-    if (batch_rows) *batch_rows = sh.batch_rows;
-    return PSK_OK;
-}
-
-extern "C" int psk_cx_pc_plan(int n1, int n0, int n_samples, int min_samples, int max_samples, double thr, uint64_t *feas)
-{
-    if (n1 < 0 || n0 < 0 || n_samples < 0 || n_samples > CX_MAX_SAMPLES || n1 + n0 > n_samples || !feas) return PSK_EINVAL;
-    cx_pc_plan(n1, n0, n_samples, min_samples, max_samples, thr, feas);
-    return PSK_OK;
-}
-
-extern "C" int psk_cx_pc_shape(uint64_t n_ov, uint64_t cap_blocks, uint32_t *blocks, uint64_t *rows_per_block, uint32_t *batch_rows)
-{
-    if (cap_blocks < 1 || cap_blocks > 0xffffffffull || !blocks || !rows_per_block) return PSK_EINVAL;
-    const cx_side_shape_t sh = cx_pc_shape(n_ov, cap_blocks);
-    *blocks = sh.blocks;
-    *rows_per_block = sh.rows_per_block;
-    if (batch_rows) *batch_rows = sh.batch_rows;
-    return PSK_OK;
-}
-
-extern "C" int psk_last_scan_filter(const psk_ctx *ctx, int *filtered, uint64_t *rows_feasible, uint64_t *rows_overflow)
-{
-    if (!ctx) return PSK_EINVAL;
-    if (filtered) *filtered = ctx->cx_last_plan && ctx->cx_last_filtered ? 1 : 0;
-    if (rows_feasible) *rows_feasible = ctx->cx_last_plan ? ctx->cx_last_rows_feasible : 0;
-    if (rows_overflow) *rows_overflow = ctx->cx_last_plan ? ctx->cx_n_ov : 0;
-    return PSK_OK;
-}
-
-extern "C" int psk_last_scan_plan(const psk_ctx *ctx, int *encoded, uint32_t *class_mask, int *slots_skipped)
-{
-    if (!ctx) return PSK_EINVAL;
-    if (encoded) *encoded = ctx->cx_last_plan ? 1 : 0;
-    if (class_mask) *class_mask = ctx->cx_last_plan ? ctx->cx_last_class_mask : 0;
-    if (slots_skipped) *slots_skipped = ctx->cx_last_plan && ctx->cx_last_skipped ? 1 : 0;
-    return PSK_OK;
 }

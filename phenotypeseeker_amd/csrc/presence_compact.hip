@@ -10,7 +10,7 @@
 // Two passes over the dense matrix: the first counts the overflow rows of every workgroup (whose exclusive scan places
 // them), the host decides from the total whether to keep a copy (CX_MAX_SHARE, CX_MAX_OVF_DIV), the second writes slots and side matrix.
 // Beside each side-matrix row the encoder keeps its popcount (cx_ov_pc, u16) and, on the host, how many rows have each
-// popcount (cx_pc_hist): a scan's parameters rule out whole popcounts (cx_pc_plan, assoc_scan.hip), and the scan then
+// popcount (cx_pc_hist): a scan's parameters rule out whole popcounts (cx_pc_plan, chi2_plan.h), and the scan then
 // reads 2 bytes of such a row instead of the row.
 // PSK_TRACE=1 prints the decision, the time of the build and the popcounts' non-zero range.
 #include "dev_utils.h"

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/psk.h"
+#include "chi2_plan.h"   // ScanCuts, CxPlan and what else the host decides about a chi2 scan: no HIP in it
 
 // ---- growable device buffer -------------------------------------------------------------------
 struct DevBuf {
@@ -125,34 +126,6 @@ struct ScanSlot {
     uint64_t seg_cap = 0;            // entries per result segment of the scan that wrote this set
 };
 
-// The plan of an exception-coded chi2 scan (assoc_scan.hip), kept from scan to scan: what cx_plan, the launch shape and
-// the result segments' size come to for `key`, which names everything they are a function of -- none of it derived from
-// WHICH samples are cases.  A scan with another key recomputes; a new matrix or encoded copy drops the plan.
-struct CxPlanKey {
-    uint64_t M = 0, n_ov = 0, cap = 0, side_cap = 0, pc_cap = 0, thr_bits = 0;
-    int n1 = 0, n0 = 0, n_samples = 0, min_samples = 0, max_samples = 0, side_kernel = 0, pc_filter = 0;
-    bool operator==(const CxPlanKey &o) const
-    {
-        return M == o.M && n_ov == o.n_ov && cap == o.cap && side_cap == o.side_cap && pc_cap == o.pc_cap && thr_bits == o.thr_bits &&
-               n1 == o.n1 && n0 == o.n0 && n_samples == o.n_samples && min_samples == o.min_samples && max_samples == o.max_samples &&
-               side_kernel == o.side_kernel && pc_filter == o.pc_filter;
-    }
-};
-struct CxPlan {
-    bool valid = false;
-    CxPlanKey key;
-    uint32_t class_mask = 0;
-    uint64_t corner[2] = {0, 0};
-    bool side = false;               // launched as chi2_scan_kernel_cx_side (no feasible class, PSK_CX_SIDE_KERNEL on)
-    uint32_t grid = 0, slot_blocks = 0, ov_blocks = 0;   // filtered: grid = ov_blocks = cx_pc_shape's workgroups
-    uint64_t seg_cap = 0;            // entries per result segment
-    // the popcounts a side-matrix row must have for some table of it to be a candidate (cx_pc_plan), and how many rows
-    // have one (the encoder's histogram): with fewer than all, chi2_scan_kernel_cx_side_pc reads only those (filtered)
-    uint64_t feas[4] = {0, 0, 0, 0};
-    bool filtered = false;
-    uint64_t rows_feasible = 0;
-};
-
 struct psk_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -230,7 +203,7 @@ struct psk_ctx {
     std::vector<uint64_t> cx_pc_hist;   // [n_samples + 1] side-matrix rows of each popcount (host copy, made by the encoder)
     bool cx_valid = false;
     uint64_t cx_n_ov = 0;
-    // the plan of the last chi2 scan set up (cx_plan, assoc_scan.hip): did it take the exception-coded path, which header
+    // the plan of the last chi2 scan set up (cx_make_plan, chi2_plan.h): did it take the exception-coded path, which header
     // classes were feasible, and was the slot stream left unread (psk_last_scan_plan)
     bool cx_last_plan = false, cx_last_skipped = false, cx_last_filtered = false;
     uint64_t cx_last_rows_feasible = 0;
@@ -291,8 +264,7 @@ template <class T> int env_int(psk_ctx *ctx, const char *name, int64_t lo, int64
 
 // ---- exception-coded rows (presence_compact.hip) ----------------------------------------------------------------------
 // Slot of a row (u64, little endian): byte 0 = header -- bits 0..2 e, bit 3 "the exceptions are the ABSENT samples",
-// bit 4 overflow (e > CX_MAX_E: the row is in the side matrix) --, bytes 1..e = the exceptions' sample indices, ascending.
-constexpr int CX_MAX_E = 7;
+// bit 4 overflow (e > CX_MAX_E, chi2_plan.h: the row is in the side matrix) --, bytes 1..e = the exceptions' sample indices, ascending.
 constexpr uint32_t CX_HDR_BASE = 8, CX_HDR_OVF = 16;
 constexpr int CX_MIN_SAMPLES = 65, CX_MAX_SAMPLES = 256;   // up to 64 samples a dense row is already 8 bytes
 // Encoded when slots + side matrix + its row ids take at most CX_MAX_SHARE of the dense matrix's bytes and at most

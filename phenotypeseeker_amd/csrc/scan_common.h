@@ -1,10 +1,11 @@
-// What the association scans share (assoc_scan.hip: chi2; ttest_scan.hip: Welch; scan_results.hip: their result sets):
+// What the association scans share (assoc_scan.hip, chi2_driver.hip: chi2; ttest_scan.hip: Welch; scan_results.hip: their result sets):
 // the kernel arguments, the result-segment protocol, the row stream both scan kernels are built on, the lane-per-row
 // moment forms, and the host's dispatch over the lanes-per-row constant.  Templates and inline device code only: a
 // kernel is instantiated by the one unit that launches it.
 #pragma once
 #include "dev_utils.h"
 #include "psk_internal.h"
+#include "chi2_plan.h"
 
 #include <hip/hip_ext.h>
 #include <type_traits>
@@ -32,15 +33,8 @@ constexpr int SC_UNROLL = PSK_SC_UNROLL;
 constexpr int SC_NSEG = 256;
 constexpr int SC_CNT_STRIDE = 32;  // u32 per counter slot
 constexpr int SC_INL_WORDS = 16;   // mask words carried inside ScanArgs
+static_assert(CX_WAVES * 64 == SC_THREADS && CX_NSEG == SC_NSEG, "chi2_plan.h restates the launch constants");
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-// What decides a row: the class sizes (popcounts of the masks), the frequency filter and the cut-offs.
-struct ScanCuts {
-    double pcut, pcut_bonf, thr;  // thr: statistic threshold of the division-free pre-test
-    int n1, n0;
-    int min_samples, max_samples;
-    int omit_B;
-};
 
 struct ScanArgs {
     const u32x4 *bits;
@@ -129,7 +123,7 @@ int mask_words(const psk_ctx *ctx);
 int group_lanes(const ScanArgs &a);
 uint64_t scan_grid_cap(const psk_ctx *ctx);
 dim3 scan_grid(const psk_ctx *ctx, uint64_t M, int G, int unroll, bool lut = false);
-uint64_t result_seg_cap(dim3 grid, uint64_t rows_per_block);
+uint64_t result_seg_cap(dim3 grid, uint64_t rows_per_block);   // chi2_plan.h's arithmetic on grid.x
 int bind_results(psk_ctx *ctx, ScanSink &s, uint64_t seg_cap, int set);
 int setup_results_rows(psk_ctx *ctx, ScanSink &s, dim3 grid, uint64_t rows_per_block, int set);
 int setup_results(psk_ctx *ctx, ScanArgs &a, dim3 grid, int G, int unroll, int set, int threads = SC_THREADS);

@@ -1,4 +1,4 @@
-// The result sets of the association scans (assoc_scan.hip, ttest_scan.hip): the launch shape and the segmented result
+// The result sets of the association scans (chi2_driver.hip, ttest_scan.hip): the launch shape and the segmented result
 // arrays that follow from it, the per-segment counts, and the calls that hand the survivors out.
 #include "scan_common.h"
 
@@ -20,12 +20,7 @@ int group_lanes(const ScanArgs &a)
 // result arrays (SoA) inside ctx->res: row u64 | stat f64 | p f64 | mx f64 | my f64 | nw i32, each
 // SC_NSEG * seg_cap entries; seg_cap bounds the rows the blocks of one segment can visit
 // (rows_per_block: the most rows one workgroup of the launch visits)
-uint64_t result_seg_cap(dim3 grid, uint64_t rows_per_block)
-{
-    const uint64_t blocks_per_seg = ((uint64_t)grid.x + SC_NSEG - 1) / SC_NSEG;
-    const uint64_t seg_cap = blocks_per_seg * rows_per_block;
-    return seg_cap < 64 ? 64 : seg_cap;
-}
+uint64_t result_seg_cap(dim3 grid, uint64_t rows_per_block) { return result_seg_cap((uint64_t)grid.x, rows_per_block); }
 
 // Result set `set` with segments of seg_cap entries, as a kernel addresses it.  The layout is worked out when the set's
 // buffer is reserved or seg_cap changes (the buffer only ever grows, and only here); a scan of the same shape copies it.
