@@ -365,6 +365,41 @@ int psk_tree_fit(psk_ctx *ctx, const float *X, const int32_t *y01, int n, int p,
                  int32_t *node_count_out, int32_t *max_depth_out, int32_t *nodes_out, double *impurity_out,
                  int32_t *leaf_out, double *frac_out);
 
+/* ---- f7: the `-bc RF` estimator -------------------------------------------------------------------
+ * Replaces RandomizedSearchCV over RandomForestClassifier() with the seven-key grid of set_model (modeling.py:1030-1031,
+ * :1057-1068, :1096-1099).  The contract is scikit-learn 1.7.2's forest for a given seed, to the node: the caller draws what
+ * NumPy's RandomState draws and passes it in, the library builds the trees (csrc/solver_forest.hip), a workgroup building
+ * one TREE at a time.  X, y01, n, p as for psk_tree_fit.  Per tree t:
+ *   tree_weight[n_trees][n]    u16 sample weights (bootstrap multiplicities; 0 = not in the tree, which is also how a
+ *                              held-out fold is expressed); at least one must be positive
+ *   tree_state[n_trees]        state of the splitter's 32-bit xorshift (RandomState(seed_t).randint(0, 2^31 - 1))
+ *   tree_fit[n_trees]          the fit (forest) the tree belongs to
+ *   tree_export[n_trees]       != 0: the tree's node arrays are wanted
+ * Per fit f: fit_criterion (0 gini, 1 entropy), fit_max_depth (0 = none), fit_max_features (columns visited per node, 1..p),
+ * fit_min_samples_leaf (>= 1), fit_min_samples_split (>= 2).  Per tree, scikit-learn's depth-first builder over its
+ * BestSplitter: the Fisher-Yates column walk with its constant-feature bookkeeping, the first column in visit order with a
+ * strictly larger proxy, n_node_samples counting distinct in-bag samples, everything else weighted.
+ *   sum0_out[n_fits][n], sum1_out[n_fits][n]   for EVERY sample: the class-0 / class-1 fractions of the leaves it lands in,
+ *                                              added in tree order over the fit's trees (predict_proba x number of trees)
+ *   node_count_out[n_trees], max_depth_out[n_trees]   nodes made, deepest level reached
+ *   tree_node_off_out[n_trees]                 first slot of an exported tree in the node pool (-1: not exported); an
+ *                                              exported tree reserves 2 x (samples of positive weight) - 1 slots, in tree
+ *                                              order; node_pool is the pool's size in slots (PSK_ERANGE if too small)
+ *   nodes_out[node_pool][6]                    feature (-2: leaf), left, right (-1: leaf), n_node_samples, w0, w1 (weighted
+ *                                              class counts)
+ *   impurity_out[node_pool]
+ *   leaf_out[exported trees][n]                every sample's leaf, rows in tree order of the exported trees
+ * (nodes_out / impurity_out / leaf_out may be NULL when no tree is exported.)  The design must be 0/1 (PSK_EINVAL
+ * otherwise); at most 4096 samples (PSK_ERANGE beyond); a tree whose in-bag samples are of one class is a single leaf.
+ */
+int psk_forest_fit(psk_ctx *ctx, const float *X, const int32_t *y01, int n, int p, int n_trees,
+                   const uint16_t *tree_weight, const uint32_t *tree_state, const int32_t *tree_fit,
+                   const int32_t *tree_export, int n_fits, const int32_t *fit_criterion, const int32_t *fit_max_depth,
+                   const int32_t *fit_max_features, const int32_t *fit_min_samples_leaf,
+                   const int32_t *fit_min_samples_split, double *sum0_out, double *sum1_out, int32_t *node_count_out,
+                   int32_t *max_depth_out, int64_t node_pool, int64_t *tree_node_off_out, int32_t *nodes_out,
+                   double *impurity_out, int32_t *leaf_out);
+
 /* ---- f1: fixed-dictionary counting (prediction) ---------------------------------------------
  * Replaces `gmer_counter -db <txt> <addr>` (prediction.Samples.map_samples, prediction.py:72-80):
  * occurrences, both strands with multiplicity, of each dictionary k-mer (canonical words) in

@@ -505,6 +505,56 @@ class PskContext:
                             frac=frac[j].copy()))
         return out
 
+    def forest_fit(self, X, y01, tree_weight, tree_state, tree_fit, fit_criterion, fit_max_depth, fit_max_features,
+                   fit_min_samples_leaf, fit_min_samples_split, export=None):
+        """Random-forest fits (psk_forest_fit): scikit-learn's forest trees for the draws the caller made, one workgroup per
+        tree.  tree_weight[n_trees][n]: integer sample weights (0 = not in the tree); tree_state[n_trees]: the splitter's
+        generator state; tree_fit[n_trees]: the fit a tree belongs to; per fit the criterion (0 / 'gini', 1 / 'entropy'),
+        max_depth (0 / None = no limit), max_features (a number of columns), min_samples_leaf, min_samples_split;
+        export[n_trees]: which trees' node arrays to return (None: all).  Returns (sum0[n_fits][n], sum1[n_fits][n], trees):
+        the two class fractions of every sample's leaves added in tree order, and per tree None or a dict of node_count,
+        max_depth, feature / left / right / n_node_samples / counts[:, 2] (weighted) / impurity by node (pre-order), leaf[n]."""
+        X = np.ascontiguousarray(X, dtype=np.float32)
+        n, p = X.shape
+        y = np.ascontiguousarray(y01, dtype=np.int32)
+        wt = np.asarray(tree_weight)
+        if wt.ndim != 2 or wt.shape[1] != n or wt.min() < 0 or wt.max() > 65535:
+            raise ValueError("tree_weight must be [n_trees][n] integers in 0..65535")
+        wt = np.ascontiguousarray(wt, dtype=np.uint16)
+        nt = wt.shape[0]
+        state = np.ascontiguousarray(tree_state, dtype=np.uint32)
+        tfit = np.ascontiguousarray(tree_fit, dtype=np.int32)
+        flag = np.ones(nt, dtype=np.int32) if export is None else np.ascontiguousarray(np.asarray(export) != 0, dtype=np.int32)
+        crit = np.ascontiguousarray([{"gini": 0, "entropy": 1}.get(c, c) for c in fit_criterion], dtype=np.int32)
+        depth = np.ascontiguousarray([d or 0 for d in fit_max_depth], dtype=np.int32)
+        mf = np.ascontiguousarray(fit_max_features, dtype=np.int32)
+        msl = np.ascontiguousarray(fit_min_samples_leaf, dtype=np.int32)
+        mss = np.ascontiguousarray(fit_min_samples_split, dtype=np.int32)
+        nf = len(crit)
+        if not (len(state) == len(tfit) == len(flag) == nt and len(depth) == len(mf) == len(msl) == len(mss) == nf):
+            raise ValueError("per-tree arrays must have n_trees entries and per-fit arrays n_fits")
+        n_exp = int(flag.sum())
+        pool = int((2 * (wt[flag != 0] != 0).sum(axis=1) - 1).sum()) if n_exp else 0
+        sum0, sum1 = np.zeros((nf, n)), np.zeros((nf, n))
+        count, deepest, off = np.zeros(nt, dtype=np.int32), np.zeros(nt, dtype=np.int32), np.zeros(nt, dtype=np.int64)
+        nodes, imp, leaf = np.zeros((max(pool, 1), 6), dtype=np.int32), np.zeros(max(pool, 1)), np.zeros((max(n_exp, 1), n), dtype=np.int32)
+        self._check(self._lib.psk_forest_fit(self._h, _ptr(X), _ptr(y), n, p, nt, _ptr(wt), _ptr(state), _ptr(tfit), _ptr(flag), nf,
+                                             _ptr(crit), _ptr(depth), _ptr(mf), _ptr(msl), _ptr(mss), _ptr(sum0), _ptr(sum1),
+                                             _ptr(count), _ptr(deepest), pool, _ptr(off), _ptr(nodes), _ptr(imp), _ptr(leaf)),
+                    "psk_forest_fit")
+        trees, row = [], 0
+        for t in range(nt):
+            if not flag[t]:
+                trees.append(None)
+                continue
+            a, k = int(off[t]), int(count[t])
+            nd = nodes[a:a + k]
+            trees.append(dict(node_count=k, max_depth=int(deepest[t]), feature=nd[:, 0].astype(np.int64), left=nd[:, 1].astype(np.int64),
+                              right=nd[:, 2].astype(np.int64), n_node_samples=nd[:, 3].astype(np.int64),
+                              counts=nd[:, 4:6].astype(np.int64), impurity=imp[a:a + k].copy(), leaf=leaf[row].astype(np.int64)))
+            row += 1
+        return sum0, sum1, trees
+
     # -- population-structure weights --------------------------------------------------------------
     def minhash_sketch(self, data, k=21, sketch_size=1000, seed=42):
         data = bytes(data)

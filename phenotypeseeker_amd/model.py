@@ -8,7 +8,9 @@ refit) are solved on the GPU in one psk_logreg_l1_fit / psk_lasso_fit launch.  `
 (modeling.py:1001-1002, :1015-1019) maps to RidgeRegression / L2LogisticRegression over
 psk_ridge_fit / psk_logreg_l2_fit in the same way, `-bc SVM` (modeling.py:1025-1029) to SVC over
 psk_svc_fit, whose folds are scored from the decision values the engine returns, and `-bc DT` (modeling.py:1032-1033) to
-DecisionTree over psk_tree_fit under a two-key grid, scored from the leaves the engine returns for every sample.
+DecisionTree over psk_tree_fit under a two-key grid, scored from the leaves the engine returns for every sample, and `-bc RF`
+(modeling.py:1030-1031) to RandomForest over psk_forest_fit under RandomizedSearch: scikit-learn's forest and sampler for a
+given seed, the host drawing what NumPy's RandomState draws.
 """
 import numpy as np
 
@@ -335,13 +337,16 @@ class Tree:
     pre-order, threshold 0.5 at a split and -2 at a leaf, value the class fractions ([node_count][1][2], scikit-learn >= 1.3)."""
     n_outputs, max_n_classes = 1, 2
 
-    def __init__(self, n_features, feature, left, right, n_node_samples, counts, impurity, max_depth):
+    def __init__(self, n_features, feature, left, right, n_node_samples, counts, impurity, max_depth, weighted_n_node_samples=None):
+        """counts: the class counts by node; in a forest's tree they are weighted (bootstrap multiplicities) and
+        weighted_n_node_samples is their sum, while n_node_samples counts the distinct samples."""
         self.n_features = int(n_features)
         self.n_classes = np.array([2], dtype=np.int64)
         self.feature = np.asarray(feature, dtype=np.int64)
         self.children_left, self.children_right = np.asarray(left, dtype=np.int64), np.asarray(right, dtype=np.int64)
         self.n_node_samples = np.asarray(n_node_samples, dtype=np.int64)
-        self.weighted_n_node_samples = self.n_node_samples.astype(np.float64)
+        self.weighted_n_node_samples = (self.n_node_samples.astype(np.float64) if weighted_n_node_samples is None
+                                        else np.asarray(weighted_n_node_samples, dtype=np.float64))
         self.impurity = np.asarray(impurity, dtype=np.float64)
         self.threshold = np.where(self.feature >= 0, 0.5, -2.0)
         self.value = (np.asarray(counts, dtype=np.float64) / self.weighted_n_node_samples[:, None]).reshape(-1, 1, 2)
@@ -397,7 +402,8 @@ class Tree:
     def _from_sklearn_state(cls, n_features, state):
         nd, val = state["nodes"], np.asarray(state["values"], dtype=np.float64)
         t = cls(n_features, nd["feature"], nd["left_child"], nd["right_child"], nd["n_node_samples"],
-                val[:, 0, :] * np.asarray(nd["weighted_n_node_samples"], dtype=np.float64)[:, None], nd["impurity"], state["max_depth"])
+                val[:, 0, :] * np.asarray(nd["weighted_n_node_samples"], dtype=np.float64)[:, None], nd["impurity"], state["max_depth"],
+                weighted_n_node_samples=nd["weighted_n_node_samples"])
         t.threshold, t.value = np.asarray(nd["threshold"], dtype=np.float64), val.reshape(-1, 1, val.shape[-1])
         return t
 
@@ -477,6 +483,226 @@ class DecisionTree:
 
     def score(self, X, y):
         return np.float64(np.mean(self.predict(X) == np.asarray(y)))
+
+
+def _sk_repr(name, parts, width=80):
+    """name(part, part, ...) broken into lines as scikit-learn's estimator printer does (utils/_pprint.py, compact): greedy
+    filling of `width` columns, continuation lines indented to the opening parenthesis."""
+    indent = len(name) + 1
+    room = full = width - indent + 1
+    out, delim = [], ""
+    for i, rep in enumerate(parts):
+        if i == len(parts) - 1:          # the closing parenthesis
+            full -= 1
+            room -= 1
+        w = len(rep) + 2
+        if room < w:
+            room = full
+            if delim:
+                delim = ",\n" + " " * indent
+        if room >= w:
+            room -= w
+        out.append(delim + rep)
+        delim = ", "
+    return "%s(%s)" % (name, "".join(out))
+
+
+RAND_R_MAX = 2147483647   # sklearn/utils/_random.pxd
+
+
+class ForestDraws:
+    """Everything scikit-learn draws from NumPy's RandomState for RandomForestClassifier(random_state=seed), on the host:
+    tree t's seed is the t-th rs.randint(int32 max) of rs = RandomState(seed) (ensemble/_base.py::_set_random_states, drawn in
+    tree order before any fit); the splitter's generator state is RandomState(seed_t).randint(0, RAND_R_MAX)
+    (_splitter.pyx::Splitter.init); with bootstrap the tree trains on bincount(RandomState(seed_t).randint(0, n_train,
+    n_train, dtype=int32)) as sample weights (ensemble/_forest.py::_generate_sample_indices), mapped through the training
+    rows.  Draws are kept: the candidates of a search share their trees' seeds (clone keeps an integer random_state)."""
+
+    def __init__(self, seed, n_all):
+        self.rs = np.random.RandomState(int(seed))
+        self.n_all = int(n_all)
+        self.seeds, self.states, self.weights = [], [], {}
+
+    def state(self, t):
+        while len(self.seeds) <= t:
+            self.seeds.append(int(self.rs.randint(np.iinfo(np.int32).max)))
+            self.states.append(int(np.random.RandomState(self.seeds[-1]).randint(0, RAND_R_MAX)))
+        return self.states[t]
+
+    def weight(self, t, rows_key, rows, bootstrap):
+        """uint16[n_all]: tree t's sample weights when it trains on the (ascending) sample rows `rows`; rows_key names them."""
+        key = (t if bootstrap else -1, rows_key)
+        w = self.weights.get(key)
+        if w is None:
+            w = np.zeros(self.n_all, dtype=np.uint16)
+            if bootstrap:
+                self.state(t)
+                idx = np.random.RandomState(self.seeds[t]).randint(0, len(rows), len(rows), dtype=np.int32)
+                w[rows] = np.bincount(idx, minlength=len(rows))
+            else:
+                w[rows] = 1
+            self.weights[key] = w
+        return w
+
+
+class ForestTree(DecisionTree):
+    """One tree of a RandomForest: a DecisionTree whose tree_ carries weighted class counts (model.Tree with
+    weighted_n_node_samples) and which, as in scikit-learn, knows its own seed and the forest's parameters."""
+
+    def __init__(self, criterion="gini", max_depth=None, min_samples_split=2, min_samples_leaf=1, max_features="sqrt", random_state=None):
+        super().__init__(criterion, max_depth)
+        self.min_samples_split, self.min_samples_leaf, self.max_features, self.random_state = (
+            min_samples_split, min_samples_leaf, max_features, random_state)
+
+    def _set_fit(self, fit, n_features):
+        self.tree_ = Tree(n_features, fit["feature"], fit["left"], fit["right"], fit["n_node_samples"], fit["counts"],
+                          fit["impurity"], fit["max_depth"], weighted_n_node_samples=np.asarray(fit["counts"]).sum(axis=1))
+        self.n_features_in_ = int(n_features)
+        self.n_outputs_, self.n_classes_ = 1, np.int64(2)
+        self.max_features_ = RandomForest.n_max_features(self.max_features, n_features)
+        return self
+
+    def _sklearn_state(self):
+        return dict(n_features_in_=self.n_features_in_, n_outputs_=1, classes_=np.array([0.0, 1.0]), n_classes_=np.int64(2),
+                    max_features_=int(self.max_features_))
+
+
+class RandomForest:
+    """sklearn.ensemble.RandomForestClassifier for two classes on a 0/1 design (set_model, modeling.py:1030-1031) over
+    psk_forest_fit: for an integer random_state, scikit-learn 1.7.2's forest to the node.  The seven
+    parameters of the reference's grid plus random_state; everything else at scikit-learn's defaults."""
+    _is_classifier = True
+    _fits_forest = True
+    PARAMS = ("bootstrap", "criterion", "max_depth", "max_features", "min_samples_leaf", "min_samples_split", "n_estimators")
+    DEFAULTS = dict(bootstrap=True, criterion="gini", max_depth=None, max_features="sqrt", min_samples_leaf=1, min_samples_split=2,
+                    n_estimators=100)
+    TREE_PARAMS = ("criterion", "max_depth", "min_samples_split", "min_samples_leaf", "min_weight_fraction_leaf", "max_features",
+                   "max_leaf_nodes", "min_impurity_decrease", "random_state", "ccp_alpha", "monotonic_cst")   # estimator_params
+    SCRATCH_BYTES = 1 << 30   # per engine call: 16 bytes per tree and sample of leaf fractions
+
+    def __init__(self, n_estimators=100, criterion="gini", max_depth=None, min_samples_split=2, min_samples_leaf=1,
+                 max_features="sqrt", bootstrap=True, random_state=0):
+        self.n_estimators, self.criterion, self.max_depth = n_estimators, criterion, max_depth
+        self.min_samples_split, self.min_samples_leaf, self.max_features = min_samples_split, min_samples_leaf, max_features
+        self.bootstrap, self.random_state = bootstrap, random_state
+        self._check(self.get_params())
+        self.classes_ = np.array([0, 1])
+        self.estimators_ = None
+
+    @staticmethod
+    def _check(q):
+        if q["criterion"] not in ("gini", "entropy"):
+            raise ValueError("RandomForest: criterion must be 'gini' or 'entropy', got %r" % (q["criterion"],))
+        if q["max_features"] not in (None, "sqrt", "log2"):
+            raise ValueError("RandomForest: max_features must be None, 'sqrt' or 'log2', got %r" % (q["max_features"],))
+        if q["max_depth"] is not None and int(q["max_depth"]) < 1:
+            raise ValueError("RandomForest: max_depth must be None or >= 1, got %r" % (q["max_depth"],))
+        if int(q["n_estimators"]) < 1 or int(q["min_samples_leaf"]) < 1 or int(q["min_samples_split"]) < 2:
+            raise ValueError("RandomForest: n_estimators >= 1, min_samples_leaf >= 1 and min_samples_split >= 2 are required")
+
+    def get_params(self):
+        return {k: getattr(self, k) for k in self.PARAMS}
+
+    def __repr__(self):
+        parts = ["%s=%r" % (k, getattr(self, k)) for k in self.PARAMS if getattr(self, k) != self.DEFAULTS[k]]
+        if self.random_state is not None:
+            parts.append("random_state=%r" % (self.random_state,))
+        return _sk_repr("RandomForestClassifier", parts)
+
+    def _clone(self, **params):
+        kw = dict(self.get_params(), random_state=self.random_state)
+        kw.update(params)
+        return type(self)(**kw)
+
+    @staticmethod
+    def n_max_features(max_features, p):
+        """tree/_classes.py: None -> p, 'sqrt' -> max(1, int(sqrt(p))), 'log2' -> max(1, int(log2(p)))."""
+        if max_features is None:
+            return int(p)
+        return max(1, int(np.sqrt(p))) if max_features == "sqrt" else max(1, int(np.log2(p)))
+
+    def _engine_fits(self, ctx, X, y, jobs, export):
+        """jobs: (parameter dict, rows_key, training rows) per forest; keys a dict lacks come from this estimator.  Every
+        forest's trees go into one psk_forest_fit call, or into several when the leaf fractions of all trees would exceed
+        SCRATCH_BYTES on the device.  Returns per job (proba[n][2] of every sample of X, the trees or None)."""
+        y = np.asarray(y)
+        if not set(y.tolist()) <= {0, 1}:
+            raise ValueError("RandomForest: the two classes must be labelled 0 and 1")
+        if self.random_state is None:
+            raise ValueError("RandomForest: random_state must be an integer (the fit reproduces scikit-learn's for that seed)")
+        n, p = X.shape
+        draws = ForestDraws(self.random_state, n)
+        per_call = max(1, self.SCRATCH_BYTES // (16 * n))
+        params = [dict(self.get_params(), **q) for q, _, _ in jobs]
+        for q in params:
+            self._check(q)
+        out, at = [], 0
+        while at < len(jobs):
+            end, n_trees = at, 0
+            while end < len(jobs) and (end == at or n_trees + int(params[end]["n_estimators"]) <= per_call):
+                n_trees += int(params[end]["n_estimators"])
+                end += 1
+            weight, state, tree_fit = [], [], []
+            for f in range(at, end):
+                q, (_, rows_key, rows) = params[f], jobs[f]
+                for t in range(int(q["n_estimators"])):
+                    state.append(draws.state(t))
+                    weight.append(draws.weight(t, rows_key, rows, bool(q["bootstrap"])))
+                    tree_fit.append(f - at)
+            chunk = params[at:end]
+            s0, s1, trees = ctx.forest_fit(X, y.astype(np.int32), np.array(weight), state, tree_fit, [q["criterion"] for q in chunk],
+                                           [q["max_depth"] for q in chunk], [self.n_max_features(q["max_features"], p) for q in chunk],
+                                           [int(q["min_samples_leaf"]) for q in chunk], [int(q["min_samples_split"]) for q in chunk],
+                                           export=np.full(len(state), bool(export)))
+            k = 0
+            for f, q in enumerate(chunk):
+                T = int(q["n_estimators"])
+                out.append((np.column_stack([s0[f] / T, s1[f] / T]), trees[k:k + T] if export else None))
+                k += T
+            at = end
+        return out, draws
+
+    def fit(self, X, y, engine_ctx):
+        X = np.asarray(X, dtype=np.float64)
+        (res,), draws = self._engine_fits(engine_ctx, X, y, [({}, "all", np.arange(X.shape[0]))], True)
+        return self._set_fit(res[1], draws, X.shape[1], X.shape[0])
+
+    def _set_fit(self, trees, draws, n_features, n_samples):
+        self.estimators_ = [ForestTree(self.criterion, self.max_depth, self.min_samples_split, self.min_samples_leaf, self.max_features,
+                                       draws.seeds[t])._set_fit(fit, n_features) for t, fit in enumerate(trees)]
+        self.n_features_in_, self._n_samples = int(n_features), int(n_samples)
+        return self
+
+    def predict_proba(self, X):
+        """ForestClassifier.predict_proba: the trees' leaf fractions added in tree order, class by class, over their number."""
+        X = np.asarray(X, dtype=np.float64)
+        total = np.zeros((X.shape[0], 2))
+        for e in self.estimators_:
+            total += e.predict_proba(X)
+        total /= len(self.estimators_)
+        return total
+
+    def predict(self, X):
+        # np.argmax: class 1 only when its probability is strictly larger
+        return self.classes_[np.argmax(self.predict_proba(X), axis=1)]
+
+    def score(self, X, y):
+        return np.float64(np.mean(self.predict(X) == np.asarray(y)))
+
+    @property
+    def feature_importances_(self):
+        """The mean over the trees with more than one node of their normalised importances, renormalised by its sum."""
+        rows = [e.tree_.compute_feature_importances() for e in self.estimators_ if e.tree_.node_count > 1]
+        if not rows:
+            return np.zeros(self.n_features_in_)
+        mean = np.mean(rows, axis=0, dtype=np.float64)
+        return mean / np.sum(mean)
+
+    def _sklearn_state(self):
+        """The fitted attributes of sklearn.ensemble.RandomForestClassifier (scikit-learn 1.7) but estimator / estimator_ /
+        estimators_, which hold estimators of their own."""
+        return dict(estimator_params=self.TREE_PARAMS, n_features_in_=self.n_features_in_, _n_samples=self._n_samples, n_outputs_=1,
+                    classes_=np.array([0, 1]), n_classes_=2, _n_samples_bootstrap=self._n_samples if self.bootstrap else None)
 
 
 def platt_sigmoid_train(dec, positive):
@@ -769,6 +995,138 @@ class GridSearch:
         gs.n_splits_, gs.refit_time_, gs.multimetric_ = self.n_splits_, 0.0, False
         gs.scorer_ = None
         return gs
+
+
+class RandomizedSearch(GridSearch):
+    """RandomizedSearchCV(estimator, grid of lists, n_iter, cv=int, random_state=int) with refit, for RandomForest (get_best_model,
+    modeling.py:1096-1099).  The candidates are scikit-learn's for that random_state: ParameterGrid(grid)[i] (keys sorted, the
+    last key fastest) for the i that sample_without_replacement(grid_size, n_iter, random_state) yields.  Only its tracking
+    selection is restated -- the regime n_iter / grid_size < 0.01, where the reference's default 25 of 10,692 lies; another
+    n_iter is refused.  Every candidate x fold is fitted first, scored from the forests' sums on the held-out samples;
+    only the best candidate is refitted on everything, with its trees returned."""
+    TRACKING_RATIO = 0.01
+
+    def __init__(self, estimator, param_grid, n_iter, cv, random_state=0):
+        super().__init__(estimator, dict(param_grid), cv=cv)
+        self.n_iter, self.random_state = int(n_iter), random_state
+
+    def grid_size(self):
+        return int(np.prod([len(v) for v in self.param_grid.values()]))
+
+    @classmethod
+    def max_n_iter(cls, grid_size):
+        """The largest n_iter of the restated regime: n_iter / grid_size < 0.01."""
+        k = int(grid_size * cls.TRACKING_RATIO)
+        while k > 0 and not k / grid_size < cls.TRACKING_RATIO:
+            k -= 1
+        return k
+
+    def grid_point(self, i):
+        """ParameterGrid(grid)[i], its keys in ParameterGrid's order (the last sorted key first)."""
+        out = {}
+        for k in reversed(sorted(self.param_grid)):
+            i, r = divmod(i, len(self.param_grid[k]))
+            out[k] = self.param_grid[k][r]
+        return out
+
+    def sampled_indices(self):
+        size = self.grid_size()
+        n_iter = min(self.n_iter, size)           # scikit-learn caps n_iter at the grid size (with a warning)
+        if n_iter < 1 or not n_iter / size < self.TRACKING_RATIO:
+            raise ValueError("RandomizedSearch draws its candidates as scikit-learn does for n_iter / grid size < %g only: "
+                             "n_iter must be 1..%d for this grid of %d points, got %d"
+                             % (self.TRACKING_RATIO, self.max_n_iter(size), size, self.n_iter))
+        rs = np.random.RandomState(int(self.random_state))
+        taken, out = set(), []
+        for _ in range(n_iter):                   # utils/_random.pyx::_sample_without_replacement_with_tracking_selection
+            j = int(rs.randint(size))
+            while j in taken:
+                j = int(rs.randint(size))
+            taken.add(j)
+            out.append(j)
+        return out
+
+    def candidates(self):
+        return [self.grid_point(i) for i in self.sampled_indices()]
+
+    def fit(self, X, y, engine_ctx):
+        if not getattr(self.estimator, "_fits_forest", False):
+            raise ValueError("RandomizedSearch searches RandomForest only")
+        X = np.asarray(X, dtype=np.float64)
+        y = np.asarray(y)
+        if self.cv < 2:
+            raise ValueError("k-fold cross-validation requires at least one train/test split by setting "
+                             "n_splits=2 or more, got n_splits=%d." % self.cv)
+        cand = self.candidates()
+        folds = _cv.stratified_kfold(y, self.cv)
+        rows = [np.nonzero(folds != f)[0] for f in range(self.cv)]
+        jobs = [(q, f, rows[f]) for q in cand for f in range(self.cv)]
+        fits, _ = self.estimator._engine_fits(engine_ctx, X, y, jobs, False)
+        scores = np.zeros((len(cand), self.cv))
+        for gi in range(len(cand)):
+            for f in range(self.cv):
+                te = folds == f
+                proba = fits[gi * self.cv + f][0][te]
+                scores[gi, f] = np.mean(self.estimator.classes_[np.argmax(proba, axis=1)] == y[te])
+        self._store(cand, scores)
+        self.best_estimator_ = self.estimator._clone(**cand[self.best_index_]).fit(X, y, engine_ctx)
+        self.n_unique_columns_ = int(X.shape[1])
+        self.n_splits_ = self.cv
+        self.test_folds_ = folds
+        return self
+
+    @staticmethod
+    def _forest_shell(sp, rf, fitted):
+        kw = dict(rf.get_params(), random_state=rf.random_state, estimator=sp.make("DecisionTreeClassifier"),
+                  estimator_params=RandomForest.TREE_PARAMS)
+        if fitted:
+            trees = []
+            for e in rf.estimators_:
+                t = sp.make("DecisionTreeClassifier", criterion=e.criterion, max_depth=e.max_depth, min_samples_split=e.min_samples_split,
+                            min_samples_leaf=e.min_samples_leaf, max_features=e.max_features, random_state=e.random_state,
+                            **e._sklearn_state())
+                if t is None:
+                    return None
+                t.state["tree_"] = sp.Reduced("sklearn.tree._tree", "Tree", (e.n_features_in_, np.array([2], dtype=np.int64), 1),
+                                              e.tree_._sklearn_state())
+                trees.append(t)
+            kw.update(rf._sklearn_state(), estimator_=sp.make("DecisionTreeClassifier"), estimators_=trees)
+        return None if kw["estimator"] is None else sp.make("RandomForestClassifier", **kw)
+
+    def to_sklearn_shell(self):
+        from . import skpickle as sp
+        est, proto = self._forest_shell(sp, self.best_estimator_, True), self._forest_shell(sp, self.estimator, False)
+        if est is None or proto is None:
+            return None
+        return sp.make("RandomizedSearchCV", estimator=proto, param_distributions=self.param_grid, n_iter=self.n_iter,
+                       random_state=self.random_state, cv=self.cv, best_estimator_=est, best_params_=dict(self.best_params_),
+                       best_index_=self.best_index_, best_score_=self.best_score_, cv_results_=dict(self.cv_results_),
+                       n_splits_=self.n_splits_, refit_time_=0.0, multimetric_=False, scorer_=None)
+
+    def to_sklearn(self):
+        from sklearn.ensemble import RandomForestClassifier
+        from sklearn.model_selection import RandomizedSearchCV
+        from sklearn.tree import DecisionTreeClassifier
+        from sklearn.tree._tree import Tree as SkTree
+        be = self.best_estimator_
+        est = RandomForestClassifier(random_state=be.random_state, **be.get_params())
+        est.__dict__.update({k: v for k, v in be._sklearn_state().items() if k != "estimator_params"})
+        est.estimator_, est.estimators_ = DecisionTreeClassifier(), []
+        for e in be.estimators_:
+            t = DecisionTreeClassifier(criterion=e.criterion, max_depth=e.max_depth, min_samples_split=e.min_samples_split,
+                                       min_samples_leaf=e.min_samples_leaf, max_features=e.max_features, random_state=e.random_state)
+            t.__dict__.update(e._sklearn_state())
+            t.tree_ = SkTree(e.n_features_in_, np.array([2], dtype=np.intp), 1)
+            t.tree_.__setstate__(e.tree_._sklearn_state())
+            est.estimators_.append(t)
+        proto = RandomForestClassifier(random_state=self.estimator.random_state, **self.estimator.get_params())
+        rs = RandomizedSearchCV(proto, self.param_grid, n_iter=self.n_iter, cv=self.cv, random_state=self.random_state)
+        rs.best_estimator_, rs.best_params_ = est, dict(self.best_params_)
+        rs.best_index_, rs.best_score_ = self.best_index_, self.best_score_
+        rs.cv_results_ = dict(self.cv_results_)
+        rs.n_splits_, rs.refit_time_, rs.multimetric_ = self.n_splits_, 0.0, False
+        rs.scorer_ = None
+        return rs
 
 
 def _unique_columns(X):

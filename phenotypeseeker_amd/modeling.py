@@ -29,7 +29,8 @@ from . import formats, metrics, _stats
 from .engine import PskContext
 from . import _lib
 from ._lib import PSK_EGZIP, PskError
-from .model import SVC, DecisionTree, GridSearch, L1LogisticRegression, L2LogisticRegression, LassoRegression, RidgeRegression
+from .model import (SVC, DecisionTree, GridSearch, L1LogisticRegression, L2LogisticRegression, LassoRegression, RandomForest,
+                    RandomizedSearch, RidgeRegression)
 
 RED_BANNER = "\x1b[1;1;101m%s\x1b[0m\n"
 GREEN = "\x1b[1;32m%s\x1b[0m"
@@ -342,8 +343,8 @@ class Input:
                    n_iter, n_splits_cv_inner, testset_size, train_on_whole, logreg_solver, jump_to, pca,
                    real_counts, omit_B, kmerDB):
         """Same positional signature as the reference (:141-183).  Options that select estimators
-        outside the hot path (SVM/RF/DT/NB, L2/elastic net, saga, PCA) are rejected here; `-bc SVM` and `-bc DT` pass
-        with their knobs (PSK_SVM, PSK_DT)."""
+        outside the hot path (SVM/RF/DT/NB, L2/elastic net, saga, PCA) are rejected here; `-bc SVM`, `-bc DT` and `-bc RF` pass
+        with their knobs (PSK_SVM, PSK_DT, PSK_RF)."""
         if alphas is None:
             phenotypes.alphas = np.logspace(math.log10(alpha_min), math.log10(alpha_max), num=n_alphas)
         else:
@@ -392,6 +393,24 @@ class Input:
                                      "--pca is not supported with -bc DT.")
                 phenotypes.binary_classifier = "DT"
                 phenotypes.model_name_long, phenotypes.model_name_short = "decision tree", "DT"
+            elif binary_classifier == "RF" and _lib.env_flag("PSK_RF"):
+                # set_model (:1030-1031, :1057-1068) under get_best_model's RandomizedSearchCV(n_iter, cv) (:1096-1099).  The
+                # reference leaves every draw unseeded; here the seed is PSK_RF_SEED and the run is scikit-learn's for that seed
+                if real_counts:
+                    raise SystemExit("The random forest on the GPU engine takes the 0/1 presence matrix only: "
+                                     "--real_counts is not supported with -bc RF.")
+                if pca:
+                    raise SystemExit("The random forest on the GPU engine takes the 0/1 presence matrix only: "
+                                     "--pca is not supported with -bc RF.")
+                phenotypes.rf_seed = _rf_seed()
+                phenotypes.n_iter = int(n_iter)
+                size = int(np.prod([len(v) for v in RF_GRID.values()]))
+                if not 1 <= phenotypes.n_iter <= RandomizedSearch.max_n_iter(size):
+                    raise SystemExit("The random forest's randomized search draws its candidates as scikit-learn does for "
+                                     "n_iter / grid size < 0.01 only: --n_iter must be 1..%d for the grid of %d points, got %d."
+                                     % (RandomizedSearch.max_n_iter(size), size, phenotypes.n_iter))
+                phenotypes.binary_classifier = "RF"
+                phenotypes.model_name_long, phenotypes.model_name_short = "random forest", "RF"
             elif binary_classifier != "log":
                 raise SystemExit("Only the logistic-regression classifier runs on the GPU engine, got %r "
                                  "(SVM/RF/DT/NB are outside the accelerated path)." % binary_classifier)
@@ -421,6 +440,22 @@ class Input:
             raise SystemExit("--pca is outside the accelerated path.")
 
 
+# set_model's hyper-parameters of the random forest, in the reference's own spelling and order (:1057-1068)
+RF_GRID = {"bootstrap": [True, False], "max_depth": [4, 5, 6, 7, 8, 10, 20, 100, None], "max_features": [None, "sqrt", "log2"],
+           "min_samples_leaf": [1, 2, 4], "min_samples_split": [2, 5, 10],
+           "n_estimators": [10, 20, 40, 60, 80, 100, 120, 140, 160, 180, 200], "criterion": ["gini", "entropy"]}
+
+
+def _rf_seed():
+    """PSK_RF_SEED (docs/KNOBS.md): the random_state of the forest and of its randomized search, 0 .. 2^32 - 1."""
+    text = os.environ.get("PSK_RF_SEED", "")
+    if text == "":
+        return 0
+    if not text.isdigit() or int(text) > 0xFFFFFFFF:
+        raise SystemExit("PSK_RF_SEED must be an integer 0 .. 4294967295, got %r." % text)
+    return int(text)
+
+
 class phenotypes:
     pred_scale = "binary"
     real_counts = False
@@ -433,6 +468,8 @@ class phenotypes:
     penalty = None
     binary_classifier = "log"
     kernel = None
+    n_iter = None
+    rf_seed = 0
     logreg_solver = None
     max_iter = None
     tol = None
@@ -686,6 +723,8 @@ class phenotypes:
             if self.binary_classifier == "DT":
                 # (a grid of two parameters goes to GridSearch as a dictionary, in the reference's own spelling, :1069-1073)
                 return DecisionTree(), {"max_depth": [1, 2, 3, 4, 5, 6, 7, 8, 9, 10], "criterion": ["gini", "entropy"]}, None
+            if self.binary_classifier == "RF":
+                return RandomForest(random_state=self.rf_seed), {k: list(v) for k, v in RF_GRID.items()}, None
             if self.binary_classifier == "SVM":
                 return SVC(kernel=self.kernel, probability=True, max_iter=self.max_iter, tol=self.tol), "C", grid
             if self.penalty == "L2":
@@ -699,6 +738,9 @@ class phenotypes:
     def _fit(self, ctx, X, y):
         est, pname, grid = self._new_estimator()
         self.model = est
+        if isinstance(est, RandomForest):
+            self.model_fitted = RandomizedSearch(est, pname, self.n_iter, self.n_splits_cv_inner, random_state=self.rf_seed).fit(X, y, ctx)
+            return
         self.model_fitted = GridSearch(est, pname, grid, self.n_splits_cv_inner).fit(X, y, ctx)
         if isinstance(est, SVC) and int(est.max_iter) != -1 and np.any(self.model_fitted.n_iter_ >= int(est.max_iter)):
             # scikit-learn's ConvergenceWarning (svm/_base.py, _warn_from_fit_status), once per grid search
@@ -874,7 +916,7 @@ class phenotypes:
         with open(path, "w") as out:
             out.write("K-mer\tcoef._in_" + self.model_name_short + "_model\tNo._of_samples_with_k-mer\tSamples_with_k-mer\n")
         be = self.model_fitted.best_estimator_
-        if isinstance(be, DecisionTree):
+        if isinstance(be, (DecisionTree, RandomForest)):
             coefs = be.feature_importances_      # (:1430-1432: the importances stand in the coefficient column)
         else:
             coefs = be.coef_[0] if self.pred_scale == "binary" else be.coef_

@@ -83,6 +83,11 @@ def _emit(obj, out):
             _emit(k, out)
             _emit(v, out)
         out.append(b"u")                                                              # SETITEMS
+    elif isinstance(obj, list) and _has_shell(obj):
+        out.append(b"](")                                                             # EMPTY_LIST, MARK
+        for v in obj:
+            _emit(v, out)
+        out.append(b"e")                                                              # APPENDS
     else:
         # a leaf: the standard pickler's stream without its PROTO header and STOP; its memo indices start from 0 again,
         # which is harmless -- every GET of a fragment refers to a PUT of the same fragment, executed just before
@@ -96,6 +101,8 @@ def _has_shell(obj):
         return True
     if isinstance(obj, dict):
         return any(_has_shell(v) for v in obj.values())
+    if isinstance(obj, list):
+        return any(_has_shell(v) for v in obj)
     return False
 
 
@@ -214,11 +221,32 @@ def _tree_from_state(est):
     return m
 
 
+def _forest_from_state(est):
+    """model.RandomForest from the attribute dictionary of a fitted two-class, single-output
+    sklearn.ensemble.RandomForestClassifier whose estimators_ came through the stub: every tree as _tree_from_state reads
+    it.  None for anything else."""
+    from .model import RandomForest
+    d = est.__dict__
+    classes, trees = d.get("classes_"), d.get("estimators_")
+    if classes is None or getattr(classes, "ndim", 0) != 1 or list(classes) != [0, 1] or d.get("n_outputs_") != 1 or not trees:
+        return None
+    models = [_tree_from_state(t) for t in trees]
+    if any(m is None for m in models):
+        return None
+    m = RandomForest(n_estimators=d.get("n_estimators", len(models)), criterion=d.get("criterion", "gini"), max_depth=d.get("max_depth"),
+                     min_samples_split=d.get("min_samples_split", 2), min_samples_leaf=d.get("min_samples_leaf", 1),
+                     max_features=d.get("max_features", "sqrt"), bootstrap=d.get("bootstrap", True), random_state=d.get("random_state"))
+    m.estimators_ = models
+    m.n_features_in_ = int(d["n_features_in_"])
+    return m
+
+
 def load_linear_package(path):
     """The model package of `path` ({'model', 'kmers', 'pca', 'pred_scale'}) with 'model' as a LinearModel -- for files
     that are plain pickles of a (grid search over a) binary linear classifier or a linear regressor, which is what
     `modeling` writes; a two-class SVC with a Platt pair comes back as model.SVC (_svc_from_state), a two-class decision tree
-    as model.DecisionTree (_tree_from_state).  None for anything else
+    as model.DecisionTree (_tree_from_state), a two-class random forest as model.RandomForest (_forest_from_state).  None for
+    anything else
     (joblib-wrapped arrays, multi-class models, other estimators, a PCA pipeline): the caller then takes joblib.load and
     scikit-learn itself."""
     try:
@@ -232,6 +260,11 @@ def load_linear_package(path):
         coef, icpt = getattr(est, "coef_", None), getattr(est, "intercept_", None)
         if kind == "DecisionTreeClassifier":
             model = _tree_from_state(est)
+            if model is None:
+                return None
+            return dict(pkg, model=model)
+        if kind == "RandomForestClassifier":
+            model = _forest_from_state(est)
             if model is None:
                 return None
             return dict(pkg, model=model)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Records, for the installed scikit-learn, what a default-constructed LogisticRegression / Lasso / Ridge / SVC /
-DecisionTreeClassifier / GridSearchCV pickles as (module, class name, state) into phenotypeseeker_amd/sklearn_shells.json, keyed by the
+DecisionTreeClassifier / RandomForestClassifier / GridSearchCV / RandomizedSearchCV pickles as (module, class name, state) into phenotypeseeker_amd/sklearn_shells.json, keyed by the
 scikit-learn version.  phenotypeseeker_amd/skpickle.py writes model files from these templates without importing
 scikit-learn (0.3-0.5 s, as long as the rest of a 256-genome `modeling` run); a version without a template takes the
 import.  usage: tools/make_sklearn_shells.py"""
@@ -9,8 +9,9 @@ import math
 import os
 
 import sklearn
+from sklearn.ensemble import RandomForestClassifier
 from sklearn.linear_model import Lasso, LogisticRegression, Ridge
-from sklearn.model_selection import GridSearchCV
+from sklearn.model_selection import GridSearchCV, RandomizedSearchCV
 from sklearn.svm import SVC
 from sklearn.tree import DecisionTreeClassifier
 
@@ -42,6 +43,9 @@ out[sklearn.__version__] = {
     "Ridge": shell(Ridge()),
     "SVC": shell(SVC()),
     "DecisionTreeClassifier": shell(DecisionTreeClassifier()),
+    # (estimator: a DecisionTreeClassifier shell, estimator_params: a tuple of names -- both filled in by model.py)
+    "RandomForestClassifier": shell(RandomForestClassifier(), drop=("estimator", "estimator_params")),
+    "RandomizedSearchCV": shell(RandomizedSearchCV(LogisticRegression(), {"C": [1.0]}), drop=("estimator", "param_distributions")),
     "GridSearchCV": shell(GridSearchCV(LogisticRegression(), {"C": [1.0]}), drop=("estimator", "param_grid")),
 }
 with open(path, "w") as f:
