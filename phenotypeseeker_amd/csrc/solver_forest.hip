@@ -2,7 +2,8 @@
 // the seven-key grid of set_model (modeling.py:1030-1031, :1057-1068, :1096-1099).  The contract is scikit-learn 1.7.2's forest
 // for a GIVEN seed, to the node: the host draws everything NumPy's RandomState draws (tree seeds, the
 // bootstrap multiplicities, the splitter's generator state) and this unit builds the trees, running only the 32-bit xorshift
-// of sklearn/utils/_random.pxd::our_rand_r.  What differs from solver_tree.hip's tree:
+// of sklearn/utils/_random.pxd::our_rand_r.  The packed design, the impurity expressions and the node record are the decision
+// tree's (solver_tree_common.h).  What differs from its tree:
 //   * a sample carries an integer weight (its bootstrap multiplicity; 0 = not in the tree, which is also how a held-out fold is
 //     expressed).  n_node_samples counts DISTINCT in-bag samples, class counts / impurities / proxies use the weights
 //   * a node visits a random subset of the columns: _splitter.pyx::node_split_best's Fisher-Yates walk over features[] with its
@@ -11,8 +12,8 @@
 //     order with a strictly larger proxy (no lowest-index rule).  The generator advances only in nodes that reach the search
 //   * min_samples_leaf (on distinct in-bag samples: a column whose split leaves fewer on a side is visited but offers no
 //     split), min_samples_split, and no bound on the depth
-// Leaf rules, pre-order numbering, impurity expressions and their order are those of solver_tree.hip with weighted counts in
-// place of counts; improvement = (w_node / w_tree) (I - w_r / w_node I_r - w_l / w_node I_l).  f64, no FMA fusion.
+// Leaf rules and pre-order numbering are the decision tree's, with weighted counts in place of counts;
+// improvement = (w_node / w_tree) (I - w_r / w_node I_r - w_l / w_node I_l).  f64, no FMA fusion.
 //
 // One workgroup builds one tree at a time (a persistent grid strides over the trees).  In LDS (all of it in the dynamic region,
 // laid out by the host, ForestLds): the weights as bit planes (as many as the call's largest weight needs, so a weighted count
@@ -36,6 +37,7 @@
 #include "dev_utils.h"
 #include "psk_internal.h"
 #include "solver_host.h"
+#include "solver_tree_common.h"
 
 namespace {
 
@@ -44,57 +46,11 @@ namespace {
 // from a wide one.
 constexpr int FOREST_THREADS = 256;
 constexpr int FOREST_MAX_N = 4096;
-constexpr int FOREST_NODE_FIELDS = 6;      // feature, left, right, n_node_samples, w0, w1
 constexpr int FOREST_LDS_COLS = 1024;      // per-column arrays stay in LDS up to this many columns
 constexpr int FOREST_COL_BYTES = 28;       // proxy f64, features / constant_features / state / w_r / w_r1 i32
 constexpr int FOREST_GRID_PER_CU = 4;
 constexpr uint32_t FOREST_NO_LABEL = 0xffff;
 constexpr int COL_CONSTANT = -1, COL_NO_SPLIT = -2;
-
-__device__ __forceinline__ size_t forest_bit_at(int j, int w, int p) { return (size_t)w * p + j; }   // word-major, as tree_pack_kernel
-
-// bits[w][j]: bit k = X[64 w + k][j] (the layout of solver_tree.hip's pack and its reason: a wave's loads of one word of 64
-// consecutive columns are contiguous)
-__global__ __launch_bounds__(256) void forest_pack_kernel(const float *__restrict__ X, const int32_t *__restrict__ y01, int n, int p,
-                                                          uint64_t *__restrict__ bits, uint64_t *__restrict__ ymask,
-                                                          int32_t *__restrict__ bad_flag)
-{
-    const int j = blockIdx.x * blockDim.x + threadIdx.x, w = blockIdx.y;
-    const int s0 = w * 64, s1 = min(n, s0 + 64);
-    if (j < p) {
-        uint64_t b = 0;
-        bool bad = false;
-        for (int s = s0; s < s1; s++) {
-            const float x = X[(size_t)s * p + j];
-            if (x == 1.0f) b |= 1ull << (s - s0);
-            else if (!(x == 0.0f)) bad = true;
-        }
-        bits[forest_bit_at(j, w, p)] = b;
-        if (bad) atomicOr(bad_flag, 1);
-    }
-    if (j == 0) {
-        uint64_t b = 0;
-        for (int s = s0; s < s1; s++)
-            if (y01[s] != 0) b |= 1ull << (s - s0);
-        ymask[w] = b;
-    }
-}
-
-__device__ __forceinline__ double forest_log2(double x) { return log(x) / log(2.0); }   // sklearn/tree/_utils.pyx::log
-
-__device__ __forceinline__ double forest_impurity(int crit, double c0, double c1, double nn)
-{
-    if (crit == 0) {
-        double sq = 0.0;
-        sq += c0 * c0;
-        sq += c1 * c1;
-        return 1.0 - sq / (nn * nn);
-    }
-    double e = 0.0;
-    if (c0 > 0.0) { const double c = c0 / nn; e -= c * forest_log2(c); }
-    if (c1 > 0.0) { const double c = c1 / nn; e -= c * forest_log2(c); }
-    return e;
-}
 
 // a pending node: its parent, level, side, distinct / weighted / weighted class-1 in-bag samples, the constants known on the
 // way down, and the impurity its parent's split computed for it
@@ -169,7 +125,7 @@ __global__ __launch_bounds__(FOREST_THREADS) void forest_fit_kernel(const Forest
         }
         const double w_tree = (double)w_tot;
         if (tid == 0)
-            stack[0] = ForestRec{-1, 0, 0, n_tot, w_tot, w1_tot, 0, 0, forest_impurity(crit, (double)(w_tot - w1_tot), (double)w1_tot, w_tree)};
+            stack[0] = ForestRec{-1, 0, 0, n_tot, w_tot, w1_tot, 0, 0, tree_impurity(crit, (double)(w_tot - w1_tot), (double)w1_tot, w_tree)};
         int sp = 1, next_id = 0, deepest = 0;
         while (sp > 0) {
             __syncthreads();   // labels, per-column arrays and `cur` of the node before
@@ -202,7 +158,7 @@ __global__ __launch_bounds__(FOREST_THREADS) void forest_fit_kernel(const Forest
                     for (int w = 0; w < W; w++) {
                         const uint64_t m = MT[w];
                         if (!m) continue;   // (uniform: the mask words are the workgroup's)
-                        const uint64_t v = a.bits[forest_bit_at(j, w, p)];
+                        const uint64_t v = a.bits[tree_bit_at(j, w, p)];
                         c += __popcll(v & m);
                         for (int b = 0; b < B; b++) {
                             cw += __popcll(v & MP[b * W + w]) << b;
@@ -214,8 +170,8 @@ __global__ __launch_bounds__(FOREST_THREADS) void forest_fit_kernel(const Forest
                     else if (rec.n - c < msl || c < msl) st = COL_NO_SPLIT;
                     else {
                         const double dwr = (double)cw, dwl = (double)(rec.wn - cw);
-                        const double ir = forest_impurity(crit, (double)(cw - cw1), (double)cw1, dwr);
-                        const double il = forest_impurity(crit, c0n - (double)(cw - cw1), c1n - (double)cw1, dwl);
+                        const double ir = tree_impurity(crit, (double)(cw - cw1), (double)cw1, dwr);
+                        const double il = tree_impurity(crit, c0n - (double)(cw - cw1), c1n - (double)cw1, dwl);
                         proxy[j] = -dwr * ir - dwl * il;
                     }
                     col_state[j] = st;
@@ -273,8 +229,8 @@ __global__ __launch_bounds__(FOREST_THREADS) void forest_fit_kernel(const Forest
                     wr = col_wr[best];
                     wr1 = col_wr1[best];
                     const double dwr = (double)wr, dwl = (double)(rec.wn - wr);
-                    imp_r = forest_impurity(crit, (double)(wr - wr1), (double)wr1, dwr);
-                    imp_l = forest_impurity(crit, c0n - (double)(wr - wr1), c1n - (double)wr1, dwl);
+                    imp_r = tree_impurity(crit, (double)(wr - wr1), (double)wr1, dwr);
+                    imp_l = tree_impurity(crit, c0n - (double)(wr - wr1), c1n - (double)wr1, dwl);
                     const double improvement = (wn / w_tree) * (rec.imp - (dwr / wn * imp_r) - (dwl / wn * imp_l));
                     if (improvement + DBL_EPSILON < 0.0) is_leaf = true;
                     else feat = best;
@@ -282,17 +238,9 @@ __global__ __launch_bounds__(FOREST_THREADS) void forest_fit_kernel(const Forest
             }
             const int id = next_id++;
             deepest = max(deepest, rec.depth);
-            if (tid == 0 && node_off >= 0 && id < node_cap) {
-                int32_t *nd = a.nodes + (size_t)(node_off + id) * FOREST_NODE_FIELDS;
-                nd[0] = feat;
-                nd[1] = is_leaf ? -1 : id + 1;
-                nd[2] = -1;   // a split node's right child writes its own number here when it is made
-                nd[3] = rec.n;
-                nd[4] = rec.wn - rec.w1;
-                nd[5] = rec.w1;
-                a.imp_out[node_off + id] = rec.imp;
-                if (rec.parent >= 0 && !rec.is_left) a.nodes[(size_t)(node_off + rec.parent) * FOREST_NODE_FIELDS + 2] = id;
-            }
+            if (tid == 0 && node_off >= 0 && id < node_cap)
+                tree_write_node(a.nodes + (size_t)node_off * TREE_NODE_FIELDS, a.imp_out + node_off, id, rec.parent, rec.is_left, feat, is_leaf,
+                                rec.n, rec.wn - rec.w1, rec.w1, rec.imp);
             if (is_leaf) {
                 const double f0 = c0n / wn, f1 = c1n / wn;
                 for (int s = tid; s < n; s += FOREST_THREADS)
@@ -305,7 +253,7 @@ __global__ __launch_bounds__(FOREST_THREADS) void forest_fit_kernel(const Forest
             } else {
                 // the right child takes this node's slot, the left one the slot above it: popped first
                 for (int s = tid; s < n; s += FOREST_THREADS)
-                    if (label[s] == slot && !((a.bits[forest_bit_at(feat, s >> 6, p)] >> (s & 63)) & 1ull)) label[s] = (uint16_t)(slot + 1);
+                    if (label[s] == slot && !((a.bits[tree_bit_at(feat, s >> 6, p)] >> (s & 63)) & 1ull)) label[s] = (uint16_t)(slot + 1);
                 if (tid == 0) {
                     stack[sp] = ForestRec{id, rec.depth + 1, 0, nr, wr, wr1, n_const, 0, imp_r};
                     stack[sp + 1] = ForestRec{id, rec.depth + 1, 1, rec.n - nr, rec.wn - wr, rec.w1 - wr1, n_const, 0, imp_l};
@@ -426,22 +374,8 @@ extern "C" int psk_forest_fit(psk_ctx *ctx, const float *X, const int32_t *y01, 
 
     PSK_HIP(ctx, hipSetDevice(ctx->device));
     const int W = (n + 63) / 64;
-    FitArr<float> x;
     FitArr<uint64_t> bits, ymask;
-    FitArr<int32_t> bad_flag, y;
-    PSK_HIP(ctx, x.upload(X, (size_t)n * p, ctx->stream));
-    PSK_HIP(ctx, y.upload(y01, n, ctx->stream));
-    PSK_HIP(ctx, bits.alloc((size_t)p * W));
-    PSK_HIP(ctx, ymask.alloc(W));
-    PSK_HIP(ctx, bad_flag.alloc(1));
-    PSK_HIP(ctx, bad_flag.zero(ctx->stream));
-    forest_pack_kernel<<<dim3(div_up(p, 256), W), 256, 0, ctx->stream>>>(x, y, n, p, bits, ymask, bad_flag);
-    PSK_HIP(ctx, hipGetLastError());
-    int32_t bad = 0;
-    PSK_HIP(ctx, bad_flag.download(&bad, 1, ctx->stream));
-    PSK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (bad)
-        return psk_fail(ctx, PSK_EINVAL, "psk_forest_fit takes a 0/1 design (k-mer presence): the matrix holds another value");
+    if (const int rc = tree_pack_design(ctx, "psk_forest_fit", X, y01, n, p, bits, ymask)) return rc;
 
     const int grid = std::min(n_trees, FOREST_GRID_PER_CU * (ctx->n_cu > 0 ? ctx->n_cu : 256));
     ForestArgs a{};
@@ -450,7 +384,7 @@ extern "C" int psk_forest_fit(psk_ctx *ctx, const float *X, const int32_t *y01, 
     FitArr<uint16_t> d_weight;
     FitArr<uint32_t> d_state;
     FitArr<int32_t> d_tree_fit, d_crit, d_depth, d_mf, d_msl, d_mss, d_cap, d_leaf_row, d_count, d_deepest, d_nodes, d_leaf, d_fit_ptr,
-        d_fit_trees;
+        d_fit_tree_ids;
     FitArr<int64_t> d_off;
     FitArr<double> d_imp, frac0, frac1, sum0, sum1;
     FitArr<ForestRec> d_stack;
@@ -467,10 +401,10 @@ extern "C" int psk_forest_fit(psk_ctx *ctx, const float *X, const int32_t *y01, 
     PSK_HIP(ctx, d_cap.upload(node_cap, ctx->stream));
     PSK_HIP(ctx, d_leaf_row.upload(leaf_row, ctx->stream));
     PSK_HIP(ctx, d_fit_ptr.upload(fit_ptr, ctx->stream));
-    PSK_HIP(ctx, d_fit_trees.upload(fit_trees, ctx->stream));
+    PSK_HIP(ctx, d_fit_tree_ids.upload(fit_trees, ctx->stream));
     PSK_HIP(ctx, d_count.alloc(n_trees));
     PSK_HIP(ctx, d_deepest.alloc(n_trees));
-    PSK_HIP(ctx, d_nodes.alloc((size_t)pool * FOREST_NODE_FIELDS));
+    PSK_HIP(ctx, d_nodes.alloc((size_t)pool * TREE_NODE_FIELDS));
     PSK_HIP(ctx, d_imp.alloc((size_t)pool));
     PSK_HIP(ctx, d_leaf.alloc((size_t)n_export * n));
     PSK_HIP(ctx, frac0.alloc((size_t)n_trees * n));
@@ -489,14 +423,14 @@ extern "C" int psk_forest_fit(psk_ctx *ctx, const float *X, const int32_t *y01, 
     a.stack = d_stack; a.cols_global = d_cols;
     forest_fit_kernel<<<grid, FOREST_THREADS, a.lds.total, ctx->stream>>>(a);
     PSK_HIP(ctx, hipGetLastError());
-    forest_sum_kernel<<<dim3(div_up(n, 256), n_fits), 256, 0, ctx->stream>>>(frac0, frac1, n, d_fit_ptr, d_fit_trees, sum0, sum1);
+    forest_sum_kernel<<<dim3(div_up(n, 256), n_fits), 256, 0, ctx->stream>>>(frac0, frac1, n, d_fit_ptr, d_fit_tree_ids, sum0, sum1);
     PSK_HIP(ctx, hipGetLastError());
     PSK_HIP(ctx, sum0.download(sum0_out, (size_t)n_fits * n, ctx->stream));
     PSK_HIP(ctx, sum1.download(sum1_out, (size_t)n_fits * n, ctx->stream));
     PSK_HIP(ctx, d_count.download(node_count_out, n_trees, ctx->stream));
     PSK_HIP(ctx, d_deepest.download(max_depth_out, n_trees, ctx->stream));
     if (n_export) {
-        PSK_HIP(ctx, d_nodes.download(nodes_out, (size_t)pool * FOREST_NODE_FIELDS, ctx->stream));
+        PSK_HIP(ctx, d_nodes.download(nodes_out, (size_t)pool * TREE_NODE_FIELDS, ctx->stream));
         PSK_HIP(ctx, d_imp.download(impurity_out, (size_t)pool, ctx->stream));
         PSK_HIP(ctx, d_leaf.download(leaf_out, (size_t)n_export * n, ctx->stream));
     }

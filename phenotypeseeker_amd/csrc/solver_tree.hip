@@ -14,8 +14,9 @@
 //     COLUMN INDEX WINS among bit-equal maxima.  The reduction runs over (value, index) pairs, a total
 //     order, so the order in which lanes and waves are combined cannot matter
 //   * a child's impurity is the children_impurity value its parent's split computed; the root's is node_impurity
-// Two kernels: tree_pack_kernel turns the float design into bit words (W x p u64, W = ceil(n / 64), word-major) plus the
-// label mask and flags any value other than 0 or 1; tree_fit_kernel runs one workgroup per fit with the routing masks of
+// Two kernels: tree_pack_kernel (solver_tree_common.h, with the impurity expressions and the node record) turns the float
+// design into bit words (W x p u64, W = ceil(n / 64), word-major) plus the label mask and flags any value other than 0 or 1;
+// tree_fit_kernel runs one workgroup per fit with the routing masks of
 // the current root-to-node path in LDS (11 levels x 64 words = 5.6 KB at 4096 samples) and the pending right children on a
 // 12-entry stack.  The routing masks carry every sample, held-out ones included, so each sample's leaf is known when the
 // leaf is made; counts are taken under the fit's training mask.
@@ -29,6 +30,7 @@
 #include "dev_utils.h"
 #include "psk_internal.h"
 #include "solver_host.h"
+#include "solver_tree_common.h"
 
 namespace {
 
@@ -39,57 +41,6 @@ constexpr int TREE_WAVES = TREE_THREADS / 64;
 constexpr int TREE_MAX_N = 4096;
 constexpr int TREE_MAX_W = TREE_MAX_N / 64;
 constexpr int TREE_MAX_DEPTH = 10;
-constexpr int TREE_NODE_FIELDS = 6;   // feature, left, right, n_node_samples, n0, n1
-// Word w of column j.  Word-major (W x p): the threads of a wave hold consecutive columns, so a wave's 64 loads of one word
-// are 512 contiguous bytes.  Column-major (p x W) put them W x 8 B apart, a cache line per lane: the 220-fit grid at
-// 2,048 x 1,000 took 3.89 ms in that layout and 2.85 ms in this one (profiles/tree_grid_*; 0.36 ms either way at n = 256).
-__device__ __forceinline__ size_t tree_bit_at(int j, int w, int p, int W) { return (size_t)w * p + j; }
-
-// ---- pack --------------------------------------------------------------------------------------------------------------
-// bits[w][j]: bit k = X[64 w + k][j]; threads of a workgroup take consecutive columns, so the reads of a sample's row and the
-// writes of a word coalesce.
-__global__ __launch_bounds__(256) void tree_pack_kernel(const float *__restrict__ X, const int32_t *__restrict__ y01, int n, int p,
-                                                        int W, uint64_t *__restrict__ bits, uint64_t *__restrict__ ymask,
-                                                        int32_t *__restrict__ bad_flag)
-{
-    const int j = blockIdx.x * blockDim.x + threadIdx.x, w = blockIdx.y;
-    const int s0 = w * 64, s1 = min(n, s0 + 64);
-    if (j < p) {
-        uint64_t b = 0;
-        bool bad = false;
-        for (int s = s0; s < s1; s++) {
-            const float x = X[(size_t)s * p + j];
-            if (x == 1.0f) b |= 1ull << (s - s0);
-            else if (!(x == 0.0f)) bad = true;
-        }
-        bits[tree_bit_at(j, w, p, W)] = b;
-        if (bad) atomicOr(bad_flag, 1);
-    }
-    if (j == 0) {
-        uint64_t b = 0;
-        for (int s = s0; s < s1; s++)
-            if (y01[s] != 0) b |= 1ull << (s - s0);
-        ymask[w] = b;
-    }
-}
-
-// ---- fit ---------------------------------------------------------------------------------------------------------------
-// scikit-learn's entropy is in bits: sklearn/tree/_utils.pyx defines log(x) as ln(x) / ln(2.0)
-__device__ __forceinline__ double tree_log2(double x) { return log(x) / log(2.0); }
-
-template <int CRIT> __device__ __forceinline__ double tree_impurity(double c0, double c1, double nn)
-{
-    if (CRIT == 0) {
-        double sq = 0.0;
-        sq += c0 * c0;
-        sq += c1 * c1;
-        return 1.0 - sq / (nn * nn);
-    }
-    double e = 0.0;
-    if (c0 > 0.0) { const double c = c0 / nn; e -= c * tree_log2(c); }
-    if (c1 > 0.0) { const double c = c1 / nn; e -= c * tree_log2(c); }
-    return e;
-}
 
 // (value, column) maximum, the LOWEST column winning among equal values
 __device__ __forceinline__ bool tree_better(double v, int i, double bv, int bi) { return v > bv || (v == bv && i < bi); }
@@ -116,7 +67,7 @@ __device__ void tree_build(const uint64_t *__restrict__ bits, int n, int p, int 
         if (tid < W) {
             uint64_t m = mask[0][tid];
             if (d > 0) {
-                const uint64_t col = bits[tree_bit_at(path_feat[d - 1], tid, p, W)];
+                const uint64_t col = bits[tree_bit_at(path_feat[d - 1], tid, p)];
                 m = mask[d - 1][tid] & (rec.is_left ? ~col : col);
                 mask[d][tid] = m;
             }
@@ -136,7 +87,7 @@ __device__ void tree_build(const uint64_t *__restrict__ bits, int n, int p, int 
                 for (int w = 0; w < W; w++) {
                     const uint64_t m = MT[w];
                     if (!m) continue;   // (uniform: the mask words are the workgroup's)
-                    const uint64_t v = bits[tree_bit_at(j, w, p, W)];
+                    const uint64_t v = bits[tree_bit_at(j, w, p)];
                     c += __popcll(v & m);
                     c1 += __popcll(v & MTY[w]);
                 }
@@ -173,17 +124,7 @@ __device__ void tree_build(const uint64_t *__restrict__ bits, int n, int p, int 
         }
         const int id = next_id++;
         deepest = max(deepest, d);
-        if (tid == 0) {
-            int32_t *nd = nodes + (size_t)id * TREE_NODE_FIELDS;
-            nd[0] = feat;
-            nd[1] = is_leaf ? -1 : id + 1;
-            nd[2] = -1;   // a split node's right child writes its own number here when it is made
-            nd[3] = rec.n;
-            nd[4] = rec.n - rec.n1;
-            nd[5] = rec.n1;
-            imp_out[id] = rec.imp;
-            if (rec.parent >= 0 && !rec.is_left) nodes[(size_t)rec.parent * TREE_NODE_FIELDS + 2] = id;
-        }
+        if (tid == 0) tree_write_node(nodes, imp_out, id, rec.parent, rec.is_left, feat, is_leaf, rec.n, rec.n - rec.n1, rec.n1, rec.imp);
         if (is_leaf) {
             const double f1 = c1n / nn;
             for (int s = tid; s < n; s += TREE_THREADS)
@@ -265,23 +206,10 @@ extern "C" int psk_tree_fit(psk_ctx *ctx, const float *X, const int32_t *y01, in
 
     PSK_HIP(ctx, hipSetDevice(ctx->device));
     const int W = (n + 63) / 64;
-    FitArr<float> x;
     FitArr<uint64_t> bits, ymask;
-    FitArr<int32_t> bad_flag, y, d_fold, depth, crit, d_fit_fold, d_off, count, dout, d_nodes, leaf;
+    FitArr<int32_t> d_fold, depth, crit, d_fit_fold, d_off, count, dout, d_nodes, leaf;
     FitArr<double> d_imp, frac;
-    PSK_HIP(ctx, x.upload(X, (size_t)n * p, ctx->stream));
-    PSK_HIP(ctx, y.upload(y01, n, ctx->stream));
-    PSK_HIP(ctx, bits.alloc((size_t)p * W));
-    PSK_HIP(ctx, ymask.alloc(W));
-    PSK_HIP(ctx, bad_flag.alloc(1));
-    PSK_HIP(ctx, bad_flag.zero(ctx->stream));
-    tree_pack_kernel<<<dim3(div_up(p, 256), W), 256, 0, ctx->stream>>>(x, y, n, p, W, bits, ymask, bad_flag);
-    PSK_HIP(ctx, hipGetLastError());
-    int32_t bad = 0;
-    PSK_HIP(ctx, bad_flag.download(&bad, 1, ctx->stream));
-    PSK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (bad)
-        return psk_fail(ctx, PSK_EINVAL, "psk_tree_fit takes a 0/1 design (k-mer presence): the matrix holds another value");
+    if (const int rc = tree_pack_design(ctx, "psk_tree_fit", X, y01, n, p, bits, ymask)) return rc;
 
     // a tree of max_depth d has at most 2^(d+1) - 1 nodes: fit f's nodes start at off[f] of one packed buffer (a depth-1 fit
     // takes 3 slots, not PSK_TREE_NODE_CAP), and only the node_count[f] nodes it made go back into the caller's strided arrays

@@ -401,69 +401,45 @@ class PskContext:
         return ms.value, nb.value, ("grid-stride, non-temporal", "grid-stride", "wave-contiguous, non-temporal", "wave-contiguous")[shape.value]
 
     # -- models -----------------------------------------------------------------------------------
-    def _fit(self, fn, name, X, y, ydtype, fold, fit_param, fit_fold, tol, max_iter):
+    @staticmethod
+    def _fit_arrays(X, y, ydtype, fold, fit_param, fit_fold):
+        """(X, n, p, y, fold, fit_param, fit_fold, n_fits) as the fit entry points take them: contiguous, in the ABI's types."""
         X = np.ascontiguousarray(X, dtype=np.float32)
-        n, p = X.shape
-        y = np.ascontiguousarray(y, dtype=ydtype)
-        fold = np.ascontiguousarray(fold, dtype=np.int32)
         fit_param = np.ascontiguousarray(fit_param, dtype=np.float64)
-        fit_fold = np.ascontiguousarray(fit_fold, dtype=np.int32)
-        nf = len(fit_param)
-        coef = np.zeros((nf, p))
-        icpt = np.zeros(nf)
-        iters = np.zeros(nf, dtype=np.int32)
-        self._check(fn(self._h, _ptr(X), _ptr(y), n, p, _ptr(fold), _ptr(fit_param), _ptr(fit_fold), nf, float(tol),
-                       int(max_iter), _ptr(coef), _ptr(icpt), _ptr(iters)), name)
+        return (X, X.shape[0], X.shape[1], np.ascontiguousarray(y, dtype=ydtype), np.ascontiguousarray(fold, dtype=np.int32), fit_param,
+                np.ascontiguousarray(fit_fold, dtype=np.int32), len(fit_param))
+
+    def _fit(self, fn, name, X, y, ydtype, fold, fit_param, fit_fold, *extra):
+        """A linear-model entry point: (coef[n_fits][p], intercept[n_fits], iterations[n_fits]); `extra`: the arguments
+        it takes between n_fits and the outputs."""
+        X, n, p, y, fold, fit_param, fit_fold, nf = self._fit_arrays(X, y, ydtype, fold, fit_param, fit_fold)
+        coef, icpt, iters = np.zeros((nf, p)), np.zeros(nf), np.zeros(nf, dtype=np.int32)
+        self._check(fn(self._h, _ptr(X), _ptr(y), n, p, _ptr(fold), _ptr(fit_param), _ptr(fit_fold), nf, *extra, _ptr(coef), _ptr(icpt),
+                       _ptr(iters)), name)
         return coef, icpt, iters
 
     def logreg_l1_fit(self, X, y01, fold, fit_param, fit_fold, tol=1e-4, max_iter=1000):
         return self._fit(self._lib.psk_logreg_l1_fit, "psk_logreg_l1_fit", X, y01, np.int32, fold, fit_param, fit_fold,
-                         tol, max_iter)
+                         float(tol), int(max_iter))
 
     def lasso_fit(self, X, y, fold, fit_param, fit_fold, tol=1e-4, max_iter=1000):
-        return self._fit(self._lib.psk_lasso_fit, "psk_lasso_fit", X, y, np.float64, fold, fit_param, fit_fold, tol,
-                         max_iter)
+        return self._fit(self._lib.psk_lasso_fit, "psk_lasso_fit", X, y, np.float64, fold, fit_param, fit_fold, float(tol),
+                         int(max_iter))
 
     def ridge_fit(self, X, y, fold, fit_param, fit_fold):
         """Ridge fits (psk_ridge_fit): same batching as lasso_fit, solved to convergence."""
-        X = np.ascontiguousarray(X, dtype=np.float32)
-        n, p = X.shape
-        y = np.ascontiguousarray(y, dtype=np.float64)
-        fold = np.ascontiguousarray(fold, dtype=np.int32)
-        fit_param = np.ascontiguousarray(fit_param, dtype=np.float64)
-        fit_fold = np.ascontiguousarray(fit_fold, dtype=np.int32)
-        nf = len(fit_param)
-        coef, icpt, iters = np.zeros((nf, p)), np.zeros(nf), np.zeros(nf, dtype=np.int32)
-        self._check(self._lib.psk_ridge_fit(self._h, _ptr(X), _ptr(y), n, p, _ptr(fold), _ptr(fit_param), _ptr(fit_fold),
-                                            nf, _ptr(coef), _ptr(icpt), _ptr(iters)), "psk_ridge_fit")
-        return coef, icpt, iters
+        return self._fit(self._lib.psk_ridge_fit, "psk_ridge_fit", X, y, np.float64, fold, fit_param, fit_fold)
 
     def logreg_l2_fit(self, X, y01, fold, fit_param, fit_fold, tol=1e-4, max_iter=1000, penalise_intercept=False):
-        X = np.ascontiguousarray(X, dtype=np.float32)
-        n, p = X.shape
-        y = np.ascontiguousarray(y01, dtype=np.int32)
-        fold = np.ascontiguousarray(fold, dtype=np.int32)
-        fit_param = np.ascontiguousarray(fit_param, dtype=np.float64)
-        fit_fold = np.ascontiguousarray(fit_fold, dtype=np.int32)
-        nf = len(fit_param)
-        coef, icpt, iters = np.zeros((nf, p)), np.zeros(nf), np.zeros(nf, dtype=np.int32)
-        self._check(self._lib.psk_logreg_l2_fit(self._h, _ptr(X), _ptr(y), n, p, _ptr(fold), _ptr(fit_param),
-                                                _ptr(fit_fold), nf, float(tol), int(max_iter), int(bool(penalise_intercept)),
-                                                _ptr(coef), _ptr(icpt), _ptr(iters)), "psk_logreg_l2_fit")
-        return coef, icpt, iters
+        return self._fit(self._lib.psk_logreg_l2_fit, "psk_logreg_l2_fit", X, y01, np.int32, fold, fit_param, fit_fold,
+                         float(tol), int(max_iter), int(bool(penalise_intercept)))
 
     def svc_fit(self, X, y01, fold, fit_C, fit_fold, kernel="linear", fit_gamma=None, tol=1e-3, max_iter=-1):
         """C-SVC fits (psk_svc_fit): libsvm's solver without shrinking, one workgroup per fit.  Returns
         (dual[n_fits][n], rho[n_fits], dec[n_fits][n], iters[n_fits]) in libsvm's sign: class 0 is positive."""
         if kernel not in ("linear", "rbf"):
             raise ValueError("kernel must be 'linear' or 'rbf', got %r" % (kernel,))
-        X = np.ascontiguousarray(X, dtype=np.float32)
-        n, p = X.shape
-        y = np.ascontiguousarray(y01, dtype=np.int32)
-        fold = np.ascontiguousarray(fold, dtype=np.int32)
-        fit_C = np.ascontiguousarray(fit_C, dtype=np.float64)
-        fit_fold = np.ascontiguousarray(fit_fold, dtype=np.int32)
-        nf = len(fit_C)
+        X, n, p, y, fold, fit_C, fit_fold, nf = self._fit_arrays(X, y01, np.int32, fold, fit_C, fit_fold)
         if kernel == "rbf":
             fit_gamma = np.ascontiguousarray(np.broadcast_to(np.asarray(fit_gamma, dtype=np.float64), (nf,)))
         dual, rho, dec = np.zeros((nf, n)), np.zeros(nf), np.zeros((nf, n))
@@ -475,6 +451,14 @@ class PskContext:
         return dual, rho, dec, iters
 
     TREE_NODE_CAP = 2047      # PSK_TREE_NODE_CAP of include/psk.h
+
+    @staticmethod
+    def _tree_dict(nodes, impurity, max_depth, leaf):
+        """nodes[k][6] (feature, left, right, n_node_samples, the two class counts), impurity[k] by node in pre-order,
+        the tree's depth and leaf[n], every sample's leaf, as the dictionary tree_fit and forest_fit return per tree."""
+        return dict(node_count=len(nodes), max_depth=int(max_depth), feature=nodes[:, 0].astype(np.int64), left=nodes[:, 1].astype(np.int64),
+                    right=nodes[:, 2].astype(np.int64), n_node_samples=nodes[:, 3].astype(np.int64), counts=nodes[:, 4:6].astype(np.int64),
+                    impurity=impurity.copy(), leaf=leaf.astype(np.int64))
 
     def tree_fit(self, X, y01, fold, fit_max_depth, fit_criterion, fit_fold):
         """Decision-tree fits (psk_tree_fit): scikit-learn's depth-first best-split builder on a 0/1 design, one workgroup
@@ -495,15 +479,7 @@ class PskContext:
         self._check(self._lib.psk_tree_fit(self._h, _ptr(X), _ptr(y), n, p, _ptr(fold), _ptr(depth), _ptr(crit), _ptr(fit_fold),
                                            nf, _ptr(count), _ptr(deepest), _ptr(nodes), _ptr(imp), _ptr(leaf), _ptr(frac)),
                     "psk_tree_fit")
-        out = []
-        for j in range(nf):
-            k = int(count[j])
-            nd = nodes[j, :k]
-            out.append(dict(node_count=k, max_depth=int(deepest[j]), feature=nd[:, 0].astype(np.int64), left=nd[:, 1].astype(np.int64),
-                            right=nd[:, 2].astype(np.int64), n_node_samples=nd[:, 3].astype(np.int64),
-                            counts=nd[:, 4:6].astype(np.int64), impurity=imp[j, :k].copy(), leaf=leaf[j].astype(np.int64),
-                            frac=frac[j].copy()))
-        return out
+        return [dict(self._tree_dict(nodes[j, :count[j]], imp[j, :count[j]], deepest[j], leaf[j]), frac=frac[j].copy()) for j in range(nf)]
 
     def forest_fit(self, X, y01, tree_weight, tree_state, tree_fit, fit_criterion, fit_max_depth, fit_max_features,
                    fit_min_samples_leaf, fit_min_samples_split, export=None):
@@ -548,10 +524,7 @@ class PskContext:
                 trees.append(None)
                 continue
             a, k = int(off[t]), int(count[t])
-            nd = nodes[a:a + k]
-            trees.append(dict(node_count=k, max_depth=int(deepest[t]), feature=nd[:, 0].astype(np.int64), left=nd[:, 1].astype(np.int64),
-                              right=nd[:, 2].astype(np.int64), n_node_samples=nd[:, 3].astype(np.int64),
-                              counts=nd[:, 4:6].astype(np.int64), impurity=imp[a:a + k].copy(), leaf=leaf[row].astype(np.int64)))
+            trees.append(self._tree_dict(nodes[a:a + k], imp[a:a + k], deepest[t], leaf[row]))
             row += 1
         return sum0, sum1, trees
 

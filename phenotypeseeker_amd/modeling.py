@@ -29,8 +29,8 @@ from . import formats, metrics, _stats
 from .engine import PskContext
 from . import _lib
 from ._lib import PSK_EGZIP, PskError
-from .model import (SVC, DecisionTree, GridSearch, L1LogisticRegression, L2LogisticRegression, LassoRegression, RandomForest,
-                    RandomizedSearch, RidgeRegression)
+from .model import (SVC, DecisionTree, L1LogisticRegression, L2LogisticRegression, LassoRegression, RandomForest, RandomizedSearch,
+                    RidgeRegression)
 
 RED_BANNER = "\x1b[1;1;101m%s\x1b[0m\n"
 GREEN = "\x1b[1;32m%s\x1b[0m"
@@ -738,11 +738,8 @@ class phenotypes:
     def _fit(self, ctx, X, y):
         est, pname, grid = self._new_estimator()
         self.model = est
-        if isinstance(est, RandomForest):
-            self.model_fitted = RandomizedSearch(est, pname, self.n_iter, self.n_splits_cv_inner, random_state=self.rf_seed).fit(X, y, ctx)
-            return
-        self.model_fitted = GridSearch(est, pname, grid, self.n_splits_cv_inner).fit(X, y, ctx)
-        if isinstance(est, SVC) and int(est.max_iter) != -1 and np.any(self.model_fitted.n_iter_ >= int(est.max_iter)):
+        self.model_fitted = est._new_search(pname, grid, self.n_splits_cv_inner, self.n_iter).fit(X, y, ctx)
+        if est._warns_at_max_iter and int(est.max_iter) != -1 and np.any(self.model_fitted.n_iter_ >= int(est.max_iter)):
             # scikit-learn's ConvergenceWarning (svm/_base.py, _warn_from_fit_status), once per grid search
             _err("ConvergenceWarning: Solver terminated early (max_iter=%i).  Consider pre-processing your data with "
                  "StandardScaler or MinMaxScaler.\n" % int(est.max_iter))
@@ -916,10 +913,8 @@ class phenotypes:
         with open(path, "w") as out:
             out.write("K-mer\tcoef._in_" + self.model_name_short + "_model\tNo._of_samples_with_k-mer\tSamples_with_k-mer\n")
         be = self.model_fitted.best_estimator_
-        if isinstance(be, (DecisionTree, RandomForest)):
-            coefs = be.feature_importances_      # (:1430-1432: the importances stand in the coefficient column)
-        else:
-            coefs = be.coef_[0] if self.pred_scale == "binary" else be.coef_
+        # what the estimator declares; a scikit-learn linear model handed over in the fit's place: its coef_ as one row
+        coefs = be._coef_column if hasattr(be, "_coef_column") else np.ravel(be.coef_)
         X, index, kmers = self.ML["X"], self.ML["index"], self.ML["kmers"]
         # the lines are formatted by libpsk (psk_write_model_coefficients: a 2,048-sample model names a million samples --
         # 0.07 s of joins here); it appends to the file whose header this function has just written

@@ -139,6 +139,16 @@ def test_edges(ctx):
     assert e.value.code == -4
     with pytest.raises(PskError):                        # depth 11 would not fit the 2,047-node capacity
         ctx.tree_fit(X, y, np.zeros(8, dtype=int), [11], ["gini"], [-1])
+    # 65 samples: a second bit word with one live bit, sample 64 trained on in one fit and held out in the other
+    rng = np.random.default_rng(3)
+    Xs = (rng.random((65, 3)) < 0.5).astype(np.float64)
+    ys = ((Xs[:, 0] + Xs[:, 2] + rng.normal(0, 0.5, 65)) > 1).astype(int)
+    fs = np.arange(65) % 3
+    got = ctx.tree_fit(Xs, ys, fs, [3, 3], ["gini", "entropy"], [-1, 1])
+    for k, (cr, ff) in enumerate((("gini", -1), ("entropy", 1))):
+        want = R.fit(Xs, ys, fs != ff, 3, cr)
+        assert_same_tree(got[k], want, ("65", cr))
+        assert np.array_equal(got[k]["leaf"], want["leaf"]) and np.array_equal(got[k]["frac"], want["frac"])
     # 4096 samples, the largest mask: against the restatement
     rng = np.random.default_rng(11)
     Xb = (rng.random((4096, 70)) < 0.4).astype(np.float64)

@@ -43,7 +43,7 @@ out[sklearn.__version__] = {
     "Ridge": shell(Ridge()),
     "SVC": shell(SVC()),
     "DecisionTreeClassifier": shell(DecisionTreeClassifier()),
-    # (estimator: a DecisionTreeClassifier shell, estimator_params: a tuple of names -- both filled in by model.py)
+    # (estimator: a DecisionTreeClassifier shell, estimator_params: a tuple of names -- both filled in by model_trees.py)
     "RandomForestClassifier": shell(RandomForestClassifier(), drop=("estimator", "estimator_params")),
     "RandomizedSearchCV": shell(RandomizedSearchCV(LogisticRegression(), {"C": [1.0]}), drop=("estimator", "param_distributions")),
     "GridSearchCV": shell(GridSearchCV(LogisticRegression(), {"C": [1.0]}), drop=("estimator", "param_grid")),
