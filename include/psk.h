@@ -193,7 +193,15 @@ int psk_chi2_scan(psk_ctx *ctx, const int8_t *pheno, const double *weights, int 
  * are read (the pipeline over phenotypes: end(j), begin(j+1), read j); issued while a scan is in flight it takes
  * the set of the last scan ended (after any asynchronous export of it, on the device), and the result calls fail
  * with PSK_ESTATE until the next psk_scan_end.  A third _begin, and the one-call scans while a scan is in flight,
- * fail with PSK_ESTATE. */
+ * fail with PSK_ESTATE.
+ * What "ended" means.  The scan's survivor count is final and every call of this library that reads its results --
+ * psk_get_results, psk_export_survivors, psk_export_survivors_async on any stream, the next scans -- sees all of
+ * them: each is ordered behind the scan on the device.  It does NOT mean that the scan's dispatch has retired: an
+ * unweighted scan is ended by the words its kernel writes to pinned memory (PSK_SCAN_WAIT, docs/KNOBS.md), which
+ * arrive as its last workgroups finish.  A caller that reads the context's device buffers by means of its own, on a
+ * stream of its own, synchronises with the context first (any blocking call of this library does).  Once
+ * psk_export_survivors_async has been called on a context its scans are ended by events again (the dispatch has
+ * completed when psk_scan_end returns), so the export never waits for a later scan already queued. */
 int psk_chi2_scan_begin(psk_ctx *ctx, const int8_t *pheno, const double *weights, int min_samples, int max_samples,
                         double pvalue_cutoff, int omit_B, uint64_t n_kmers_global);
 int psk_scan_end(psk_ctx *ctx, uint64_t *n_pass);
@@ -218,7 +226,8 @@ int psk_get_results(psk_ctx *ctx, uint64_t *row_idx, uint64_t *words, double *st
 int psk_export_survivors(psk_ctx *ctx, void *device_dst, uint64_t cap_records, uint64_t *n_records);
 /* The same export queued on the CALLER's stream (a hipStream_t, e.g. torch's current stream) and not waited for:
  * work queued on that stream afterwards -- the RCCL all-gather -- is ordered behind it without a host
- * synchronisation; the next scan that writes the same result set waits on the device for the export to finish. */
+ * synchronisation; the next scan that writes the same result set waits on the device for the export to finish.
+ * The export itself is ordered behind the scan it reads, on the device, whichever way that scan was ended. */
 int psk_export_survivors_async(psk_ctx *ctx, void *device_dst, uint64_t cap_records, void *stream);
 /* Whether the current matrix has an exception-coded copy for the unweighted chi2 scan (*encoded = 1; 65..256 samples,
  * rows mostly within 7 samples of all-absent or all-present), and how many of its rows sit in the side matrix of dense
@@ -262,7 +271,8 @@ int psk_last_scan_filter(const psk_ctx *ctx, int *filtered, uint64_t *rows_feasi
  * (else the other two are 0), *class_mask as psk_cx_plan gives it, *slots_skipped = 1 when the launch read only the side
  * matrix of overflow rows.  Measurement and tests only.  Any pointer may be NULL. */
 int psk_last_scan_plan(const psk_ctx *ctx, int *encoded, uint32_t *class_mask, int *slots_skipped);
-/* HIP-event duration of the last scan kernel launch in milliseconds (for bench.py). */
+/* Duration of the last scan in milliseconds (for bench.py): from the clock words its kernel stamped (an unweighted chi2
+ * scan ended by psk_scan_end; PSK_SCAN_WAIT=0: its event pair), else the HIP-event duration of its kernel launches. */
 double psk_last_scan_ms(const psk_ctx *ctx);
 /* Re-launches the last chi2 scan `reps` times back to back on the context's stream and
  * returns the mean kernel duration in ms measured with HIP events on that stream. */

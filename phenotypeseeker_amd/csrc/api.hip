@@ -304,7 +304,7 @@ extern "C" void psk_free(psk_ctx *ctx)
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     for (ScanSlot &sl : ctx->slot)
-        for (hipEvent_t e : {sl.ev0, sl.ev1, sl.ev_export}) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : {sl.ev0, sl.ev1, sl.ev_export, sl.ev_ended}) if (e) (void)hipEventDestroy(e);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     lap("events, main stream released");
     delete ctx;

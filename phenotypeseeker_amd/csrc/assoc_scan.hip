@@ -88,6 +88,7 @@ __global__ __launch_bounds__(LUT ? SC_LUT_THREADS : SC_THREADS) void chi2_scan_k
     constexpr bool WEIGHTED = MODE == 1, QUEUED = MODE != 0;
     constexpr bool HALF = G == 0;          // 8-byte rows, two per load
     constexpr int THREADS = sc_threads<G, LUT>(), UNR = sc_unroll<G, LUT>();
+    if (!WEIGHTED) stamp_scan_start(P.sink);   // (the weighted scan is two kernels, timed by events)
     __shared__ uint64_t s_qrow[QUEUED ? THREADS / 64 : 1][QUEUED ? rq_cap(G, UNR) : 1];
     __shared__ int2 s_qval[QUEUED ? THREADS / 64 : 1][QUEUED ? rq_cap(G, UNR) : 1];
     extern __shared__ __attribute__((aligned(16))) double s_lut[];   // LUT: the nibble table of row_moments_lut / the six-bit f32 table
@@ -261,6 +262,7 @@ __global__ __launch_bounds__(SC_THREADS) void chi2_scan_kernel_cx(const CxScanAr
     static_assert(SC_THREADS == CX_MAX_SAMPLES, "the class table is filled one sample per thread");
     const ScanArgs &P = X.s;
     __shared__ uint16_t s_cls[CX_MAX_SAMPLES];
+    stamp_scan_start(P.sink);
     const int lane = threadIdx.x & 63;
     if (blockIdx.x < X.slot_blocks) {
         {
@@ -325,6 +327,7 @@ __global__ __launch_bounds__(SC_THREADS) void chi2_scan_kernel_cx(const CxScanAr
 template <int CPR>
 __global__ __launch_bounds__(SC_THREADS) void chi2_scan_kernel_cx_side(const CxSideArgs X)
 {
+    stamp_scan_start(X.sink);
     const SideRows<CPR, CX_SIDE_UNROLL, PSK_CX_SIDE_NT != 0> R(X.ov, X.ov_row, X.n_ov, X.m1, X.m0);
     const uint64_t stride = (uint64_t)gridDim.x * CX_WAVES * CX_SIDE_UNROLL;
     const uint64_t n_steps = R.n_steps();
@@ -427,6 +430,7 @@ struct PcRows {
 template <int CPR>
 __global__ __launch_bounds__(SC_THREADS) void chi2_scan_kernel_cx_side_pc(const CxSidePcArgs X)
 {
+    stamp_scan_start(X.s.sink);
     const PcRows<CPR> R(X);
     const uint64_t stride = (uint64_t)gridDim.x * CX_WAVES;
     const uint64_t n_batches = R.n_batches();
@@ -514,7 +518,7 @@ __global__ __launch_bounds__(SC_FIN_THREADS) void chi2w_finalize_kernel(const Sc
     if (threadIdx.x == 0) {
         P.sink.counter[seg * SC_CNT_STRIDE] = 0;  // re-armed for the next scan
         P.sink.final_counts[seg] = s_out;
-        P.sink.host_counts[seg] = s_out;
+        stamp_count(P.sink, seg, s_out);
     }
 }
 

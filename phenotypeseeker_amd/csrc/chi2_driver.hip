@@ -4,6 +4,7 @@
 #include "chi2_launch.h"
 
 #include <cmath>
+#include <sched.h>
 
 namespace {
 
@@ -143,6 +144,12 @@ int chi2_scan_launch(psk_ctx *ctx, const int8_t *pheno, const double *weights, i
     if (!ctx->have_presence) return psk_fail(ctx, PSK_ESTATE, "no presence matrix (psk_build_presence first)");
     if (!pheno) return psk_fail(ctx, PSK_EINVAL, "null phenotype vector");
     if (n_kmers_global == 0) n_kmers_global = ctx->n_kmers ? ctx->n_kmers : 1;
+    // How psk_scan_end learns that the scan is done (read per scan: A/B runs and tests in one build).  1: from the stamps
+    // its kernel writes to pinned memory -- the dispatch carries no events; 0: from an event pair on the dispatch.  The
+    // weighted scan is two kernels and keeps its events either way, and so do the scans of a context whose survivors are
+    // exported on another stream (psk_export_survivors_async: that export needs the scan COMPLETE, not merely published).
+    int wait_by_stamps = 1;
+    PSK_TRY(env_choice(ctx, "PSK_SCAN_WAIT", {0, 1}, &wait_by_stamps));
     PSK_HIP(ctx, hipSetDevice(ctx->device));
     const int N = ctx->n_samples, wpr = mask_words(ctx);   // masks and tables: whole 16-byte chunks, also for 8-byte rows
     // one pinned staging block [m1 | m0 | w1 | w0] and ONE stream-ordered upload (weights only when given)
@@ -193,10 +200,11 @@ int chi2_scan_launch(psk_ctx *ctx, const int8_t *pheno, const double *weights, i
     ctx->last_scan_kind = 1;
     if (ctx->n_kmers) {
         ScanSlot &sl = ctx->slot[set];
-        launch_chi2_any(ctx, CL, {sl.ev0, sl.ev1});   // the events ride on the dispatch: one command per scan
+        const bool stamped = wait_by_stamps == 1 && !weights && !ctx->exports_async;
+        launch_chi2_any(ctx, CL, stamped ? TimedBy{} : TimedBy{sl.ev0, sl.ev1});   // (the events ride on the dispatch: one command per scan)
         PSK_HIP(ctx, hipGetLastError());
+        sl.stamped = stamped;
         sl.in_flight = true;
-        sl.seq = ++ctx->scan_seq;
         ctx->n_in_flight++;
     } else {  // nothing to scan: an empty result, at once
         ctx->n_pass = 0;
@@ -227,6 +235,48 @@ int rescan(psk_ctx *ctx, int reps, double *mean_ms, double *ms_each)
     return PSK_OK;
 }
 
+// Waits for the stamps of the scan in flight on result set `set` (launched without events) and takes its time from
+// their clocks.  The host spins on pinned memory -- the words arrive while the kernel's last workgroups end --, asks the
+// stream now and then whether the scan has failed or ended without a word, and gives up after WAIT_LIMIT: it never
+// loops without a bound.
+int wait_stamps(psk_ctx *ctx, int set)
+{
+    using clk = std::chrono::steady_clock;
+    constexpr auto QUERY_EVERY = std::chrono::microseconds(20), YIELD_AFTER = std::chrono::microseconds(50);
+    constexpr auto WAIT_LIMIT = std::chrono::seconds(30);
+    const volatile uint64_t *counts = scan_stamp_words(ctx, set), *clocks = counts + STAMP_NSEG;
+    const uint32_t seq = (uint32_t)ctx->slot[set].seq;
+    int nc = 0, nk = 0;   // words seen so far: a stamp that has arrived stays
+    auto all_here = [&] {
+        nc = stamp_counts_missing(counts, seq, nc);
+        if (nc == STAMP_NSEG) nk = stamp_clocks_missing(clocks, seq, nk);
+        return nc == STAMP_NSEG && nk == STAMP_CLOCKS;
+    };
+    if (!all_here()) {
+        const clk::time_point t0 = clk::now();
+        clk::time_point next_query = t0 + QUERY_EVERY;
+        for (;;) {
+            __builtin_ia32_pause();
+            if (all_here()) break;
+            const clk::time_point now = clk::now();
+            if (now >= next_query) {
+                const hipError_t e = hipStreamQuery(ctx->stream);
+                if (e == hipSuccess) {   // everything queued has ended: the words are there now, or never will be
+                    if (all_here()) break;
+                    return psk_fail(ctx, PSK_ESTATE, "scan ended without publishing (segment %d of scan %u)", nc < STAMP_NSEG ? nc : nk, seq);
+                }
+                if (e != hipErrorNotReady) return psk_fail(ctx, PSK_EHIP, "hipStreamQuery failed while scan %u was awaited: %s", seq, hipGetErrorString(e));
+                (void)hipGetLastError();   // "not ready" is an answer, not an error for the next launch's check to find
+                if (now - t0 > WAIT_LIMIT) return psk_fail(ctx, PSK_ESTATE, "scan %u has not published its counts after 30 s", seq);
+                next_query = clk::now() + QUERY_EVERY;
+            }
+            if (now - t0 > YIELD_AFTER) sched_yield();
+        }
+    }
+    ctx->last_scan_ms = (double)stamp_scan_ticks(clocks) / ctx->wall_clock_khz;
+    return PSK_OK;
+}
+
 }  // namespace
 
 extern "C" int psk_chi2_scan_begin(psk_ctx *ctx, const int8_t *pheno, const double *weights, int min_samples,
@@ -243,12 +293,19 @@ extern "C" int psk_scan_end(psk_ctx *ctx, uint64_t *n_pass)
         int set = ctx->slot[0].in_flight ? 0 : 1;
         if (ctx->slot[0].in_flight && ctx->slot[1].in_flight && ctx->slot[1].seq < ctx->slot[0].seq) set = 1;
         ScanSlot &sl = ctx->slot[set];
-        PSK_HIP(ctx, hipEventSynchronize(sl.ev1));  // its kernels have written the counts to pinned memory
-        sl.in_flight = false;
-        ctx->n_in_flight--;
-        float ms = 0;
-        PSK_HIP(ctx, hipEventElapsedTime(&ms, sl.ev0, sl.ev1));
-        ctx->last_scan_ms = ms;
+        if (sl.stamped) {
+            const int rc = wait_stamps(ctx, set);   // the kernel's own words: no event on the dispatch, no runtime call when the GPU is ahead
+            sl.in_flight = false;
+            ctx->n_in_flight--;
+            PSK_TRY(rc);
+        } else {
+            PSK_HIP(ctx, hipEventSynchronize(sl.ev1));  // its kernels have written the counts to pinned memory
+            sl.in_flight = false;
+            ctx->n_in_flight--;
+            float ms = 0;
+            PSK_HIP(ctx, hipEventElapsedTime(&ms, sl.ev0, sl.ev1));
+            ctx->last_scan_ms = ms;
+        }
         PSK_TRY(fetch_counts(ctx, set));
         ctx->dense_hint = ctx->n_pass * 1000 > ctx->n_kmers ? 1 : 0;  // only chi2 scans come through here
     }

@@ -109,8 +109,10 @@ struct ScanSink {
     // end of a scan: the last workgroup of a segment (chi2) / the segment's finalize workgroup (Welch) publishes
     // the segment's count to final_counts (device, compact) and host_counts (pinned host memory, written
     // straight from the kernel) and zeroes the counter for the next scan -- no memset, no read-back copy
-    uint32_t *final_counts, *host_counts;
+    uint32_t *final_counts;
+    uint64_t *host_counts;   // one stamped word per segment, the set's clock words behind them (scan_stamps.h)
     uint32_t seg_cap;    // entries per segment
+    uint32_t seq;        // low 32 bits of the launch number of the scan that writes the set: the tag of its stamps
 };
 
 // One of the two result sets of the scans.
@@ -118,11 +120,14 @@ struct ScanSlot {
     DevBuf res;                      // SoA result arrays (setup_results)
     ScanSink sink = {};              // ... as a kernel addresses them: laid out when `res` is reserved or seg_cap changes
     bool sink_valid = false;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;   // around the scan's kernels
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;   // around the scan's kernels (scans that are waited for by event)
+    bool stamped = false;            // the set's last scan carried no events: psk_scan_end waits (waited) for its stamps, and its
+                                     // dispatch may still be retiring when that returns -- see psk_export_survivors_async
+    hipEvent_t ev_ended = nullptr;   // recorded on ctx->stream when another stream has to be ordered behind a stamped scan
     hipEvent_t ev_export = nullptr;  // recorded on the caller's stream after an asynchronous export of this set
     bool export_pending = false;     // the next scan that writes this set waits for ev_export on the device
     bool in_flight = false;
-    uint64_t seq = 0;                // launch order
+    uint64_t seq = 0;                // launch number of the set's last scan (bind_results): launch order, and the tag of its stamps
     uint64_t seg_cap = 0;            // entries per result segment of the scan that wrote this set
 };
 
@@ -136,7 +141,8 @@ struct psk_ctx {
     int res_set = 0;                  // set of the last scan ENDED (= the one the result calls read)
     bool results_valid = false;       // false once a later psk_chi2_scan_begin has taken that set again
     int n_in_flight = 0;              // scans launched and not yet ended (0..2)
-    uint64_t scan_seq = 0;
+    bool exports_async = false;       // psk_export_survivors_async has been called: this context's scans keep their events (chi2_scan_launch)
+    uint64_t scan_seq = 1;            // launch number of the next scan; from 1: the zeroed stamp block matches no scan
     std::string err;
     int n_cu = 0;
     // knobs psk_init reads once per context: PSK_GRID_MULT (0: the build's PSK_SC_GRID_MULT), PSK_COPY_STREAMS, PSK_PINNED_CACHE_MB
@@ -168,8 +174,9 @@ struct psk_ctx {
     std::vector<size_t> ring_cap;
     void *scan_pinned = nullptr;  // pinned staging for the scan's masks / weights
     size_t scan_pinned_cap = 0;
-    void *cnt_pinned = nullptr;   // pinned landing buffer of the scan's result counters
-    uint32_t *cnt_pinned_dev = nullptr;   // ... as the device addresses it (looked up once, with the allocation)
+    void *cnt_pinned = nullptr;   // pinned, coherent landing block of the scans' stamps: STAMP_SET_WORDS u64 per result set (scan_stamps.h)
+    uint64_t *cnt_pinned_dev = nullptr;   // ... as the device addresses it (looked up once, with the allocation)
+    double wall_clock_khz = 0;    // rate of the clock the kernels stamp with (hipDeviceAttributeWallClockRate)
     static constexpr int LANES = 24;
     // .gz inputs (gz_inflate.hip): what a run of them is inflated in.  Two sets of the buffers that outlive the inflate -- the
     // compressed images in host memory, their copy and the text on the device --, because a call's runs are a pipeline: one is

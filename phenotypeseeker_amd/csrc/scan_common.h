@@ -6,6 +6,7 @@
 #include "dev_utils.h"
 #include "psk_internal.h"
 #include "chi2_plan.h"
+#include "scan_stamps.h"
 
 #include <hip/hip_ext.h>
 #include <type_traits>
@@ -34,6 +35,7 @@ constexpr int SC_NSEG = 256;
 constexpr int SC_CNT_STRIDE = 32;  // u32 per counter slot
 constexpr int SC_INL_WORDS = 16;   // mask words carried inside ScanArgs
 static_assert(CX_WAVES * 64 == SC_THREADS && CX_NSEG == SC_NSEG, "chi2_plan.h restates the launch constants");
+static_assert(STAMP_NSEG == SC_NSEG, "scan_stamps.h restates the number of segments");
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 struct ScanArgs {
@@ -77,6 +79,25 @@ __device__ __forceinline__ void append_candidate(const ScanSink &S, uint64_t row
     S.res_nw[idx] = n_w;
 }
 
+// ---- stamps: what the host learns of a scan straight from its kernels (scan_stamps.h) ------------------------------------
+// One relaxed system-scope store of an aligned 8-byte word into pinned, coherent host memory: value and tag arrive
+// together, so no fence and no second atomic go with it.
+__device__ __forceinline__ void stamp_store(uint64_t *p, uint64_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
+__device__ __forceinline__ void stamp_clock(const ScanSink &S, int slot) { stamp_store(S.host_counts + STAMP_NSEG + slot, stamp_clock_word(S.seq, (uint64_t)wall_clock64())); }
+// a segment's count (the finalize kernels of the two-kernel scans: they are waited for and timed by events)
+__device__ __forceinline__ void stamp_count(const ScanSink &S, uint32_t seg, uint32_t c) { stamp_store(S.host_counts + seg, stamp_count_word(S.seq, c)); }
+// ... with the clock just before it: the single-kernel chi2 scans, whose time is the last of these less the start clock
+__device__ __forceinline__ void stamp_segment(const ScanSink &S, uint32_t seg, uint32_t c)
+{
+    stamp_clock(S, (int)seg);
+    stamp_count(S, seg, c);
+}
+// first thing in a single-kernel chi2 scan: the start clock
+__device__ __forceinline__ void stamp_scan_start(const ScanSink &S)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) stamp_clock(S, STAMP_START);
+}
+
 // Called by every thread at the very end of a chi2 scan workgroup: the LAST workgroup of a segment to get here
 // publishes the segment's count and re-arms the counter (ticket = second word of the counter's 128-byte line).
 __device__ __forceinline__ void publish_segment(const ScanSink &S)
@@ -93,7 +114,7 @@ __device__ __forceinline__ void publish_segment(const ScanSink &S)
         const uint32_t c = atomicExch(slot, 0u);
         slot[1] = 0;
         S.final_counts[seg] = c;
-        S.host_counts[seg] = c;
+        stamp_segment(S, seg, c);
     }
 }
 
@@ -113,7 +134,7 @@ __device__ __forceinline__ void publish_segment_once(const ScanSink &S)
         const uint32_t c = (uint32_t)old;
         *slot = 0ull;
         S.final_counts[seg] = c;
-        S.host_counts[seg] = c;
+        stamp_segment(S, seg, c);
     }
 }
 
@@ -129,6 +150,7 @@ int setup_results_rows(psk_ctx *ctx, ScanSink &s, dim3 grid, uint64_t rows_per_b
 int setup_results(psk_ctx *ctx, ScanArgs &a, dim3 grid, int G, int unroll, int set, int threads = SC_THREADS);
 int pick_result_set(psk_ctx *ctx, int *set_out, bool keep_results = false);
 int fetch_counts(psk_ctx *ctx, int set);
+const volatile uint64_t *scan_stamp_words(const psk_ctx *ctx, int set);
 // ttest_scan.hip: the moment tables (their two building kernels live there, for both scans)
 struct ScanShape {   // what a scan launches with
     dim3 grid;
@@ -503,15 +525,18 @@ void dispatch_G(int G, F &&f)
 
 // The event pair of a timed launch; either may be null.  The events ride on the kernel's own dispatch: nothing is queued
 // before or after the kernel for them, hipEventSynchronize(stop) waits for the kernel, and hipEventElapsedTime(start, stop)
-// is the dispatch's start to its end.  A scan of several kernels puts start on the first and stop on the last.
+// is the dispatch's start to its end.  A scan of several kernels puts start on the first and stop on the last.  TimedBy{}:
+// no events at all -- the dispatch carries no completion signal, and whoever launched it learns of its end and its time
+// from the kernel's stamps (the unweighted chi2 scans of psk_chi2_scan_begin; psk_scan_end, chi2_driver.hip).
 struct TimedBy {
     hipEvent_t start = nullptr, stop = nullptr;
     TimedBy first() const { return {start, nullptr}; }
     TimedBy last() const { return {nullptr, stop}; }
 };
 
-// The one way a scan kernel is launched: on `st`, timed by `ev`; lds > 0: the kernel keeps `lds` bytes of tables in
-// dynamic LDS (beyond the 64 KB a kernel gets unasked).
+// The one way a scan kernel is launched: on `st`, timed by `ev` or, with both events null, by nothing (r19: a plain
+// hipLaunchKernelGGL in that case cost the host the same, 7.1-7.4 us per step of the native ring either way, so there
+// is one call); lds > 0: the kernel keeps `lds` bytes of tables in dynamic LDS (beyond the 64 KB a kernel gets unasked).
 template <class... KA, class... A>
 void launch_timed(void (*kern)(KA...), dim3 grid, int threads, size_t lds, hipStream_t st, TimedBy ev, const A &...args)
 {

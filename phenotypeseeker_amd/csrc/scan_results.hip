@@ -46,21 +46,43 @@ int bind_results(psk_ctx *ctx, ScanSink &s, uint64_t seg_cap, int set)
             PSK_HIP(ctx, hipMemsetAsync(ctx->res_count.p, 0, (SC_NSEG * SC_CNT_STRIDE + 2 * SC_NSEG) * 4, ctx->stream));
         }
         if (!ctx->cnt_pinned) {
-            PSK_HIP(ctx, hipHostMalloc(&ctx->cnt_pinned, 2 * SC_NSEG * 4, hipHostMallocDefault));
-            void *hc = nullptr;
-            PSK_HIP(ctx, hipHostGetDevicePointer(&hc, ctx->cnt_pinned, 0));
-            ctx->cnt_pinned_dev = static_cast<uint32_t *>(hc);
+            // coherent, said explicitly: the host reads the stamps while the kernel that writes them still runs.  Zeroed:
+            // launch numbers start at 1, so a word no scan has written carries no scan's tag.
+            void *blk = nullptr, *hc = nullptr;
+            PSK_HIP(ctx, hipHostMalloc(&blk, 2 * STAMP_SET_WORDS * 8, hipHostMallocCoherent));
+            memset(blk, 0, 2 * STAMP_SET_WORDS * 8);
+            if (hipHostGetDevicePointer(&hc, blk, 0) != hipSuccess) {
+                (void)hipHostFree(blk);
+                return psk_fail(ctx, PSK_EHIP, "hipHostGetDevicePointer failed for the scans' stamp block");
+            }
+            int khz = 0;
+            if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, ctx->device) != hipSuccess || khz <= 0) {
+                (void)hipHostFree(blk);
+                return psk_fail(ctx, PSK_EHIP, "the device reports no wall clock rate");
+            }
+            ctx->wall_clock_khz = khz;
+            ctx->cnt_pinned = blk;
+            ctx->cnt_pinned_dev = static_cast<uint64_t *>(hc);
         }
         a.counter = ctx->res_count.as<uint32_t>();
         a.final_counts = a.counter + SC_NSEG * SC_CNT_STRIDE + set * SC_NSEG;  // one compact array per result set
-        a.host_counts = ctx->cnt_pinned_dev + set * SC_NSEG;
+        a.host_counts = ctx->cnt_pinned_dev + set * STAMP_SET_WORDS;
         a.seg_cap = (uint32_t)seg_cap;
         sl.sink_valid = true;
     }
+    sl.stamped = false;         // (chi2_scan_launch says otherwise after it has launched without events)
+    sl.seq = ctx->scan_seq++;   // the scan being set up: its place in the launch order and the tag of its stamps
     s = sl.sink;
+    s.seq = (uint32_t)sl.seq;
     sl.seg_cap = seg_cap;
     if (set == ctx->res_set) ctx->results_valid = false;  // the last ended scan's results are about to go
     return PSK_OK;
+}
+
+// the stamp words of result set `set` as the host reads them: STAMP_NSEG counts, then STAMP_CLOCKS clocks
+const volatile uint64_t *scan_stamp_words(const psk_ctx *ctx, int set)
+{
+    return static_cast<const volatile uint64_t *>(ctx->cnt_pinned) + set * STAMP_SET_WORDS;
 }
 
 int setup_results_rows(psk_ctx *ctx, ScanSink &s, dim3 grid, uint64_t rows_per_block, int set)
@@ -78,15 +100,20 @@ int setup_results(psk_ctx *ctx, ScanArgs &a, dim3 grid, int G, int unroll, int s
 }
 
 // per-segment counts of the scan that wrote result set `set`, as its kernels left them in pinned host memory (after
-// that scan has been waited for); n_pass = their sum.  The set becomes the one the result calls read.
+// that scan has been waited for, by event or by these very stamps); n_pass = their sum.  The set becomes the one the
+// result calls read.  Every word must carry the scan's launch number: a count of another scan is never handed out.
 int fetch_counts(psk_ctx *ctx, int set)
 {
-    const uint32_t *raw = static_cast<const uint32_t *>(ctx->cnt_pinned) + set * SC_NSEG;
+    const volatile uint64_t *raw = scan_stamp_words(ctx, set);
     const uint64_t seg_cap = ctx->slot[set].seg_cap;
+    const uint32_t seq = (uint32_t)ctx->slot[set].seq;
     ctx->seg_counts.assign(SC_NSEG, 0);
     uint64_t tot = 0;
     for (int s = 0; s < SC_NSEG; s++) {
-        const uint32_t c = raw[s];
+        const uint64_t w = stamp_load(raw + s);
+        if (stamp_word_seq(w) != seq)
+            return psk_fail(ctx, PSK_ESTATE, "result segment %d carries the count of scan %u, not of scan %u", s, stamp_word_seq(w), seq);
+        const uint32_t c = stamp_word_count(w);
         if (c > seg_cap) return psk_fail(ctx, PSK_ERANGE, "result segment %d overflowed (%u > %llu)", s, c, (unsigned long long)seg_cap);
         ctx->seg_counts[s] = c;
         tot += c;
@@ -299,7 +326,19 @@ extern "C" int psk_export_survivors_async(psk_ctx *ctx, void *device_dst, uint64
     if (!device_dst || cap_records < 1) return psk_fail(ctx, PSK_EINVAL, "bad destination");
     PSK_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    hipEvent_t &ev = ctx->slot[ctx->res_set].ev_export;
+    ScanSlot &sl = ctx->slot[ctx->res_set];
+    // A scan that psk_scan_end waited for by its event has completed: its rows and counts are visible to any stream.  A
+    // stamped scan has only published its words: the dispatch may not have retired, and its rows lie in the L2 of whichever
+    // XCD appended them until it does.  The export runs on another stream, so it is ordered behind the scan on the device.
+    // (The event also covers a later scan already queued on ctx->stream: hence exports_async, after which the scans of
+    // this context carry their events again and this branch is not taken.)
+    if (sl.stamped) {
+        if (!sl.ev_ended) PSK_HIP(ctx, hipEventCreateWithFlags(&sl.ev_ended, hipEventDisableTiming));
+        PSK_HIP(ctx, hipEventRecord(sl.ev_ended, ctx->stream));
+        PSK_HIP(ctx, hipStreamWaitEvent(st, sl.ev_ended, 0));
+    }
+    ctx->exports_async = true;
+    hipEvent_t &ev = sl.ev_export;
     if (!ev) PSK_HIP(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     export_records_kernel<<<SC_NSEG, SC_NSEG, 0, st>>>(
         ctx->slot[ctx->res_set].res.as<uint8_t>(), ctx->res_seg_cap * SC_NSEG, (uint32_t)ctx->res_seg_cap,

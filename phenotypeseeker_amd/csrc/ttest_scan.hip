@@ -235,7 +235,7 @@ __global__ __launch_bounds__(SC_FIN_THREADS) void ttest_finalize_kernel(const Sc
     if (threadIdx.x == 0) {
         P.sink.counter[seg * SC_CNT_STRIDE] = 0;  // re-armed for the next scan
         P.sink.final_counts[seg] = s_out;
-        P.sink.host_counts[seg] = s_out;
+        stamp_count(P.sink, seg, s_out);
     }
 }
 
