@@ -410,6 +410,39 @@ int psk_forest_fit(psk_ctx *ctx, const float *X, const int32_t *y01, int n, int 
                    int32_t *max_depth_out, int64_t node_pool, int64_t *tree_node_off_out, int32_t *nodes_out,
                    double *impurity_out, int32_t *leaf_out);
 
+/* ---- f8: the `-bc NB` estimator -------------------------------------------------------------------
+ * set_model makes BernoulliNB() (modeling.py:1034-1035), but the REFERENCE CANNOT COMPLETE `-bc NB`: get_best_model
+ * (:1075-1103) has no NB branch, best_model stays None (:623) and fit_model (:1216) fails on None.fit.  The yardstick is
+ * therefore scikit-learn 1.7.2's BernoulliNB() with its default parameters, fitted directly, without a search
+ * (csrc/solver_nb.hip).  The library counts and adds; the logarithms between the two calls are the caller's, taken on the
+ * host in scikit-learn's own expressions, so that the fitted attributes are scikit-learn's bit for bit.
+ *
+ * psk_nb_fit: same batching and the same meaning of X, y01, n, p, fold, fit_fold, n_fits as psk_tree_fit (fit_fold[j] = -1:
+ * all samples).  Per fit, over its training samples:
+ *   feature_count_out[n_fits][2][p]   samples of class 0 / class 1 that carry the k-mer
+ *   class_count_out[n_fits][2]        samples of class 0 / class 1
+ * Integers, so the result is exact.  The design must be 0/1 (PSK_EINVAL otherwise); a fit whose training samples are of one
+ * class is refused (PSK_EINVAL).
+ *
+ * psk_nb_jll: the joint log-likelihood of every row of X[n][p] (0/1, PSK_EINVAL otherwise) under n_models models:
+ *   delta[n_models][2][p]          feature_log_prob_ - log(1 - exp(feature_log_prob_))
+ *   class_log_prior[n_models][2]
+ *   neg_sum[n_models][2]           sum over the columns of log(1 - exp(feature_log_prob_))
+ *   jll_out[n_models][n][2]        ((sum over the columns j the row carries of delta[m][c][j]) + class_log_prior[m][c])
+ *                                  + neg_sum[m][c]
+ * in f64 without multiplications.  The order of the sum is part of the contract: 64 partial sums, partial sum l starting from
+ * +0.0 and adding the set columns among l, l + 64, l + 128, ... in ascending order; then a_l = a_l + a_(l xor m) for m = 32,
+ * 16, 8, 4, 2, 1 over all l at once, and a_0 is the sum.  A row's result depends on nothing but that row and the model.
+ *
+ * Limits of both calls (no sample x sample structure, so not the 4096 samples of the other fits): n <= 65535 x 64 =
+ * 4,194,240 samples and at most 65535 fits or models per call (PSK_ERANGE beyond); every index is 64-bit, so n x p is
+ * bounded only by the device memory that the float design of 4 n p bytes needs.
+ */
+int psk_nb_fit(psk_ctx *ctx, const float *X, const int32_t *y01, int n, int p, const int32_t *fold,
+               const int32_t *fit_fold, int n_fits, int32_t *feature_count_out, int32_t *class_count_out);
+int psk_nb_jll(psk_ctx *ctx, const float *X, int n, int p, const double *delta, int n_models,
+               const double *class_log_prior, const double *neg_sum, double *jll_out);
+
 /* ---- f1: fixed-dictionary counting (prediction) ---------------------------------------------
  * Replaces `gmer_counter -db <txt> <addr>` (prediction.Samples.map_samples, prediction.py:72-80):
  * occurrences, both strands with multiplicity, of each dictionary k-mer (canonical words) in

@@ -1,4 +1,5 @@
-// Host side of the solver entry points (solver.hip, solver_l2.hip, solver_svc.hip, solver_tree.hip, solver_forest.hip): an owned, typed device
+// Host side of the solver entry points (solver.hip, solver_l2.hip, solver_svc.hip, solver_tree.hip, solver_forest.hip,
+// solver_nb.hip): an owned, typed device
 // array; the argument check and the input / result block of the four linear-model fits; the host packings of the design.
 #pragma once
 #include <hip/hip_runtime.h>

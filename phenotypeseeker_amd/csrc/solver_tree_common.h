@@ -2,7 +2,8 @@
 // the bit layout of the packed 0/1 design and the kernel that packs it, scikit-learn's impurity expressions, the node
 // record, and the host prologue that brings the design to the device.  The fit kernels are each unit's own: they
 // parallelise differently on purpose.  Both units are compiled -ffp-contract=off; the f64 expressions here are
-// scikit-learn's in its order, and this is their one statement.
+// scikit-learn's in its order, and this is their one statement.  solver_nb.hip (`-bc NB`) takes the bit layout, the packing
+// kernel and the host prologue from here and nothing else.
 #pragma once
 #include <hip/hip_runtime.h>
 

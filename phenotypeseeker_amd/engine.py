@@ -528,6 +528,39 @@ class PskContext:
             row += 1
         return sum0, sum1, trees
 
+    def nb_fit(self, X, y01, fold, fit_fold):
+        """Bernoulli naive-Bayes counts (psk_nb_fit) on a 0/1 design, every fit in one call; fit_fold[j] = -1: all samples.
+        Returns (feature_count[n_fits][2][p], class_count[n_fits][2]), int32: per class the training samples that carry
+        each k-mer, and the training samples."""
+        X = np.ascontiguousarray(X, dtype=np.float32)
+        n, p = X.shape
+        y = np.ascontiguousarray(y01, dtype=np.int32)
+        fold = np.ascontiguousarray(fold, dtype=np.int32)
+        fit_fold = np.ascontiguousarray(fit_fold, dtype=np.int32)
+        if len(y) != n or len(fold) != n or fit_fold.ndim != 1:
+            raise ValueError("y01 and fold must have one entry per row of X, fit_fold one per fit")
+        nf = len(fit_fold)
+        fc, cc = np.zeros((nf, 2, p), dtype=np.int32), np.zeros((nf, 2), dtype=np.int32)
+        self._check(self._lib.psk_nb_fit(self._h, _ptr(X), _ptr(y), n, p, _ptr(fold), _ptr(fit_fold), nf, _ptr(fc), _ptr(cc)), "psk_nb_fit")
+        return fc, cc
+
+    def nb_jll(self, X, delta, class_log_prior, neg_sum):
+        """Joint log-likelihoods of the rows of a 0/1 design under Bernoulli naive-Bayes models (psk_nb_jll):
+        delta[n_models][2][p] = feature_log_prob_ - log(1 - exp(feature_log_prob_)), class_log_prior[n_models][2],
+        neg_sum[n_models][2] (one model: the leading axis may be left out).  Returns jll[n_models][n][2] (one model:
+        jll[n][2]) in the summation order include/psk.h states."""
+        X = np.ascontiguousarray(X, dtype=np.float32)
+        n, p = X.shape
+        delta = np.ascontiguousarray(delta, dtype=np.float64)
+        one = delta.ndim == 2
+        delta = delta.reshape(-1, 2, p)
+        nm = delta.shape[0]
+        prior = np.ascontiguousarray(class_log_prior, dtype=np.float64).reshape(nm, 2)
+        neg = np.ascontiguousarray(neg_sum, dtype=np.float64).reshape(nm, 2)
+        jll = np.zeros((nm, n, 2))
+        self._check(self._lib.psk_nb_jll(self._h, _ptr(X), n, p, _ptr(delta), nm, _ptr(prior), _ptr(neg), _ptr(jll)), "psk_nb_jll")
+        return jll[0] if one else jll
+
     # -- population-structure weights --------------------------------------------------------------
     def minhash_sketch(self, data, k=21, sketch_size=1000, seed=42):
         data = bytes(data)

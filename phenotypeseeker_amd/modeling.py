@@ -29,7 +29,7 @@ from . import formats, metrics, _stats
 from .engine import PskContext
 from . import _lib
 from ._lib import PSK_EGZIP, PskError
-from .model import (SVC, DecisionTree, L1LogisticRegression, L2LogisticRegression, LassoRegression, RandomForest, RandomizedSearch,
+from .model import (SVC, BernoulliNB, DecisionTree, L1LogisticRegression, L2LogisticRegression, LassoRegression, RandomForest, RandomizedSearch,
                     RidgeRegression)
 
 RED_BANNER = "\x1b[1;1;101m%s\x1b[0m\n"
@@ -343,8 +343,8 @@ class Input:
                    n_iter, n_splits_cv_inner, testset_size, train_on_whole, logreg_solver, jump_to, pca,
                    real_counts, omit_B, kmerDB):
         """Same positional signature as the reference (:141-183).  Options that select estimators
-        outside the hot path (SVM/RF/DT/NB, L2/elastic net, saga, PCA) are rejected here; `-bc SVM`, `-bc DT` and `-bc RF` pass
-        with their knobs (PSK_SVM, PSK_DT, PSK_RF)."""
+        outside the hot path (SVM/RF/DT/NB, L2/elastic net, saga, PCA) are rejected here; `-bc SVM`, `-bc DT`, `-bc RF` and
+        `-bc NB` pass with their knobs (PSK_SVM, PSK_DT, PSK_RF, PSK_NB)."""
         if alphas is None:
             phenotypes.alphas = np.logspace(math.log10(alpha_min), math.log10(alpha_max), num=n_alphas)
         else:
@@ -411,6 +411,16 @@ class Input:
                                      % (RandomizedSearch.max_n_iter(size), size, phenotypes.n_iter))
                 phenotypes.binary_classifier = "RF"
                 phenotypes.model_name_long, phenotypes.model_name_short = "random forest", "RF"
+            elif binary_classifier == "NB" and _lib.env_flag("PSK_NB"):
+                # set_model (:1034-1035): BernoulliNB().  The reference cannot complete this branch -- get_best_model (:1075-1103)
+                # has no NB case and fit_model (:1216) calls None.fit --, so the model is scikit-learn's BernoulliNB() fitted
+                # directly (model_nb.py).  It binarizes its input (X > 0), so --real_counts gives the model of the presence matrix;
+                # principal components are not presence bits
+                if pca:
+                    raise SystemExit("The naive Bayes classifier on the GPU engine takes the k-mer presence matrix only: "
+                                     "--pca is not supported with -bc NB.")
+                phenotypes.binary_classifier = "NB"
+                phenotypes.model_name_long, phenotypes.model_name_short = "Naive Bayes", "NB"
             elif binary_classifier != "log":
                 raise SystemExit("Only the logistic-regression classifier runs on the GPU engine, got %r "
                                  "(SVM/RF/DT/NB are outside the accelerated path)." % binary_classifier)
@@ -725,6 +735,8 @@ class phenotypes:
                 return DecisionTree(), {"max_depth": [1, 2, 3, 4, 5, 6, 7, 8, 9, 10], "criterion": ["gini", "entropy"]}, None
             if self.binary_classifier == "RF":
                 return RandomForest(random_state=self.rf_seed), {k: list(v) for k, v in RF_GRID.items()}, None
+            if self.binary_classifier == "NB":
+                return BernoulliNB(), None, None
             if self.binary_classifier == "SVM":
                 return SVC(kernel=self.kernel, probability=True, max_iter=self.max_iter, tol=self.tol), "C", grid
             if self.penalty == "L2":
@@ -738,6 +750,11 @@ class phenotypes:
     def _fit(self, ctx, X, y):
         est, pname, grid = self._new_estimator()
         self.model = est
+        if self.binary_classifier == "NB" and self.pred_scale == "binary":
+            # no search: the fitted estimator itself is the model, and it is what the .pkl holds (the reference's fit_model, :1216,
+            # would fit best_model directly too).  The reports below predict on the host, in the device's order of summation
+            self.model_fitted = est.fit(X, y, ctx)
+            return
         self.model_fitted = est._new_search(pname, grid, self.n_splits_cv_inner, self.n_iter).fit(X, y, ctx)
         if est._warns_at_max_iter and int(est.max_iter) != -1 and np.any(self.model_fitted.n_iter_ >= int(est.max_iter)):
             # scikit-learn's ConvergenceWarning (svm/_base.py, _warn_from_fit_status), once per grid search
@@ -836,7 +853,9 @@ class phenotypes:
         summary.close()
 
     def _cross_validation_results(self, out):
-        """(:1219-1237)"""
+        """(:1219-1237); nothing for NB, which is not searched (:1220)"""
+        if self.model_name_short == "NB":
+            return
         out.write("Parameters:\n%s\n\n" % self.model)
         out.write("Grid scores (%s) on development set: \n" %
                   ("R2 score" if self.pred_scale == "continuous" else "mean accuracy"))
@@ -912,6 +931,14 @@ class phenotypes:
         file object is shared with it: a stale offset could overwrite what it wrote)."""
         with open(path, "w") as out:
             out.write("K-mer\tcoef._in_" + self.model_name_short + "_model\tNo._of_samples_with_k-mer\tSamples_with_k-mer\n")
+            if self.model_name_short == "NB":
+                # the coefficient column is the literal NA (:1440-1441), which psk_write_model_coefficients' column of doubles
+                # cannot say: these lines are written here
+                Xn, names = np.asarray(self.ML["X"]).reshape(len(self.ML["index"]), len(self.ML["kmers"])), self.ML["index"]
+                for j, km in enumerate(self.ML["kmers"]):
+                    who = [names[i] for i in np.nonzero(Xn[:, j] != 0)[0]]
+                    out.write("%s\tNA\t%d\t| %s\n" % (km, len(who), " ".join(who)))
+                return
         be = self.model_fitted.best_estimator_
         # what the estimator declares; a scikit-learn linear model handed over in the fit's place: its coef_ as one row
         coefs = be._coef_column if hasattr(be, "_coef_column") else np.ravel(be.coef_)

@@ -89,12 +89,15 @@ class Phenotypes:
     def get_inp_matrix(self, ctx, n_threads=8):
         self.matrix[:, :] = Samples.map_samples(ctx, list(Input.samples.values()), self, n_threads)
 
-    def predict(self):
-        """predictions_<pheno>.txt (:165-182)"""
-        predictions = self.model.predict(self.matrix)
+    def predict(self, ctx=None):
+        """predictions_<pheno>.txt (:165-182).  A naive-Bayes model of this package (what the stub reader makes of an NB file)
+        takes its joint log-likelihoods from the open context (psk_nb_jll); every other model predicts as before."""
+        from .model_nb import BernoulliNB
+        on_device = (ctx,) if ctx is not None and isinstance(self.model, BernoulliNB) else ()
+        predictions = self.model.predict(self.matrix, *on_device)
         with open("predictions_" + self.name + ".txt", "w+") as out:
             if self.pred_scale == "binary":
-                proba = self.model.predict_proba(self.matrix)
+                proba = self.model.predict_proba(self.matrix, *on_device)
                 out.write("Sample_ID\tpredicted_phenotype\tprobability_for_predicted_class\n")
                 for sample, pred, pr in zip(Input.samples.keys(), predictions, proba):
                     out.write("%s\t%s\t%s\n" % (sample, str(pred), str(round(pr[1], 2))))
@@ -141,5 +144,5 @@ def prediction(args):
         for pheno in Input.phenos.values():
             sys.stderr.write("\x1b[1;32mPredicting the phenotypes for %s.\x1b[0m\n" % pheno.name)
             pheno.get_inp_matrix(ctx, max(1, min(int(getattr(args, "num_threads", 8) or 8), 16)))
-            pheno.predict()
+            pheno.predict(ctx)
     sys.stderr.write("\n\x1b[1;1;101m######          PhenotypeSeeker prediction finished          ######\x1b[0m\n")

@@ -241,12 +241,34 @@ def _forest_from_state(est):
     return m
 
 
+def _nb_from_state(est):
+    """model.BernoulliNB from the attribute dictionary of a fitted two-class sklearn.naive_bayes.BernoulliNB with the default
+    parameters: its counts, and the two log attributes as the file holds them.  None for anything else."""
+    import numpy as np
+    from .model import BernoulliNB
+    d = est.__dict__
+    classes, flp, clp = d.get("classes_"), d.get("feature_log_prob_"), d.get("class_log_prior_")
+    if classes is None or getattr(classes, "ndim", 0) != 1 or list(classes) != [0, 1] or flp is None or clp is None:
+        return None
+    try:
+        m = BernoulliNB(**{k: d[k] for k in BernoulliNB._DEFAULTS})
+    except (KeyError, ValueError):      # other parameters than the defaults: scikit-learn itself
+        return None
+    m.feature_count_ = np.asarray(d["feature_count_"], dtype=np.float64)
+    m.class_count_ = np.asarray(d["class_count_"], dtype=np.float64)
+    m.feature_log_prob_, m.class_log_prior_ = np.asarray(flp, dtype=np.float64), np.asarray(clp, dtype=np.float64)
+    if m.feature_log_prob_.shape != (2, int(d["n_features_in_"])) or m.class_log_prior_.shape != (2,):
+        return None
+    m.n_features_in_ = int(d["n_features_in_"])
+    return m
+
+
 def load_linear_package(path):
     """The model package of `path` ({'model', 'kmers', 'pca', 'pred_scale'}) with 'model' as a LinearModel -- for files
     that are plain pickles of a (grid search over a) binary linear classifier or a linear regressor, which is what
     `modeling` writes; a two-class SVC with a Platt pair comes back as model.SVC (_svc_from_state), a two-class decision tree
-    as model.DecisionTree (_tree_from_state), a two-class random forest as model.RandomForest (_forest_from_state).  None for
-    anything else
+    as model.DecisionTree (_tree_from_state), a two-class random forest as model.RandomForest (_forest_from_state), a two-class
+    BernoulliNB() as model.BernoulliNB (_nb_from_state).  None for anything else
     (joblib-wrapped arrays, multi-class models, other estimators, a PCA pipeline): the caller then takes joblib.load and
     scikit-learn itself."""
     try:
@@ -265,6 +287,11 @@ def load_linear_package(path):
             return dict(pkg, model=model)
         if kind == "RandomForestClassifier":
             model = _forest_from_state(est)
+            if model is None:
+                return None
+            return dict(pkg, model=model)
+        if kind == "BernoulliNB":
+            model = _nb_from_state(est)
             if model is None:
                 return None
             return dict(pkg, model=model)
