@@ -410,6 +410,48 @@ int psk_forest_fit(psk_ctx *ctx, const float *X, const int32_t *y01, int n, int 
                    int32_t *max_depth_out, int64_t node_pool, int64_t *tree_node_off_out, int32_t *nodes_out,
                    double *impurity_out, int32_t *leaf_out);
 
+/* ---- f9: `-bc DT` on k-mer counts (--real_counts) -------------------------------------------------
+ * psk_tree_fit on a COUNT design: the reference fits DecisionTreeClassifier() on the count matrix under --real_counts
+ * (modeling.py:1032-1033, :1069-1073, :1100-1103).  Arguments, limits and outputs as psk_tree_fit, except:
+ *   X[n][p]   integers in 0 .. 2^24 (PSK_EINVAL on a negative, fractional, non-finite or larger value)
+ *   threshold_out[n_fits][PSK_TREE_NODE_CAP]   the threshold at a split, -2.0 at a leaf (first node_count_out[j] slots)
+ * Per node, _splitter.pyx::node_split_best of scikit-learn 1.7.2 on the float32 design: a column is constant in the node
+ * when the node's training samples share one value; otherwise its candidates are the gaps between consecutive distinct
+ * values present among them, in ascending order; the proxy and its strict comparison are psk_tree_fit's; the threshold is
+ * lo / 2.0 + hi / 2.0 of the two values around the gap and x <= threshold goes left.  Among bit-equal proxies the LOWEST
+ * column index wins, then the lowest threshold.  leaf_out / frac_out route EVERY sample by the reported thresholds.  On a
+ * 0/1 design the result is psk_tree_fit's with every split threshold 0.5.  impurity_out (of all four tree calls) is taken on the
+ * host from the node's class counts through the C library's log: scikit-learn's value to the bit.
+ * The call makes one bit plane per gap between the distinct values of a column over all n samples: at most
+ * PSK_TREE_PLANE_CAP planes (PSK_ERANGE beyond), 8 x ceil(n / 64) bytes of device memory each, next to the float design
+ * (csrc/solver_tree_common.h).
+ */
+#define PSK_TREE_PLANE_CAP 1048576
+int psk_tree_fit_counts(psk_ctx *ctx, const float *X, const int32_t *y01, int n, int p, const int32_t *fold,
+                        const int32_t *fit_max_depth, const int32_t *fit_criterion, const int32_t *fit_fold, int n_fits,
+                        int32_t *node_count_out, int32_t *max_depth_out, int32_t *nodes_out, double *impurity_out,
+                        int32_t *leaf_out, double *frac_out, double *threshold_out);
+
+/* ---- f10: `-bc RF` on k-mer counts (--real_counts) ------------------------------------------------
+ * psk_forest_fit on a COUNT design (RandomForestClassifier() on the count matrix, modeling.py:1030-1031, :1057-1068,
+ * :1096-1099).  Arguments, limits and outputs as psk_forest_fit; the design, the per-node search, the threshold and the
+ * plane cap as psk_tree_fit_counts, with weighted counts in the proxy and min_samples_leaf on the distinct in-bag samples
+ * of either side of a gap.  Ties: the first column in visit order wins, then the lowest threshold inside it; the
+ * Fisher-Yates walk, the constant bookkeeping, the xorshift and n_node_samples are psk_forest_fit's.
+ *   threshold_out[node_pool]   by node slot, as impurity_out: the threshold at a split, -2.0 at a leaf; may be NULL when
+ *                              no tree is exported
+ * sum0_out / sum1_out / leaf_out route EVERY sample, weight-0 ones included, by the reported thresholds.  On a 0/1
+ * design the result is psk_forest_fit's with every split threshold 0.5.
+ */
+int psk_forest_fit_counts(psk_ctx *ctx, const float *X, const int32_t *y01, int n, int p, int n_trees,
+                          const uint16_t *tree_weight, const uint32_t *tree_state, const int32_t *tree_fit,
+                          const int32_t *tree_export, int n_fits, const int32_t *fit_criterion,
+                          const int32_t *fit_max_depth, const int32_t *fit_max_features,
+                          const int32_t *fit_min_samples_leaf, const int32_t *fit_min_samples_split, double *sum0_out,
+                          double *sum1_out, int32_t *node_count_out, int32_t *max_depth_out, int64_t node_pool,
+                          int64_t *tree_node_off_out, int32_t *nodes_out, double *impurity_out, int32_t *leaf_out,
+                          double *threshold_out);
+
 /* ---- f8: the `-bc NB` estimator -------------------------------------------------------------------
  * set_model makes BernoulliNB() (modeling.py:1034-1035), but the REFERENCE CANNOT COMPLETE `-bc NB`: get_best_model
  * (:1075-1103) has no NB branch, best_model stays None (:623) and fit_model (:1216) fails on None.fit.  The yardstick is

@@ -48,6 +48,8 @@ constexpr int FOREST_THREADS = 256;
 constexpr int FOREST_MAX_N = 4096;
 constexpr int FOREST_LDS_COLS = 1024;      // per-column arrays stay in LDS up to this many columns
 constexpr int FOREST_COL_BYTES = 28;       // proxy f64, features / constant_features / state / w_r / w_r1 i32
+constexpr int FOREST_COL_BYTES_COUNTS = 32;   // on a count design also the column's best plane, i32
+constexpr int FOREST_LDS_BYTES = 64 << 10;    // what a launch may ask for without opting in to more
 constexpr int FOREST_GRID_PER_CU = 4;
 constexpr uint32_t FOREST_NO_LABEL = 0xffff;
 constexpr int COL_CONSTANT = -1, COL_NO_SPLIT = -2;
@@ -74,10 +76,24 @@ struct ForestArgs {
     ForestLds lds;
 };
 
+// what forest_fit_kernel<true> takes besides: on a count design ForestArgs::bits holds the P threshold planes
+// (solver_tree_common.h).  Empty for the 0/1 kernel, whose arguments and code stay what they were.
+template <bool COUNTS> struct ForestCountArgs {};
+template <> struct ForestCountArgs<true> {
+    TreePlaneView<true> pv;
+    int P;
+    double *thr_out;                   // by node slot, as imp_out
+};
+
 __device__ __forceinline__ void swap_int(int *a, int i, int j) { const int t = a[i]; a[i] = a[j]; a[j] = t; }
 
-__global__ __launch_bounds__(FOREST_THREADS) void forest_fit_kernel(const ForestArgs a)
+// COUNTS: a thread walks the planes of its column in ascending order and keeps the first strictly larger proxy among the gaps
+// between the values present in the node (a plane whose right count equals the plane's before it repeats that partition), so
+// the one-lane walk sees per column what it saw on a 0/1 design: constant, no split, or one best split.
+template <bool COUNTS> __global__ __launch_bounds__(FOREST_THREADS) void forest_fit_kernel(const ForestArgs a,
+                                                                                           const ForestCountArgs<COUNTS> ca)
 {
+    constexpr int COL_BYTES = COUNTS ? FOREST_COL_BYTES_COUNTS : FOREST_COL_BYTES;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int n = a.n, p = a.p, W = a.W, B = a.B, Wn = W * 64;
@@ -87,10 +103,13 @@ __global__ __launch_bounds__(FOREST_THREADS) void forest_fit_kernel(const Forest
     ForestRec *cur = (ForestRec *)(smem + a.lds.cur);
     int *walk = (int *)(smem + a.lds.walk);     // best column, n_known, n_found of the node's walk
     const int p_pad = (p + 3) & ~3;
-    char *cols = a.cols_in_lds ? smem + a.lds.cols : a.cols_global + (size_t)blockIdx.x * FOREST_COL_BYTES * p_pad;
+    char *cols = a.cols_in_lds ? smem + a.lds.cols : a.cols_global + (size_t)blockIdx.x * COL_BYTES * p_pad;
     double *proxy = (double *)cols;
     int *features = (int *)(cols + 8 * (size_t)p_pad), *constant = features + p_pad, *col_state = constant + p_pad;
     int *col_wr = col_state + p_pad, *col_wr1 = col_wr + p_pad;
+    int *col_plane = COUNTS ? col_wr1 + p_pad : nullptr;   // the column's best plane
+    int bit_cols = p;                   // the second dimension of a.bits
+    if constexpr (COUNTS) bit_cols = ca.P;
     ForestRec *stack = a.stack + (size_t)blockIdx.x * (n + 2);
 
     for (int tree = blockIdx.x; tree < a.n_trees; tree += gridDim.x) {
@@ -153,30 +172,67 @@ __global__ __launch_bounds__(FOREST_THREADS) void forest_fit_kernel(const Forest
             int feat = -2, nr = 0, wr = 0, wr1 = 0, n_const = rec.n_const;
             double imp_l = 0.0, imp_r = 0.0;
             if (!is_leaf) {
-                for (int j = tid; j < p; j += FOREST_THREADS) {
-                    int c = 0, cw = 0, cw1 = 0;
-                    for (int w = 0; w < W; w++) {
-                        const uint64_t m = MT[w];
-                        if (!m) continue;   // (uniform: the mask words are the workgroup's)
-                        const uint64_t v = a.bits[tree_bit_at(j, w, p)];
-                        c += __popcll(v & m);
-                        for (int b = 0; b < B; b++) {
-                            cw += __popcll(v & MP[b * W + w]) << b;
-                            cw1 += __popcll(v & MPY[b * W + w]) << b;
+                if constexpr (COUNTS) {
+                    for (int i = tid; i < p; i += FOREST_THREADS) {
+                        const int j = ca.pv.col_order[i];
+                        int st = COL_CONSTANT, prev = rec.n, bq = -1, bcw = 0, bcw1 = 0;
+                        double bp = -INFINITY;
+                        for (int q = ca.pv.col_first[j]; q < ca.pv.col_first[j + 1]; q++) {
+                            int c = 0;
+                            for (int w = 0; w < W; w++)
+                                if (MT[w]) c += __popcll(a.bits[tree_bit_at(q, w, bit_cols)] & MT[w]);
+                            if (c == 0) break;   // (the planes above hold no sample of the node either)
+                            if (c == prev) continue;
+                            prev = c;
+                            if (st == COL_CONSTANT) st = COL_NO_SPLIT;
+                            if (rec.n - c < msl || c < msl) continue;
+                            int cw = 0, cw1 = 0;
+                            for (int w = 0; w < W; w++) {
+                                if (!MT[w]) continue;
+                                const uint64_t v = a.bits[tree_bit_at(q, w, bit_cols)];
+                                for (int b = 0; b < B; b++) {
+                                    cw += __popcll(v & MP[b * W + w]) << b;
+                                    cw1 += __popcll(v & MPY[b * W + w]) << b;
+                                }
+                            }
+                            const double dwr = (double)cw, dwl = (double)(rec.wn - cw);
+                            const double ir = tree_impurity(crit, (double)(cw - cw1), (double)cw1, dwr);
+                            const double il = tree_impurity(crit, c0n - (double)(cw - cw1), c1n - (double)cw1, dwl);
+                            const double v = -dwr * ir - dwl * il;
+                            if (v > bp) { bp = v; bq = q; st = c; bcw = cw; bcw1 = cw1; }
                         }
+                        if (bq >= 0) proxy[j] = bp;
+                        col_state[j] = st;
+                        col_wr[j] = bcw;
+                        col_wr1[j] = bcw1;
+                        col_plane[j] = bq;
                     }
-                    int st = c;
-                    if (c == 0 || c == rec.n) st = COL_CONSTANT;
-                    else if (rec.n - c < msl || c < msl) st = COL_NO_SPLIT;
-                    else {
-                        const double dwr = (double)cw, dwl = (double)(rec.wn - cw);
-                        const double ir = tree_impurity(crit, (double)(cw - cw1), (double)cw1, dwr);
-                        const double il = tree_impurity(crit, c0n - (double)(cw - cw1), c1n - (double)cw1, dwl);
-                        proxy[j] = -dwr * ir - dwl * il;
+                } else {
+                    for (int j = tid; j < p; j += FOREST_THREADS) {
+                        int c = 0, cw = 0, cw1 = 0;
+                        for (int w = 0; w < W; w++) {
+                            const uint64_t m = MT[w];
+                            if (!m) continue;   // (uniform: the mask words are the workgroup's)
+                            const uint64_t v = a.bits[tree_bit_at(j, w, p)];
+                            c += __popcll(v & m);
+                            for (int b = 0; b < B; b++) {
+                                cw += __popcll(v & MP[b * W + w]) << b;
+                                cw1 += __popcll(v & MPY[b * W + w]) << b;
+                            }
+                        }
+                        int st = c;
+                        if (c == 0 || c == rec.n) st = COL_CONSTANT;
+                        else if (rec.n - c < msl || c < msl) st = COL_NO_SPLIT;
+                        else {
+                            const double dwr = (double)cw, dwl = (double)(rec.wn - cw);
+                            const double ir = tree_impurity(crit, (double)(cw - cw1), (double)cw1, dwr);
+                            const double il = tree_impurity(crit, c0n - (double)(cw - cw1), c1n - (double)cw1, dwl);
+                            proxy[j] = -dwr * ir - dwl * il;
+                        }
+                        col_state[j] = st;
+                        col_wr[j] = cw;
+                        col_wr1[j] = cw1;
                     }
-                    col_state[j] = st;
-                    col_wr[j] = cw;
-                    col_wr1[j] = cw1;
                 }
                 __syncthreads();
                 if (tid == 0) {
@@ -238,6 +294,15 @@ __global__ __launch_bounds__(FOREST_THREADS) void forest_fit_kernel(const Forest
             }
             const int id = next_id++;
             deepest = max(deepest, rec.depth);
+            int route = feat;
+            if constexpr (COUNTS) {
+                double thr = -2.0;
+                if (!is_leaf) {
+                    thr = tree_node_threshold(ca.pv.X, n, p, feat, ca.pv.plane_val[col_plane[feat]], MT, walk);
+                    route = tree_route_plane(ca.pv.col_first, ca.pv.plane_val, feat, thr);
+                }
+                if (tid == 0 && node_off >= 0 && id < node_cap) ca.thr_out[node_off + id] = thr;
+            }
             if (tid == 0 && node_off >= 0 && id < node_cap)
                 tree_write_node(a.nodes + (size_t)node_off * TREE_NODE_FIELDS, a.imp_out + node_off, id, rec.parent, rec.is_left, feat, is_leaf,
                                 rec.n, rec.wn - rec.w1, rec.w1, rec.imp);
@@ -253,7 +318,7 @@ __global__ __launch_bounds__(FOREST_THREADS) void forest_fit_kernel(const Forest
             } else {
                 // the right child takes this node's slot, the left one the slot above it: popped first
                 for (int s = tid; s < n; s += FOREST_THREADS)
-                    if (label[s] == slot && !((a.bits[tree_bit_at(feat, s >> 6, p)] >> (s & 63)) & 1ull)) label[s] = (uint16_t)(slot + 1);
+                    if (label[s] == slot && !((a.bits[tree_bit_at(route, s >> 6, bit_cols)] >> (s & 63)) & 1ull)) label[s] = (uint16_t)(slot + 1);
                 if (tid == 0) {
                     stack[sp] = ForestRec{id, rec.depth + 1, 0, nr, wr, wr1, n_const, 0, imp_r};
                     stack[sp + 1] = ForestRec{id, rec.depth + 1, 1, rec.n - nr, rec.wn - wr, rec.w1 - wr1, n_const, 0, imp_l};
@@ -285,8 +350,8 @@ __global__ __launch_bounds__(256) void forest_sum_kernel(const double *__restric
 int align16(int v) { return (v + 15) & ~15; }
 
 // the LDS region for a call of W words, B planes and p columns; the per-column arrays go last and are left out (cols_in_lds
-// = 0) past FOREST_LDS_COLS columns
-ForestLds forest_lds_layout(int W, int B, int p, int *cols_in_lds)
+// = 0) past FOREST_LDS_COLS columns, or where they would take the region past FOREST_LDS_BYTES
+ForestLds forest_lds_layout(int W, int B, int p, int col_bytes, int *cols_in_lds)
 {
     ForestLds l{};
     int at = 0;
@@ -300,22 +365,23 @@ ForestLds forest_lds_layout(int W, int B, int p, int *cols_in_lds)
     l.cur = at; at = align16(at + (int)sizeof(ForestRec));
     l.walk = at; at = align16(at + 16);
     l.cols = at;
-    *cols_in_lds = p <= FOREST_LDS_COLS;
-    if (*cols_in_lds) at = align16(at + FOREST_COL_BYTES * ((p + 3) & ~3));
+    const int with_cols = align16(at + col_bytes * ((p + 3) & ~3));
+    *cols_in_lds = p <= FOREST_LDS_COLS && with_cols <= FOREST_LDS_BYTES;
+    if (*cols_in_lds) at = with_cols;
     l.total = at;
     return l;
 }
 
-}  // namespace
-
-extern "C" int psk_forest_fit(psk_ctx *ctx, const float *X, const int32_t *y01, int n, int p, int n_trees,
-                              const uint16_t *tree_weight, const uint32_t *tree_state, const int32_t *tree_fit,
-                              const int32_t *tree_export, int n_fits, const int32_t *fit_criterion, const int32_t *fit_max_depth,
-                              const int32_t *fit_max_features, const int32_t *fit_min_samples_leaf,
-                              const int32_t *fit_min_samples_split, double *sum0_out, double *sum1_out, int32_t *node_count_out,
-                              int32_t *max_depth_out, int64_t node_pool, int64_t *tree_node_off_out, int32_t *nodes_out,
-                              double *impurity_out, int32_t *leaf_out)
+// psk_forest_fit (COUNTS false: threshold_out unused) and psk_forest_fit_counts; `who` names the entry point in messages
+template <bool COUNTS>
+int forest_fit_call(psk_ctx *ctx, const char *who, const float *X, const int32_t *y01, int n, int p, int n_trees,
+                    const uint16_t *tree_weight, const uint32_t *tree_state, const int32_t *tree_fit, const int32_t *tree_export,
+                    int n_fits, const int32_t *fit_criterion, const int32_t *fit_max_depth, const int32_t *fit_max_features,
+                    const int32_t *fit_min_samples_leaf, const int32_t *fit_min_samples_split, double *sum0_out, double *sum1_out,
+                    int32_t *node_count_out, int32_t *max_depth_out, int64_t node_pool, int64_t *tree_node_off_out, int32_t *nodes_out,
+                    double *impurity_out, int32_t *leaf_out, double *threshold_out)
 {
+    constexpr int COL_BYTES = COUNTS ? FOREST_COL_BYTES_COUNTS : FOREST_COL_BYTES;
     if (!ctx) return PSK_EINVAL;
     if (!X || !y01 || !tree_weight || !tree_state || !tree_fit || !tree_export || !fit_criterion || !fit_max_depth ||
         !fit_max_features || !fit_min_samples_leaf || !fit_min_samples_split || !sum0_out || !sum1_out || !node_count_out ||
@@ -324,7 +390,7 @@ extern "C" int psk_forest_fit(psk_ctx *ctx, const float *X, const int32_t *y01, 
     if (n < 1 || p < 1 || n_fits < 1 || n_trees < 1)
         return psk_fail(ctx, PSK_EINVAL, "bad problem shape n=%d p=%d fits=%d trees=%d", n, p, n_fits, n_trees);
     if (n > FOREST_MAX_N)
-        return psk_fail(ctx, PSK_ERANGE, "psk_forest_fit keeps a label per sample in LDS: at most %d samples, got %d", FOREST_MAX_N, n);
+        return psk_fail(ctx, PSK_ERANGE, "%s keeps a label per sample in LDS: at most %d samples, got %d", who, FOREST_MAX_N, n);
     for (int f = 0; f < n_fits; f++) {
         if (fit_criterion[f] != 0 && fit_criterion[f] != 1)
             return psk_fail(ctx, PSK_EINVAL, "fit %d: criterion must be 0 (gini) or 1 (entropy), got %d", f, fit_criterion[f]);
@@ -360,7 +426,7 @@ extern "C" int psk_forest_fit(psk_ctx *ctx, const float *X, const int32_t *y01, 
             pool += node_cap[t];
         }
     }
-    if (n_export && (!nodes_out || !impurity_out || !leaf_out)) return psk_fail(ctx, PSK_EINVAL, "null buffer");
+    if (n_export && (!nodes_out || !impurity_out || !leaf_out || (COUNTS && !threshold_out))) return psk_fail(ctx, PSK_EINVAL, "null buffer");
     if (pool > node_pool)
         return psk_fail(ctx, PSK_ERANGE, "the exported trees may need %lld node slots (2 x in-bag samples - 1 each), the pool has %lld",
                         (long long)pool, (long long)node_pool);
@@ -375,18 +441,23 @@ extern "C" int psk_forest_fit(psk_ctx *ctx, const float *X, const int32_t *y01, 
     PSK_HIP(ctx, hipSetDevice(ctx->device));
     const int W = (n + 63) / 64;
     FitArr<uint64_t> bits, ymask;
-    if (const int rc = tree_pack_design(ctx, "psk_forest_fit", X, y01, n, p, bits, ymask)) return rc;
+    TreePlanes pl;
+    if constexpr (COUNTS) {
+        if (const int rc = tree_pack_counts(ctx, who, X, y01, n, p, pl, ymask)) return rc;
+    } else {
+        if (const int rc = tree_pack_design(ctx, who, X, y01, n, p, bits, ymask)) return rc;
+    }
 
     const int grid = std::min(n_trees, FOREST_GRID_PER_CU * (ctx->n_cu > 0 ? ctx->n_cu : 256));
     ForestArgs a{};
-    a.lds = forest_lds_layout(W, B, p, &a.cols_in_lds);
+    a.lds = forest_lds_layout(W, B, p, COL_BYTES, &a.cols_in_lds);
     const size_t p_pad = ((size_t)p + 3) & ~(size_t)3;
     FitArr<uint16_t> d_weight;
     FitArr<uint32_t> d_state;
     FitArr<int32_t> d_tree_fit, d_crit, d_depth, d_mf, d_msl, d_mss, d_cap, d_leaf_row, d_count, d_deepest, d_nodes, d_leaf, d_fit_ptr,
         d_fit_tree_ids;
     FitArr<int64_t> d_off;
-    FitArr<double> d_imp, frac0, frac1, sum0, sum1;
+    FitArr<double> d_imp, d_thr, frac0, frac1, sum0, sum1;
     FitArr<ForestRec> d_stack;
     FitArr<char> d_cols;
     PSK_HIP(ctx, d_weight.upload(tree_weight, (size_t)n_trees * n, ctx->stream));
@@ -412,8 +483,11 @@ extern "C" int psk_forest_fit(psk_ctx *ctx, const float *X, const int32_t *y01, 
     PSK_HIP(ctx, sum0.alloc((size_t)n_fits * n));
     PSK_HIP(ctx, sum1.alloc((size_t)n_fits * n));
     PSK_HIP(ctx, d_stack.alloc((size_t)grid * (n + 2)));
-    PSK_HIP(ctx, d_cols.alloc(a.cols_in_lds ? 0 : (size_t)grid * FOREST_COL_BYTES * p_pad));
-    a.bits = bits; a.ymask = ymask;
+    PSK_HIP(ctx, d_cols.alloc(a.cols_in_lds ? 0 : (size_t)grid * COL_BYTES * p_pad));
+    PSK_HIP(ctx, d_thr.alloc(COUNTS ? (size_t)pool : 0));
+    a.bits = COUNTS ? (const uint64_t *)pl.bits : (const uint64_t *)bits; a.ymask = ymask;
+    ForestCountArgs<COUNTS> ca;
+    if constexpr (COUNTS) ca = ForestCountArgs<true>{{pl.x, pl.col_first, pl.plane_col, pl.col_order, pl.plane_val, p}, pl.P, d_thr};
     a.n = n; a.p = p; a.W = W; a.B = B; a.n_trees = n_trees;
     a.tree_weight = d_weight; a.tree_state = d_state; a.tree_fit = d_tree_fit;
     a.fit_crit = d_crit; a.fit_depth = d_depth; a.fit_mf = d_mf; a.fit_msl = d_msl; a.fit_mss = d_mss;
@@ -421,7 +495,7 @@ extern "C" int psk_forest_fit(psk_ctx *ctx, const float *X, const int32_t *y01, 
     a.node_count = d_count; a.depth_out = d_deepest; a.nodes = d_nodes; a.leaf_out = d_leaf;
     a.imp_out = d_imp; a.frac0 = frac0; a.frac1 = frac1;
     a.stack = d_stack; a.cols_global = d_cols;
-    forest_fit_kernel<<<grid, FOREST_THREADS, a.lds.total, ctx->stream>>>(a);
+    forest_fit_kernel<COUNTS><<<grid, FOREST_THREADS, a.lds.total, ctx->stream>>>(a, ca);
     PSK_HIP(ctx, hipGetLastError());
     forest_sum_kernel<<<dim3(div_up(n, 256), n_fits), 256, 0, ctx->stream>>>(frac0, frac1, n, d_fit_ptr, d_fit_tree_ids, sum0, sum1);
     PSK_HIP(ctx, hipGetLastError());
@@ -433,8 +507,44 @@ extern "C" int psk_forest_fit(psk_ctx *ctx, const float *X, const int32_t *y01, 
         PSK_HIP(ctx, d_nodes.download(nodes_out, (size_t)pool * TREE_NODE_FIELDS, ctx->stream));
         PSK_HIP(ctx, d_imp.download(impurity_out, (size_t)pool, ctx->stream));
         PSK_HIP(ctx, d_leaf.download(leaf_out, (size_t)n_export * n, ctx->stream));
+        if (COUNTS) PSK_HIP(ctx, d_thr.download(threshold_out, (size_t)pool, ctx->stream));
     }
     PSK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int t = 0; t < n_trees; t++)
+        if (node_off[t] >= 0)
+            tree_report_impurities(fit_criterion[tree_fit[t]], nodes_out + (size_t)node_off[t] * TREE_NODE_FIELDS,
+                                   std::min(node_count_out[t], node_cap[t]), impurity_out + node_off[t]);
     memcpy(tree_node_off_out, node_off.data(), (size_t)n_trees * sizeof(int64_t));
     return PSK_OK;
+}
+
+}  // namespace
+
+extern "C" int psk_forest_fit(psk_ctx *ctx, const float *X, const int32_t *y01, int n, int p, int n_trees,
+                              const uint16_t *tree_weight, const uint32_t *tree_state, const int32_t *tree_fit,
+                              const int32_t *tree_export, int n_fits, const int32_t *fit_criterion, const int32_t *fit_max_depth,
+                              const int32_t *fit_max_features, const int32_t *fit_min_samples_leaf,
+                              const int32_t *fit_min_samples_split, double *sum0_out, double *sum1_out, int32_t *node_count_out,
+                              int32_t *max_depth_out, int64_t node_pool, int64_t *tree_node_off_out, int32_t *nodes_out,
+                              double *impurity_out, int32_t *leaf_out)
+{
+    return forest_fit_call<false>(ctx, "psk_forest_fit", X, y01, n, p, n_trees, tree_weight, tree_state, tree_fit, tree_export, n_fits,
+                                  fit_criterion, fit_max_depth, fit_max_features, fit_min_samples_leaf, fit_min_samples_split, sum0_out,
+                                  sum1_out, node_count_out, max_depth_out, node_pool, tree_node_off_out, nodes_out, impurity_out, leaf_out,
+                                  nullptr);
+}
+
+extern "C" int psk_forest_fit_counts(psk_ctx *ctx, const float *X, const int32_t *y01, int n, int p, int n_trees,
+                                     const uint16_t *tree_weight, const uint32_t *tree_state, const int32_t *tree_fit,
+                                     const int32_t *tree_export, int n_fits, const int32_t *fit_criterion,
+                                     const int32_t *fit_max_depth, const int32_t *fit_max_features,
+                                     const int32_t *fit_min_samples_leaf, const int32_t *fit_min_samples_split, double *sum0_out,
+                                     double *sum1_out, int32_t *node_count_out, int32_t *max_depth_out, int64_t node_pool,
+                                     int64_t *tree_node_off_out, int32_t *nodes_out, double *impurity_out, int32_t *leaf_out,
+                                     double *threshold_out)
+{
+    return forest_fit_call<true>(ctx, "psk_forest_fit_counts", X, y01, n, p, n_trees, tree_weight, tree_state, tree_fit, tree_export,
+                                 n_fits, fit_criterion, fit_max_depth, fit_max_features, fit_min_samples_leaf, fit_min_samples_split,
+                                 sum0_out, sum1_out, node_count_out, max_depth_out, node_pool, tree_node_off_out, nodes_out, impurity_out,
+                                 leaf_out, threshold_out);
 }

@@ -47,12 +47,16 @@ __device__ __forceinline__ bool tree_better(double v, int i, double bv, int bi) 
 
 struct TreeRec { int parent, depth, is_left, n, n1; double imp; };
 
-template <int CRIT>
+// COUNTS: `bits` holds the P threshold planes of a count design and p is P (solver_tree_common.h), so the scan below is the
+// lowest column, then the lowest threshold; the node record gets the plane's column, thr_out scikit-learn's threshold, and the
+// path the plane that routes by it.
+template <int CRIT, bool COUNTS>
 __device__ void tree_build(const uint64_t *__restrict__ bits, int n, int p, int W, int max_depth, int32_t *__restrict__ nodes,
                            double *__restrict__ imp_out, int32_t *__restrict__ leaf_out, double *__restrict__ frac_out,
                            int32_t *__restrict__ node_count, int32_t *__restrict__ depth_out,
                            uint64_t (*mask)[TREE_MAX_W], const uint64_t *T, const uint64_t *Y, uint64_t *MT, uint64_t *MTY,
-                           TreeRec *stack, int *path_feat, double *red_v, int *red_i, int *red_c)
+                           TreeRec *stack, int *path_feat, double *red_v, int *red_i, int *red_c, const TreePlaneView<COUNTS> &pv,
+                           double *__restrict__ thr_out)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int n_tot = 0, n1_tot = 0;
@@ -124,6 +128,17 @@ __device__ void tree_build(const uint64_t *__restrict__ bits, int n, int p, int 
         }
         const int id = next_id++;
         deepest = max(deepest, d);
+        int route = feat;
+        if constexpr (COUNTS) {
+            double thr = -2.0;
+            if (!is_leaf) {
+                const int col = pv.plane_col[feat];
+                thr = tree_node_threshold(pv.X, n, pv.p, col, pv.plane_val[feat], MT, red_i);
+                route = tree_route_plane(pv.col_first, pv.plane_val, col, thr);
+                feat = col;
+            }
+            if (tid == 0) thr_out[id] = thr;
+        }
         if (tid == 0) tree_write_node(nodes, imp_out, id, rec.parent, rec.is_left, feat, is_leaf, rec.n, rec.n - rec.n1, rec.n1, rec.imp);
         if (is_leaf) {
             const double f1 = c1n / nn;
@@ -132,7 +147,7 @@ __device__ void tree_build(const uint64_t *__restrict__ bits, int n, int p, int 
         } else {
             // (the barrier of the reduction lies between every thread's read of `rec` and these writes)
             if (tid == 0) {
-                path_feat[d] = feat;
+                path_feat[d] = route;
                 stack[sp] = TreeRec{id, d + 1, 0, cr, cr1, imp_r};
                 stack[sp + 1] = TreeRec{id, d + 1, 1, rec.n - cr, rec.n1 - cr1, imp_l};
             }
@@ -142,11 +157,13 @@ __device__ void tree_build(const uint64_t *__restrict__ bits, int n, int p, int 
     if (tid == 0) { *node_count = next_id; *depth_out = deepest; }
 }
 
+template <bool COUNTS>
 __global__ __launch_bounds__(TREE_THREADS) void tree_fit_kernel(
     const uint64_t *__restrict__ bits, const uint64_t *__restrict__ ymask, const int32_t *__restrict__ fold, int n, int p, int W,
     const int32_t *__restrict__ fit_max_depth, const int32_t *__restrict__ fit_criterion, const int32_t *__restrict__ fit_fold,
     int32_t *__restrict__ node_count, int32_t *__restrict__ depth_out, int32_t *__restrict__ nodes, double *__restrict__ imp_out,
-    int32_t *__restrict__ leaf_out, double *__restrict__ frac_out, const int32_t *__restrict__ fit_off)
+    int32_t *__restrict__ leaf_out, double *__restrict__ frac_out, const int32_t *__restrict__ fit_off, const TreePlaneView<COUNTS> pv,
+    double *__restrict__ thr_out)
 {
     __shared__ uint64_t mask[TREE_MAX_DEPTH + 1][TREE_MAX_W];
     __shared__ uint64_t T[TREE_MAX_W], Y[TREE_MAX_W], MT[TREE_MAX_W], MTY[TREE_MAX_W];
@@ -172,28 +189,29 @@ __global__ __launch_bounds__(TREE_THREADS) void tree_fit_kernel(
     double *io = imp_out + (size_t)fit_off[fit];
     int32_t *lo = leaf_out + (size_t)fit * n;
     double *fo = frac_out + (size_t)fit * n;
+    double *to = COUNTS ? thr_out + (size_t)fit_off[fit] : nullptr;
     if (fit_criterion[fit] == 0)
-        tree_build<0>(bits, n, p, W, fit_max_depth[fit], nd, io, lo, fo, node_count + fit, depth_out + fit, mask, T, Y, MT, MTY,
-                      stack, path_feat, red_v, red_i, red_c);
+        tree_build<0, COUNTS>(bits, n, p, W, fit_max_depth[fit], nd, io, lo, fo, node_count + fit, depth_out + fit, mask, T, Y, MT, MTY,
+                              stack, path_feat, red_v, red_i, red_c, pv, to);
     else
-        tree_build<1>(bits, n, p, W, fit_max_depth[fit], nd, io, lo, fo, node_count + fit, depth_out + fit, mask, T, Y, MT, MTY,
-                      stack, path_feat, red_v, red_i, red_c);
+        tree_build<1, COUNTS>(bits, n, p, W, fit_max_depth[fit], nd, io, lo, fo, node_count + fit, depth_out + fit, mask, T, Y, MT, MTY,
+                              stack, path_feat, red_v, red_i, red_c, pv, to);
 }
 
-}  // namespace
-
-extern "C" int psk_tree_fit(psk_ctx *ctx, const float *X, const int32_t *y01, int n, int p, const int32_t *fold,
-                            const int32_t *fit_max_depth, const int32_t *fit_criterion, const int32_t *fit_fold, int n_fits,
-                            int32_t *node_count_out, int32_t *max_depth_out, int32_t *nodes_out, double *impurity_out,
-                            int32_t *leaf_out, double *frac_out)
+// psk_tree_fit (COUNTS false: threshold_out unused) and psk_tree_fit_counts; `who` names the entry point in messages
+template <bool COUNTS>
+int tree_fit_call(psk_ctx *ctx, const char *who, const float *X, const int32_t *y01, int n, int p, const int32_t *fold,
+                  const int32_t *fit_max_depth, const int32_t *fit_criterion, const int32_t *fit_fold, int n_fits,
+                  int32_t *node_count_out, int32_t *max_depth_out, int32_t *nodes_out, double *impurity_out, int32_t *leaf_out,
+                  double *frac_out, double *threshold_out)
 {
     if (!ctx) return PSK_EINVAL;
     if (!X || !y01 || !fold || !fit_max_depth || !fit_criterion || !fit_fold || !node_count_out || !max_depth_out || !nodes_out ||
-        !impurity_out || !leaf_out || !frac_out)
+        !impurity_out || !leaf_out || !frac_out || (COUNTS && !threshold_out))
         return psk_fail(ctx, PSK_EINVAL, "null buffer");
     if (n < 1 || p < 1 || n_fits < 1) return psk_fail(ctx, PSK_EINVAL, "bad problem shape n=%d p=%d fits=%d", n, p, n_fits);
     if (n > TREE_MAX_N)
-        return psk_fail(ctx, PSK_ERANGE, "psk_tree_fit keeps a node's sample mask in LDS: at most %d samples, got %d", TREE_MAX_N, n);
+        return psk_fail(ctx, PSK_ERANGE, "%s keeps a node's sample mask in LDS: at most %d samples, got %d", who, TREE_MAX_N, n);
     for (int f = 0; f < n_fits; f++) {
         if (fit_max_depth[f] < 1 || fit_max_depth[f] > TREE_MAX_DEPTH)
             return psk_fail(ctx, PSK_EINVAL, "fit %d: max_depth must be 1..%d, got %d", f, TREE_MAX_DEPTH, fit_max_depth[f]);
@@ -208,8 +226,15 @@ extern "C" int psk_tree_fit(psk_ctx *ctx, const float *X, const int32_t *y01, in
     const int W = (n + 63) / 64;
     FitArr<uint64_t> bits, ymask;
     FitArr<int32_t> d_fold, depth, crit, d_fit_fold, d_off, count, dout, d_nodes, leaf;
-    FitArr<double> d_imp, frac;
-    if (const int rc = tree_pack_design(ctx, "psk_tree_fit", X, y01, n, p, bits, ymask)) return rc;
+    FitArr<double> d_imp, frac, d_thr;
+    TreePlanes pl;
+    TreePlaneView<COUNTS> pv;
+    if constexpr (COUNTS) {
+        if (const int rc = tree_pack_counts(ctx, who, X, y01, n, p, pl, ymask)) return rc;
+        pv = TreePlaneView<true>{pl.x, pl.col_first, pl.plane_col, pl.col_order, pl.plane_val, p};
+    } else {
+        if (const int rc = tree_pack_design(ctx, who, X, y01, n, p, bits, ymask)) return rc;
+    }
 
     // a tree of max_depth d has at most 2^(d+1) - 1 nodes: fit f's nodes start at off[f] of one packed buffer (a depth-1 fit
     // takes 3 slots, not PSK_TREE_NODE_CAP), and only the node_count[f] nodes it made go back into the caller's strided arrays
@@ -227,11 +252,16 @@ extern "C" int psk_tree_fit(psk_ctx *ctx, const float *X, const int32_t *y01, in
     PSK_HIP(ctx, d_imp.alloc(total));
     PSK_HIP(ctx, leaf.alloc((size_t)n_fits * n));
     PSK_HIP(ctx, frac.alloc((size_t)n_fits * n));
-    tree_fit_kernel<<<n_fits, TREE_THREADS, 0, ctx->stream>>>(bits, ymask, d_fold, n, p, W, depth, crit, d_fit_fold, count, dout, d_nodes,
-                                                              d_imp, leaf, frac, d_off);
+    PSK_HIP(ctx, d_thr.alloc(COUNTS ? total : 0));
+    // (the count kernel scans the P planes where the 0/1 kernel scans the p columns)
+    const uint64_t *d_bits = COUNTS ? (const uint64_t *)pl.bits : (const uint64_t *)bits;
+    tree_fit_kernel<COUNTS><<<n_fits, TREE_THREADS, 0, ctx->stream>>>(d_bits, ymask, d_fold, n, COUNTS ? pl.P : p, W, depth,
+                                                                      crit, d_fit_fold, count, dout, d_nodes, d_imp, leaf, frac, d_off,
+                                                                      pv, d_thr);
     PSK_HIP(ctx, hipGetLastError());
     std::vector<int32_t> nodes(total * TREE_NODE_FIELDS);
-    std::vector<double> imp(total);
+    std::vector<double> imp(total), thr(COUNTS ? total : 0);
+    if (COUNTS) PSK_HIP(ctx, d_thr.download(thr.data(), thr.size(), ctx->stream));
     PSK_HIP(ctx, count.download(node_count_out, n_fits, ctx->stream));
     PSK_HIP(ctx, dout.download(max_depth_out, n_fits, ctx->stream));
     PSK_HIP(ctx, d_nodes.download(nodes.data(), nodes.size(), ctx->stream));
@@ -241,9 +271,31 @@ extern "C" int psk_tree_fit(psk_ctx *ctx, const float *X, const int32_t *y01, in
     PSK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (int f = 0; f < n_fits; f++) {
         const size_t k = (size_t)node_count_out[f];
+        tree_report_impurities(fit_criterion[f], nodes.data() + (size_t)off[f] * TREE_NODE_FIELDS, (int)k, imp.data() + off[f]);
         memcpy(nodes_out + (size_t)f * PSK_TREE_NODE_CAP * TREE_NODE_FIELDS, nodes.data() + (size_t)off[f] * TREE_NODE_FIELDS,
                k * TREE_NODE_FIELDS * 4);
         memcpy(impurity_out + (size_t)f * PSK_TREE_NODE_CAP, imp.data() + off[f], k * 8);
+        if (COUNTS) memcpy(threshold_out + (size_t)f * PSK_TREE_NODE_CAP, thr.data() + off[f], k * 8);
     }
     return PSK_OK;
+}
+
+}  // namespace
+
+extern "C" int psk_tree_fit(psk_ctx *ctx, const float *X, const int32_t *y01, int n, int p, const int32_t *fold,
+                            const int32_t *fit_max_depth, const int32_t *fit_criterion, const int32_t *fit_fold, int n_fits,
+                            int32_t *node_count_out, int32_t *max_depth_out, int32_t *nodes_out, double *impurity_out,
+                            int32_t *leaf_out, double *frac_out)
+{
+    return tree_fit_call<false>(ctx, "psk_tree_fit", X, y01, n, p, fold, fit_max_depth, fit_criterion, fit_fold, n_fits, node_count_out,
+                                max_depth_out, nodes_out, impurity_out, leaf_out, frac_out, nullptr);
+}
+
+extern "C" int psk_tree_fit_counts(psk_ctx *ctx, const float *X, const int32_t *y01, int n, int p, const int32_t *fold,
+                                   const int32_t *fit_max_depth, const int32_t *fit_criterion, const int32_t *fit_fold, int n_fits,
+                                   int32_t *node_count_out, int32_t *max_depth_out, int32_t *nodes_out, double *impurity_out,
+                                   int32_t *leaf_out, double *frac_out, double *threshold_out)
+{
+    return tree_fit_call<true>(ctx, "psk_tree_fit_counts", X, y01, n, p, fold, fit_max_depth, fit_criterion, fit_fold, n_fits,
+                               node_count_out, max_depth_out, nodes_out, impurity_out, leaf_out, frac_out, threshold_out);
 }

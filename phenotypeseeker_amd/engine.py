@@ -452,20 +452,43 @@ class PskContext:
 
     TREE_NODE_CAP = 2047      # PSK_TREE_NODE_CAP of include/psk.h
 
+    COUNT_MAX = 1 << 24       # the largest value of a count design (include/psk.h, f9)
+
     @staticmethod
-    def _tree_dict(nodes, impurity, max_depth, leaf):
+    def _tree_dict(nodes, impurity, max_depth, leaf, threshold=None):
         """nodes[k][6] (feature, left, right, n_node_samples, the two class counts), impurity[k] by node in pre-order,
-        the tree's depth and leaf[n], every sample's leaf, as the dictionary tree_fit and forest_fit return per tree."""
-        return dict(node_count=len(nodes), max_depth=int(max_depth), feature=nodes[:, 0].astype(np.int64), left=nodes[:, 1].astype(np.int64),
-                    right=nodes[:, 2].astype(np.int64), n_node_samples=nodes[:, 3].astype(np.int64), counts=nodes[:, 4:6].astype(np.int64),
-                    impurity=impurity.copy(), leaf=leaf.astype(np.int64))
+        the tree's depth and leaf[n], every sample's leaf, as the dictionary tree_fit and forest_fit return per tree; the
+        count calls add threshold[k]."""
+        d = dict(node_count=len(nodes), max_depth=int(max_depth), feature=nodes[:, 0].astype(np.int64), left=nodes[:, 1].astype(np.int64),
+                 right=nodes[:, 2].astype(np.int64), n_node_samples=nodes[:, 3].astype(np.int64), counts=nodes[:, 4:6].astype(np.int64),
+                 impurity=impurity.copy(), leaf=leaf.astype(np.int64))
+        if threshold is not None:
+            d["threshold"] = threshold.copy()
+        return d
+
+    @classmethod
+    def _count_design(cls, X, who):
+        """The float32 design of the count calls.  The range is checked on the float64 values: the cast would round
+        2^24 + 1 to 2^24 and hide it."""
+        X = np.asarray(X, dtype=np.float64)
+        if X.ndim != 2 or not np.all((X >= 0) & (X <= cls.COUNT_MAX) & (X == np.floor(X))):    # (a NaN fails every comparison)
+            raise ValueError("%s takes a count design: every value must be an integer in 0 .. 2^24" % who)
+        return np.ascontiguousarray(X, dtype=np.float32)
 
     def tree_fit(self, X, y01, fold, fit_max_depth, fit_criterion, fit_fold):
         """Decision-tree fits (psk_tree_fit): scikit-learn's depth-first best-split builder on a 0/1 design, one workgroup
         per fit, the lowest column index among equally good splits.  fit_criterion: 0 / 'gini', 1 / 'entropy'.  Returns a
         list with one dict per fit: node_count, max_depth, feature / left / right / n_node_samples / counts[:, 2] /
         impurity by node (pre-order), and leaf[n], frac[n]: every sample's leaf and that leaf's class-1 fraction."""
-        X = np.ascontiguousarray(X, dtype=np.float32)
+        return self._tree_fit(False, np.ascontiguousarray(X, dtype=np.float32), y01, fold, fit_max_depth, fit_criterion, fit_fold)
+
+    def tree_fit_counts(self, X, y01, fold, fit_max_depth, fit_criterion, fit_fold):
+        """tree_fit on a count design (psk_tree_fit_counts): integers in 0 .. 2^24, ValueError otherwise.  The same dicts
+        plus threshold by node: scikit-learn's midpoint between the two values around the split among the node's training
+        samples, -2 at a leaf; x <= threshold goes left."""
+        return self._tree_fit(True, self._count_design(X, "tree_fit_counts"), y01, fold, fit_max_depth, fit_criterion, fit_fold)
+
+    def _tree_fit(self, counts, X, y01, fold, fit_max_depth, fit_criterion, fit_fold):
         n, p = X.shape
         y = np.ascontiguousarray(y01, dtype=np.int32)
         fold = np.ascontiguousarray(fold, dtype=np.int32)
@@ -476,10 +499,15 @@ class PskContext:
         count, deepest = np.zeros(nf, dtype=np.int32), np.zeros(nf, dtype=np.int32)
         nodes, imp = np.zeros((nf, cap, 6), dtype=np.int32), np.zeros((nf, cap))
         leaf, frac = np.zeros((nf, n), dtype=np.int32), np.zeros((nf, n))
-        self._check(self._lib.psk_tree_fit(self._h, _ptr(X), _ptr(y), n, p, _ptr(fold), _ptr(depth), _ptr(crit), _ptr(fit_fold),
-                                           nf, _ptr(count), _ptr(deepest), _ptr(nodes), _ptr(imp), _ptr(leaf), _ptr(frac)),
-                    "psk_tree_fit")
-        return [dict(self._tree_dict(nodes[j, :count[j]], imp[j, :count[j]], deepest[j], leaf[j]), frac=frac[j].copy()) for j in range(nf)]
+        args = (self._h, _ptr(X), _ptr(y), n, p, _ptr(fold), _ptr(depth), _ptr(crit), _ptr(fit_fold), nf, _ptr(count), _ptr(deepest),
+                _ptr(nodes), _ptr(imp), _ptr(leaf), _ptr(frac))
+        if not counts:
+            self._check(self._lib.psk_tree_fit(*args), "psk_tree_fit")
+            return [dict(self._tree_dict(nodes[j, :count[j]], imp[j, :count[j]], deepest[j], leaf[j]), frac=frac[j].copy()) for j in range(nf)]
+        thr = np.zeros((nf, cap))
+        self._check(self._lib.psk_tree_fit_counts(*args, _ptr(thr)), "psk_tree_fit_counts")
+        return [dict(self._tree_dict(nodes[j, :count[j]], imp[j, :count[j]], deepest[j], leaf[j], thr[j, :count[j]]), frac=frac[j].copy())
+                for j in range(nf)]
 
     def forest_fit(self, X, y01, tree_weight, tree_state, tree_fit, fit_criterion, fit_max_depth, fit_max_features,
                    fit_min_samples_leaf, fit_min_samples_split, export=None):
@@ -490,7 +518,18 @@ class PskContext:
         export[n_trees]: which trees' node arrays to return (None: all).  Returns (sum0[n_fits][n], sum1[n_fits][n], trees):
         the two class fractions of every sample's leaves added in tree order, and per tree None or a dict of node_count,
         max_depth, feature / left / right / n_node_samples / counts[:, 2] (weighted) / impurity by node (pre-order), leaf[n]."""
-        X = np.ascontiguousarray(X, dtype=np.float32)
+        return self._forest_fit(False, np.ascontiguousarray(X, dtype=np.float32), y01, tree_weight, tree_state, tree_fit, fit_criterion,
+                                fit_max_depth, fit_max_features, fit_min_samples_leaf, fit_min_samples_split, export)
+
+    def forest_fit_counts(self, X, y01, tree_weight, tree_state, tree_fit, fit_criterion, fit_max_depth, fit_max_features,
+                          fit_min_samples_leaf, fit_min_samples_split, export=None):
+        """forest_fit on a count design (psk_forest_fit_counts): integers in 0 .. 2^24, ValueError otherwise.  The same
+        results, every tree's dict with threshold by node as tree_fit_counts returns it."""
+        return self._forest_fit(True, self._count_design(X, "forest_fit_counts"), y01, tree_weight, tree_state, tree_fit, fit_criterion,
+                                fit_max_depth, fit_max_features, fit_min_samples_leaf, fit_min_samples_split, export)
+
+    def _forest_fit(self, counts, X, y01, tree_weight, tree_state, tree_fit, fit_criterion, fit_max_depth, fit_max_features,
+                    fit_min_samples_leaf, fit_min_samples_split, export):
         n, p = X.shape
         y = np.ascontiguousarray(y01, dtype=np.int32)
         wt = np.asarray(tree_weight)
@@ -514,17 +553,20 @@ class PskContext:
         sum0, sum1 = np.zeros((nf, n)), np.zeros((nf, n))
         count, deepest, off = np.zeros(nt, dtype=np.int32), np.zeros(nt, dtype=np.int32), np.zeros(nt, dtype=np.int64)
         nodes, imp, leaf = np.zeros((max(pool, 1), 6), dtype=np.int32), np.zeros(max(pool, 1)), np.zeros((max(n_exp, 1), n), dtype=np.int32)
-        self._check(self._lib.psk_forest_fit(self._h, _ptr(X), _ptr(y), n, p, nt, _ptr(wt), _ptr(state), _ptr(tfit), _ptr(flag), nf,
-                                             _ptr(crit), _ptr(depth), _ptr(mf), _ptr(msl), _ptr(mss), _ptr(sum0), _ptr(sum1),
-                                             _ptr(count), _ptr(deepest), pool, _ptr(off), _ptr(nodes), _ptr(imp), _ptr(leaf)),
-                    "psk_forest_fit")
+        args = (self._h, _ptr(X), _ptr(y), n, p, nt, _ptr(wt), _ptr(state), _ptr(tfit), _ptr(flag), nf, _ptr(crit), _ptr(depth), _ptr(mf),
+                _ptr(msl), _ptr(mss), _ptr(sum0), _ptr(sum1), _ptr(count), _ptr(deepest), pool, _ptr(off), _ptr(nodes), _ptr(imp), _ptr(leaf))
+        thr = np.zeros(max(pool, 1)) if counts else None
+        if counts:
+            self._check(self._lib.psk_forest_fit_counts(*args, _ptr(thr)), "psk_forest_fit_counts")
+        else:
+            self._check(self._lib.psk_forest_fit(*args), "psk_forest_fit")
         trees, row = [], 0
         for t in range(nt):
             if not flag[t]:
                 trees.append(None)
                 continue
             a, k = int(off[t]), int(count[t])
-            trees.append(self._tree_dict(nodes[a:a + k], imp[a:a + k], deepest[t], leaf[row]))
+            trees.append(self._tree_dict(nodes[a:a + k], imp[a:a + k], deepest[t], leaf[row], thr[a:a + k] if counts else None))
             row += 1
         return sum0, sum1, trees
 

@@ -1,5 +1,6 @@
 """The tree estimators on a 0/1 design: DecisionTree over psk_tree_fit, RandomForest over psk_forest_fit with everything
-scikit-learn draws from NumPy's RandomState drawn on the host (ForestDraws)."""
+scikit-learn draws from NumPy's RandomState drawn on the host (ForestDraws).  With counts=True they take a design of k-mer
+counts through psk_tree_fit_counts / psk_forest_fit_counts and their trees carry scikit-learn's thresholds."""
 import numpy as np
 
 from .model_search import _Estimator, _Twin, _fold_scores, _launch_plan
@@ -11,9 +12,11 @@ class Tree:
     pre-order, threshold 0.5 at a split and -2 at a leaf, value the class fractions ([node_count][1][2], scikit-learn >= 1.3)."""
     n_outputs, max_n_classes = 1, 2
 
-    def __init__(self, n_features, feature, left, right, n_node_samples, counts, impurity, max_depth, weighted_n_node_samples=None):
+    def __init__(self, n_features, feature, left, right, n_node_samples, counts, impurity, max_depth, weighted_n_node_samples=None,
+                 threshold=None):
         """counts: the class counts by node; in a forest's tree they are weighted (bootstrap multiplicities) and
-        weighted_n_node_samples is their sum, while n_node_samples counts the distinct samples."""
+        weighted_n_node_samples is their sum, while n_node_samples counts the distinct samples.  threshold: by node, for a tree
+        on a count design."""
         self.n_features = int(n_features)
         self.n_classes = np.array([2], dtype=np.int64)
         self.feature = np.asarray(feature, dtype=np.int64)
@@ -22,7 +25,7 @@ class Tree:
         self.weighted_n_node_samples = (self.n_node_samples.astype(np.float64) if weighted_n_node_samples is None
                                         else np.asarray(weighted_n_node_samples, dtype=np.float64))
         self.impurity = np.asarray(impurity, dtype=np.float64)
-        self.threshold = np.where(self.feature >= 0, 0.5, -2.0)
+        self.threshold = np.where(self.feature >= 0, 0.5, -2.0) if threshold is None else np.asarray(threshold, dtype=np.float64)
         self.value = (np.asarray(counts, dtype=np.float64) / self.weighted_n_node_samples[:, None]).reshape(-1, 1, 2)
         self.missing_go_to_left = np.zeros(len(self.feature), dtype=np.uint8)
         self.node_count, self.max_depth = len(self.feature), int(max_depth)
@@ -86,14 +89,16 @@ class DecisionTree(_Estimator):
     """sklearn.tree.DecisionTreeClassifier for two classes on a 0/1 design (set_model, modeling.py:1032-1033:
     DecisionTreeClassifier() under {'max_depth': 1..10, 'criterion': ['gini', 'entropy']}) over psk_tree_fit:
     scikit-learn's depth-first best-split builder with its default settings.  scikit-learn breaks ties between equally good
-    splits by an unseeded random feature order; here the lowest column index wins."""
+    splits by an unseeded random feature order; here the lowest column index wins.  counts: the design
+    holds k-mer counts (psk_tree_fit_counts); a switch of the engine, not a parameter of scikit-learn's: neither the repr nor
+    the exported parameters show it."""
     _is_classifier = True
     MAX_DEPTH = 10
 
-    def __init__(self, criterion="gini", max_depth=None):
+    def __init__(self, criterion="gini", max_depth=None, counts=False):
         if criterion not in ("gini", "entropy"):
             raise ValueError("DecisionTree: criterion must be 'gini' or 'entropy', got %r" % (criterion,))
-        self.criterion, self.max_depth = criterion, max_depth
+        self.criterion, self.max_depth, self.counts = criterion, max_depth, bool(counts)
         self.classes_ = np.array([0, 1])
         self.tree_ = None
 
@@ -106,7 +111,7 @@ class DecisionTree(_Estimator):
         return "DecisionTreeClassifier(%s)" % ", ".join(parts)
 
     def _clone(self, **params):
-        kw = dict(criterion=self.criterion, max_depth=self.max_depth)
+        kw = dict(criterion=self.criterion, max_depth=self.max_depth, counts=self.counts)
         kw.update(params)
         return type(self)(**kw)
 
@@ -123,7 +128,8 @@ class DecisionTree(_Estimator):
         for c in crit:
             if c not in ("gini", "entropy"):
                 raise ValueError("DecisionTree: criterion must be 'gini' or 'entropy', got %r" % (c,))
-        return ctx.tree_fit(X, y.astype(np.int32), folds, [int(dp) for dp in depth], crit, fit_fold)
+        engine_fit = ctx.tree_fit_counts if self.counts else ctx.tree_fit
+        return engine_fit(X, y.astype(np.int32), folds, [int(dp) for dp in depth], crit, fit_fold)
 
     def fit(self, X, y, engine_ctx):
         X = np.asarray(X, dtype=np.float64)
@@ -132,7 +138,7 @@ class DecisionTree(_Estimator):
 
     def _set_fit(self, fit, n_features):
         self.tree_ = Tree(n_features, fit["feature"], fit["left"], fit["right"], fit["n_node_samples"], fit["counts"],
-                          fit["impurity"], fit["max_depth"])
+                          fit["impurity"], fit["max_depth"], threshold=fit.get("threshold"))
         self.n_features_in_ = int(n_features)
         self.n_outputs_, self.n_classes_, self.max_features_ = 1, np.int64(2), int(n_features)
         return self
@@ -244,14 +250,16 @@ class ForestTree(DecisionTree):
     """One tree of a RandomForest: a DecisionTree whose tree_ carries weighted class counts (model.Tree with
     weighted_n_node_samples) and which, as in scikit-learn, knows its own seed and the forest's parameters."""
 
-    def __init__(self, criterion="gini", max_depth=None, min_samples_split=2, min_samples_leaf=1, max_features="sqrt", random_state=None):
-        super().__init__(criterion, max_depth)
+    def __init__(self, criterion="gini", max_depth=None, min_samples_split=2, min_samples_leaf=1, max_features="sqrt", random_state=None,
+                 counts=False):
+        super().__init__(criterion, max_depth, counts)
         self.min_samples_split, self.min_samples_leaf, self.max_features, self.random_state = (
             min_samples_split, min_samples_leaf, max_features, random_state)
 
     def _set_fit(self, fit, n_features):
         self.tree_ = Tree(n_features, fit["feature"], fit["left"], fit["right"], fit["n_node_samples"], fit["counts"],
-                          fit["impurity"], fit["max_depth"], weighted_n_node_samples=np.asarray(fit["counts"]).sum(axis=1))
+                          fit["impurity"], fit["max_depth"], weighted_n_node_samples=np.asarray(fit["counts"]).sum(axis=1),
+                          threshold=fit.get("threshold"))
         self.n_features_in_ = int(n_features)
         self.n_outputs_, self.n_classes_ = 1, np.int64(2)
         self.max_features_ = RandomForest.n_max_features(self.max_features, n_features)
@@ -269,7 +277,8 @@ class ForestTree(DecisionTree):
 class RandomForest(_Estimator):
     """sklearn.ensemble.RandomForestClassifier for two classes on a 0/1 design (set_model, modeling.py:1030-1031) over
     psk_forest_fit: for an integer random_state, scikit-learn 1.7.2's forest to the node.  The seven
-    parameters of the reference's grid plus random_state; everything else at scikit-learn's defaults."""
+    parameters of the reference's grid plus random_state; everything else at scikit-learn's defaults.  counts: the design
+    holds k-mer counts (psk_forest_fit_counts), the engine switch of DecisionTree."""
     _is_classifier = True
     _randomized = True        # the reference searches its forest with RandomizedSearchCV (modeling.py:1096-1099)
     PARAMS = ("bootstrap", "criterion", "max_depth", "max_features", "min_samples_leaf", "min_samples_split", "n_estimators")
@@ -280,10 +289,10 @@ class RandomForest(_Estimator):
     SCRATCH_BYTES = 1 << 30   # per engine call: 16 bytes per tree and sample of leaf fractions
 
     def __init__(self, n_estimators=100, criterion="gini", max_depth=None, min_samples_split=2, min_samples_leaf=1,
-                 max_features="sqrt", bootstrap=True, random_state=0):
+                 max_features="sqrt", bootstrap=True, random_state=0, counts=False):
         self.n_estimators, self.criterion, self.max_depth = n_estimators, criterion, max_depth
         self.min_samples_split, self.min_samples_leaf, self.max_features = min_samples_split, min_samples_leaf, max_features
-        self.bootstrap, self.random_state = bootstrap, random_state
+        self.bootstrap, self.random_state, self.counts = bootstrap, random_state, bool(counts)
         self._check(self.get_params())
         self.classes_ = np.array([0, 1])
         self.estimators_ = None
@@ -309,7 +318,7 @@ class RandomForest(_Estimator):
         return _sk_repr("RandomForestClassifier", parts)
 
     def _clone(self, **params):
-        kw = dict(self.get_params(), random_state=self.random_state)
+        kw = dict(self.get_params(), random_state=self.random_state, counts=self.counts)
         kw.update(params)
         return type(self)(**kw)
 
@@ -349,10 +358,11 @@ class RandomForest(_Estimator):
                     weight.append(draws.weight(t, rows_key, rows, bool(q["bootstrap"])))
                     tree_fit.append(f - at)
             chunk = params[at:end]
-            s0, s1, trees = ctx.forest_fit(X, y.astype(np.int32), np.array(weight), state, tree_fit, [q["criterion"] for q in chunk],
-                                           [q["max_depth"] for q in chunk], [self.n_max_features(q["max_features"], p) for q in chunk],
-                                           [int(q["min_samples_leaf"]) for q in chunk], [int(q["min_samples_split"]) for q in chunk],
-                                           export=np.full(len(state), bool(export)))
+            engine_fit = ctx.forest_fit_counts if self.counts else ctx.forest_fit
+            s0, s1, trees = engine_fit(X, y.astype(np.int32), np.array(weight), state, tree_fit, [q["criterion"] for q in chunk],
+                                       [q["max_depth"] for q in chunk], [self.n_max_features(q["max_features"], p) for q in chunk],
+                                       [int(q["min_samples_leaf"]) for q in chunk], [int(q["min_samples_split"]) for q in chunk],
+                                       export=np.full(len(state), bool(export)))
             k = 0
             for f, q in enumerate(chunk):
                 T = int(q["n_estimators"])
@@ -368,7 +378,7 @@ class RandomForest(_Estimator):
 
     def _set_fit(self, trees, draws, n_features, n_samples):
         self.estimators_ = [ForestTree(self.criterion, self.max_depth, self.min_samples_split, self.min_samples_leaf, self.max_features,
-                                       draws.seeds[t])._set_fit(fit, n_features) for t, fit in enumerate(trees)]
+                                       draws.seeds[t], self.counts)._set_fit(fit, n_features) for t, fit in enumerate(trees)]
         self.n_features_in_, self._n_samples = int(n_features), int(n_samples)
         return self
 

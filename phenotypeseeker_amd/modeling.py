@@ -384,8 +384,9 @@ class Input:
                 phenotypes.model_name_long, phenotypes.model_name_short = "support vector machine", "SVM"
             elif binary_classifier == "DT" and _lib.env_flag("PSK_DT"):
                 # set_model (:1032-1033, :1069-1073): DecisionTreeClassifier() over max_depth 1..10 x {gini, entropy}.  The tree
-                # kernel works on the bit-packed presence matrix: k-mer counts and principal components are not 0/1
-                if real_counts:
+                # kernel works on the bit-packed presence matrix: principal components are not 0/1, and k-mer counts go through
+                # the count entry point only with PSK_TREE_COUNTS (docs/KNOBS.md; the reference fits the tree on the counts)
+                if real_counts and not _lib.env_flag("PSK_TREE_COUNTS"):
                     raise SystemExit("The decision tree on the GPU engine takes the 0/1 presence matrix only: "
                                      "--real_counts is not supported with -bc DT.")
                 if pca:
@@ -396,7 +397,7 @@ class Input:
             elif binary_classifier == "RF" and _lib.env_flag("PSK_RF"):
                 # set_model (:1030-1031, :1057-1068) under get_best_model's RandomizedSearchCV(n_iter, cv) (:1096-1099).  The
                 # reference leaves every draw unseeded; here the seed is PSK_RF_SEED and the run is scikit-learn's for that seed
-                if real_counts:
+                if real_counts and not _lib.env_flag("PSK_TREE_COUNTS"):
                     raise SystemExit("The random forest on the GPU engine takes the 0/1 presence matrix only: "
                                      "--real_counts is not supported with -bc RF.")
                 if pca:
@@ -732,9 +733,9 @@ class phenotypes:
             grid = [1.0 / a for a in self.alphas]
             if self.binary_classifier == "DT":
                 # (a grid of two parameters goes to GridSearch as a dictionary, in the reference's own spelling, :1069-1073)
-                return DecisionTree(), {"max_depth": [1, 2, 3, 4, 5, 6, 7, 8, 9, 10], "criterion": ["gini", "entropy"]}, None
+                return DecisionTree(counts=bool(self.real_counts)), {"max_depth": [1, 2, 3, 4, 5, 6, 7, 8, 9, 10], "criterion": ["gini", "entropy"]}, None
             if self.binary_classifier == "RF":
-                return RandomForest(random_state=self.rf_seed), {k: list(v) for k, v in RF_GRID.items()}, None
+                return RandomForest(random_state=self.rf_seed, counts=bool(self.real_counts)), {k: list(v) for k, v in RF_GRID.items()}, None
             if self.binary_classifier == "NB":
                 return BernoulliNB(), None, None
             if self.binary_classifier == "SVM":
