@@ -485,6 +485,43 @@ int psk_nb_fit(psk_ctx *ctx, const float *X, const int32_t *y01, int n, int p, c
 int psk_nb_jll(psk_ctx *ctx, const float *X, int n, int p, const double *delta, int n_models,
                const double *class_log_prior, const double *neg_sum, double *jll_out);
 
+/* ---- f11: `--pca`: principal components of the selected k-mers ---------------------------------------
+ * PCA_analysis (modeling.py:1147-1206) runs StandardScaler().fit/transform and PCA().fit/transform on the k-mer columns;
+ * prediction applies scaler.transform, pca_model.transform and [:, PCs_to_keep] (prediction.py:131-163).  The REFERENCE CANNOT
+ * COMPLETE `--pca`: PCA_analysis calls self.t_test (:1184), which does not exist.  The yardstick is therefore scikit-learn
+ * 1.7.2's StandardScaler() and PCA() with their defaults, which end in svd_flip(u_based_decision=False) (csrc/pca.hip).
+ * All arithmetic is f64; both results are pure functions of the arguments (two calls give the same bits).
+ *
+ * psk_pca_fit: X[n][p] row-major, presence 0/1 or counts.  2 <= n <= 4096 (PSK_EINVAL below, PSK_ERANGE above), p >= 1,
+ * 1 <= n_comp <= min(n, p) (PSK_EINVAL); a non-finite entry of X is PSK_EINVAL.
+ *   mean_out[p]                column sum / n
+ *   var_out[p]                 population variance (ddof 0): (sum_i (x - mean)^2) / n
+ *   scale_out[p]               sqrt(var); 1 for a column that is constant over the samples (var 0)
+ *   lambda_out[min(n, p)]      eigenvalues of Z Z', Z = (X - mean) / scale: the squared singular values of Z, descending,
+ *                              clamped at 0
+ *   scores_out[n][n_comp]      U S of the leading n_comp components
+ *   components_out[n_comp][p]  S^-1 U' Z
+ *   sweeps_out                 sweeps of the Jacobi eigen-solver (may be NULL)
+ * Sign: in every component row the entry of largest magnitude is positive, the lowest column index deciding among bit-equal
+ * magnitudes; the score column carries the same sign.  Rank floor: a component with lambda_i <= max(n, p) 2^-52 lambda_1 is
+ * outside the numerical rank of the Gram matrix (numpy.linalg.matrix_rank's rule); its component row and its score column
+ * are zeros.  The eigen-solver has a sweep cap: a fit that reaches it fails with PSK_ESTATE.
+ *
+ * psk_pca_transform: X[m][p], any m >= 1; center[p], scale[p], components[k][p]:
+ *   scores_out[m][k]           scores[i][c] = sum_j ((X[i][j] - center[j]) / scale[j]) * components[c][j]
+ * The caller passes center = scaler.mean_ + scaler.scale_ * pca.mean_ (a PCA whose mean_ is not zero is served too).  The
+ * order of the sum is part of the contract: z_j = (X[i][j] - center[j]) / scale[j]; 64 partial sums, partial sum l starting
+ * from +0.0 and adding the rounded products z_j * components[c][j] for j = l, l + 64, l + 128, ... in ascending order (a
+ * multiplication, then an addition: nothing fused); then a_l = a_l + a_(l xor m) for m = 32, 16, 8, 4, 2, 1 over all l at
+ * once, and a_0 is the sum.  A result depends on nothing but its row, its component, center and scale: transform(X[lo:hi])
+ * equals transform(X)[lo:hi] bit for bit.
+ */
+int psk_pca_fit(psk_ctx *ctx, const float *X, int n, int p, int n_comp, double *mean_out, double *var_out,
+                double *scale_out, double *lambda_out, double *scores_out, double *components_out,
+                int32_t *sweeps_out);
+int psk_pca_transform(psk_ctx *ctx, const float *X, int m, int p, const double *center, const double *scale,
+                      const double *components, int k, double *scores_out);
+
 /* ---- f1: fixed-dictionary counting (prediction) ---------------------------------------------
  * Replaces `gmer_counter -db <txt> <addr>` (prediction.Samples.map_samples, prediction.py:72-80):
  * occurrences, both strands with multiplicity, of each dictionary k-mer (canonical words) in

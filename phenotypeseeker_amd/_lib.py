@@ -103,6 +103,10 @@ _SIGNATURES = {
     "psk_nb_fit": (c.c_int, [c.c_void_p, c.c_void_p, c.c_void_p, c.c_int, c.c_int, c.c_void_p, c.c_void_p, c.c_int, c.c_void_p,
                              c.c_void_p]),
     "psk_nb_jll": (c.c_int, [c.c_void_p, c.c_void_p, c.c_int, c.c_int, c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p]),
+    "psk_pca_fit": (c.c_int, [c.c_void_p, c.c_void_p, c.c_int, c.c_int, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
+                              c.c_void_p, c.c_void_p, c.c_void_p]),
+    "psk_pca_transform": (c.c_int, [c.c_void_p, c.c_void_p, c.c_int, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int,
+                                    c.c_void_p]),
     "psk_count_dict": (c.c_int, [c.c_void_p, c.c_char_p, c.c_size_t, c.c_int, c.c_void_p, c.c_uint64, c.c_void_p]),
     "psk_count_dict_batch": (c.c_int, [c.c_void_p, c.c_int, c.POINTER(c.c_char_p), c.POINTER(c.c_size_t), c.c_int, c.c_void_p,
                                        c.c_uint64, c.c_void_p, c.c_int]),

@@ -1,6 +1,7 @@
 """Small numeric helpers for the reporting stage (host side, pure Python/numpy): Student-t tail,
 rank transform, Pearson / Spearman with p-values (what the reference takes from scipy.stats at
-modeling.py:1268-1280)."""
+modeling.py:1268-1280); the weighted Welch t-test of two groups of numbers (conduct_t_test, modeling.py:716-736) for the
+principal components of `--pca`."""
 import math
 
 import numpy as np
@@ -83,3 +84,40 @@ def pearsonr(x, y):
 
 def spearmanr(x, y):
     return pearsonr(rankdata(x), rankdata(y))
+
+
+def welch_weighted(x, y, xw, yw):
+    """(t, p, mean_x, mean_y) as conduct_t_test (modeling.py:716-736) computes them: statsmodels' ttest_ind(x, y,
+    usevar='unequal', weights=(xw, yw)) and np.average(x, weights=xw), np.average(y, weights=yw).  The sums of the statistic run
+    in sample order (DescrStatsW's), the two printed means in NumPy's pairwise order.  (nan, nan, ...) when a group has fewer
+    than two members' weight or no spread."""
+    x, y, xw, yw = (np.asarray(a, dtype=np.float64) for a in (x, y, xw, yw))
+
+    def group(v, w):
+        total, s = 0.0, 0.0
+        for vi, wi in zip(v.tolist(), w.tolist()):
+            total += wi
+            s += wi * vi
+        mean = s / total
+        q = 0.0
+        for vi, wi in zip(v.tolist(), w.tolist()):
+            d = vi - mean
+            q += wi * d * d
+        return total, mean, (q / total) / (total - 1.0)      # (the variance with ddof 0, over the weight - 1)
+
+    with np.errstate(all="ignore"):
+        mean_x = float(np.sum(x * xw) / np.sum(xw)) if len(x) else float("nan")
+        mean_y = float(np.sum(y * yw) / np.sum(yw)) if len(y) else float("nan")
+    if len(x) == 0 or len(y) == 0:
+        return float("nan"), float("nan"), mean_x, mean_y
+    try:
+        nx, mx, sem1 = group(x, xw)
+        ny, my, sem2 = group(y, yw)
+        semsum = sem1 + sem2
+        t = (mx - my) / math.sqrt(semsum)
+        z1 = (sem1 / semsum) * (sem1 / semsum) / (nx - 1.0)
+        z2 = (sem2 / semsum) * (sem2 / semsum) / (ny - 1.0)
+        df = 1.0 / (z1 + z2)
+    except (ZeroDivisionError, ValueError):
+        return float("nan"), float("nan"), mean_x, mean_y
+    return t, t_two_sided_p(t, df), mean_x, mean_y

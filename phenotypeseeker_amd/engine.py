@@ -603,6 +603,40 @@ class PskContext:
         self._check(self._lib.psk_nb_jll(self._h, _ptr(X), n, p, _ptr(delta), nm, _ptr(prior), _ptr(neg), _ptr(jll)), "psk_nb_jll")
         return jll[0] if one else jll
 
+    def pca_fit(self, X, n_comp=None):
+        """StandardScaler + PCA of a design (psk_pca_fit): X[n][p], presence or counts; n_comp leading components, all
+        min(n, p) when None.  Returns a dictionary: mean[p], var[p], scale[p], lambda[min(n, p)] (eigenvalues of Z Z',
+        descending), scores[n][n_comp], components[n_comp][p] and sweeps (of the eigen-solver)."""
+        X = np.ascontiguousarray(X, dtype=np.float32)
+        if X.ndim != 2:
+            raise ValueError("X must be samples x columns")
+        n, p = X.shape
+        k = min(n, p) if n_comp is None else int(n_comp)
+        mean, var, scale = np.zeros(p), np.zeros(p), np.zeros(p)
+        lam, scores, comp = np.zeros(min(n, p)), np.zeros((n, max(k, 0))), np.zeros((max(k, 0), p))
+        sweeps = ctypes.c_int32()
+        self._check(self._lib.psk_pca_fit(self._h, _ptr(X), n, p, k, _ptr(mean), _ptr(var), _ptr(scale), _ptr(lam), _ptr(scores),
+                                          _ptr(comp), ctypes.addressof(sweeps)), "psk_pca_fit")
+        return {"mean": mean, "var": var, "scale": scale, "lambda": lam, "scores": scores, "components": comp, "sweeps": int(sweeps.value)}
+
+    def pca_transform(self, X, center, scale, components):
+        """scores[m][k] = ((X - center) / scale) . components' (psk_pca_transform) in the summation order include/psk.h states:
+        a row's scores depend on that row and the model only."""
+        X = np.ascontiguousarray(X, dtype=np.float32)
+        if X.ndim != 2:
+            raise ValueError("X must be samples x columns")
+        m, p = X.shape
+        center = np.ascontiguousarray(center, dtype=np.float64)
+        scale = np.ascontiguousarray(scale, dtype=np.float64)
+        comp = np.ascontiguousarray(components, dtype=np.float64)
+        if center.shape != (p,) or scale.shape != (p,) or comp.ndim != 2 or comp.shape[1] != p:
+            raise ValueError("center and scale must have one entry per column of X, components one row of them per component")
+        k = comp.shape[0]
+        scores = np.zeros((m, k))
+        self._check(self._lib.psk_pca_transform(self._h, _ptr(X), m, p, _ptr(center), _ptr(scale), _ptr(comp), k, _ptr(scores)),
+                    "psk_pca_transform")
+        return scores
+
     # -- population-structure weights --------------------------------------------------------------
     def minhash_sketch(self, data, k=21, sketch_size=1000, seed=42):
         data = bytes(data)

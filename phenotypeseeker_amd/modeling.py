@@ -344,7 +344,8 @@ class Input:
                    real_counts, omit_B, kmerDB):
         """Same positional signature as the reference (:141-183).  Options that select estimators
         outside the hot path (SVM/RF/DT/NB, L2/elastic net, saga, PCA) are rejected here; `-bc SVM`, `-bc DT`, `-bc RF` and
-        `-bc NB` pass with their knobs (PSK_SVM, PSK_DT, PSK_RF, PSK_NB)."""
+        `-bc NB` pass with their knobs (PSK_SVM, PSK_DT, PSK_RF, PSK_NB), `--pca` with PSK_PCA for a binary phenotype under
+        `-bc log` and `-bc SVM`."""
         if alphas is None:
             phenotypes.alphas = np.logspace(math.log10(alpha_min), math.log10(alpha_max), num=n_alphas)
         else:
@@ -447,8 +448,11 @@ class Input:
             # L1+L2 cannot complete in the reference either: GridSearchCV is handed {'C': ...} for an
             # SGDClassifier (:1020-1024, :1045-1047) and fit_model skips the ElasticNet fit (:1211-1214)
             raise SystemExit("Only the L1 and L2 penalties run on the GPU engine, got %r." % penalty)
-        if pca:
+        if pca and not _lib.env_flag("PSK_PCA"):
             raise SystemExit("--pca is outside the accelerated path.")
+        if pca and phenotypes.pred_scale == "continuous":
+            # PCA_analysis (:1178-1193) keeps the components whose scores differ between phenotype == 1 and phenotype == 0
+            raise SystemExit("--pca on the GPU engine needs a binary phenotype: its t-test compares the two classes.")
 
 
 # set_model's hyper-parameters of the random forest, in the reference's own spelling and order (:1057-1068)
@@ -767,11 +771,14 @@ class phenotypes:
         self.get_ML_df()
         short = self.model_name_short
         summary = open("summary_of_%s_analysis_%s.txt" % (short, self.name), "w")
-        coeff_path = "k-mers_and_coefficients_in_%s_model_%s.txt" % (short, self.name)
+        coeff_path = "%s_and_coefficients_in_%s_model_%s.txt" % ("PCs" if self.pca else "k-mers", short, self.name)   # (:869-870, :1108)
         X = self.ML["X"].astype(np.float64)
         index = list(self.ML["index"])
         binary = self.pred_scale == "binary"
         y = np.array(self.ML["phenotype"], dtype=np.int64 if binary else np.float64)
+        if self.pca:
+            # once, on all samples, before any -cv1 / -ts split (:867-868): every fit, report and split below sees the kept scores
+            X = self.PCA_analysis(ctx)
         self.n_splits_cv_outer = None
         m_train, m_test = _metric_store(), _metric_store()
         if phenotypes.n_splits_cv_outer:
@@ -828,14 +835,18 @@ class phenotypes:
         # (scikit-learn-free) classes, which is also what is written when scikit-learn is missing.
         package.update({"pca": self.pca, "pred_scale": self.pred_scale})
         blob = None
+        parts = dict(model=self.model_fitted)
+        if self.pca:     # the scaler, the PCA and the mask travel with the model, the first two as scikit-learn's objects too
+            package.update(self.pca_parts)
+            parts.update(scaler=package["scaler"], pca_model=package["pca_model"])
         if not _lib.env_flag("PSK_NATIVE_PKL"):
             from . import skpickle
-            shell = self.model_fitted.to_sklearn_shell()          # no scikit-learn import (skpickle.py)
-            if shell is not None:
-                blob = skpickle.dumps(dict(package, model=shell))
+            shells = {k: v.to_sklearn_shell() for k, v in parts.items()}     # no scikit-learn import (skpickle.py)
+            if all(v is not None for v in shells.values()):
+                blob = skpickle.dumps(dict(package, **shells))
             else:                                                   # a scikit-learn version without a template: import it
                 try:
-                    package["model"] = self.model_fitted.to_sklearn()
+                    package.update({k: v.to_sklearn() for k, v in parts.items()})
                 except ImportError:
                     package["model"] = self.model_fitted
         else:
@@ -852,6 +863,46 @@ class phenotypes:
             phenotypes.png_notice_given = True
             _err("The decision tree's plot (DT_model_<phenotype>_plot.png) is not written by the GPU engine.\n")
         summary.close()
+
+    def PCA_analysis(self, ctx):
+        """(:1147-1206) StandardScaler and PCA of the selected k-mers on the device (model_pca.fit: psk_pca_fit), the components
+        with explained_variance_ > 0.9 -- a prefix, explained variance being sorted --, of them those whose scores differ
+        between the two classes (the GSC-weighted Welch t-test of conduct_t_test, p < 0.01).  Returns the design of everything
+        that follows: the kept score columns, rounded to float32 as every fit of this library takes its design; their names
+        PC_<i>, i the 1-based index among all components, and their lines of the coefficient file are kept in self.PC.
+        The reference calls self.t_test here (:1184), which does not exist: it cannot complete this branch."""
+        from . import model_pca
+        y = np.array(self.ML["phenotype"], dtype=np.int64)
+        w = np.array([float(v) for v in self.ML["weights"]])
+        scaler, pca, scores = model_pca.fit(ctx, self.ML["X"])
+        keep = np.zeros(len(pca.explained_variance_), dtype=bool)
+        tests = {}
+        for c in np.nonzero(pca.explained_variance_ > 0.9)[0]:
+            t, p, _, _ = _stats.welch_weighted(scores[y == 1, c], scores[y == 0, c], w[y == 1], w[y == 0])
+            if p < 0.01:
+                keep[c] = True
+                tests[int(c)] = (t, p)
+        if not keep.any():
+            raise SystemExit("--pca: no principal component of phenotype %s has an explained variance above 0.9 and a t-test "
+                             "p-value below 0.01: there is nothing to fit a model on." % self.name)
+        kept = [int(c) for c in np.nonzero(keep)[0]]
+        self.PC = {"names": ["PC_%d" % (c + 1) for c in kept], "explained_variance": pca.explained_variance_[kept],
+                   "explained_variance_ratio": pca.explained_variance_ratio_[kept], "t": [tests[c][0] for c in kept],
+                   "p": [tests[c][1] for c in kept]}
+        self.pca_parts = {"scaler": scaler, "pca_model": pca, "PCs_to_keep": keep}     # (:1194, :1205-1206) this phenotype's, for its package
+        return scores[:, keep].astype(np.float32).astype(np.float64)
+
+    def _write_pc_coefficients(self, path):
+        """(:1415-1420, :1445-1450) one line per kept component, the numbers as an f-string formats a numpy.float64."""
+        be = self.model_fitted.best_estimator_
+        coefs = np.ravel(be._coef_column if hasattr(be, "_coef_column") else be.coef_)
+        pc = self.PC
+        with open(path, "w") as out:
+            out.write("PC\tcoef._in_" + self.model_name_short + "_model\texplained_variance\texplained_variance_ratio"
+                      "\tt-test_statistic\tt-test_pvalue\n")
+            for i, name in enumerate(pc["names"]):
+                out.write(f"{name}\t{np.float64(coefs[i])}\t{np.float64(pc['explained_variance'][i])}"
+                          f"\t{np.float64(pc['explained_variance_ratio'][i])}\t{np.float64(pc['t'][i])}\t{np.float64(pc['p'][i])}\n")
 
     def _cross_validation_results(self, out):
         """(:1219-1237); nothing for NB, which is not searched (:1220)"""
@@ -930,6 +981,8 @@ class phenotypes:
     def _write_model_coefficients(self, path):
         """(:1414-1455).  The header is written and the file CLOSED here; libpsk then appends the lines to `path` (no Python
         file object is shared with it: a stale offset could overwrite what it wrote)."""
+        if self.pca:
+            return self._write_pc_coefficients(path)
         with open(path, "w") as out:
             out.write("K-mer\tcoef._in_" + self.model_name_short + "_model\tNo._of_samples_with_k-mer\tSamples_with_k-mer\n")
             if self.model_name_short == "NB":

@@ -63,8 +63,9 @@ class Phenotypes:
     cutoff = 1
     no_phenotypes = 0
 
-    def __init__(self, name, model, kmers, pca, pred_scale):
+    def __init__(self, name, model, kmers, pca, pred_scale, projection=None):
         self.name, self.model, self.kmers, self.pca, self.pred_scale = name, model, kmers, pca, pred_scale
+        self.projection = projection      # `modeling --pca`: (scaler, pca_model, PCs_to_keep) of the package
         self.k = len(str(kmers[0])) if kmers.shape[0] else 0
         self.words = np.array([formats.canonical(formats.kmer_to_word(str(km)), self.k) for km in kmers],
                               dtype=np.uint64)
@@ -82,8 +83,13 @@ class Phenotypes:
         if pkg is None:
             import joblib
             pkg = joblib.load(path)
-        if pkg.get("pca"):
+        if pkg.get("pca") and not env_flag("PSK_PCA"):
             raise SystemExit("PCA models are outside the accelerated path.")
+        if pkg.get("pca"):
+            # (:131-143) the scaler, the PCA and the mask travel with the model; read by the stub they are model_pca's classes,
+            # by joblib.load scikit-learn's: the projection reads their fitted attributes only
+            keep = np.asarray(pkg["PCs_to_keep"], dtype=bool)
+            return cls(name, pkg["model"], np.asarray(pkg["kmers"]), True, pkg["pred_scale"], (pkg["scaler"], pkg["pca_model"], keep))
         return cls(name, pkg["model"], np.asarray(pkg["kmers"]), False, pkg["pred_scale"])
 
     def get_inp_matrix(self, ctx, n_threads=8):
@@ -94,10 +100,17 @@ class Phenotypes:
         takes its joint log-likelihoods from the open context (psk_nb_jll); every other model predicts as before."""
         from .model_nb import BernoulliNB
         on_device = (ctx,) if ctx is not None and isinstance(self.model, BernoulliNB) else ()
-        predictions = self.model.predict(self.matrix, *on_device)
+        design = self.matrix
+        if self.pca:
+            # (:155-163) scaler.transform, pca_model.transform, [:, PCs_to_keep]: one psk_pca_transform on the open context for
+            # the kept components, handed to the model rounded to float32 as `modeling` handed it the training scores
+            from . import model_pca
+            scaler, pca_model, keep = self.projection
+            design = model_pca.project(scaler, pca_model, self.matrix, keep, ctx).astype(np.float32).astype(np.float64)
+        predictions = self.model.predict(design, *on_device)
         with open("predictions_" + self.name + ".txt", "w+") as out:
             if self.pred_scale == "binary":
-                proba = self.model.predict_proba(self.matrix, *on_device)
+                proba = self.model.predict_proba(design, *on_device)
                 out.write("Sample_ID\tpredicted_phenotype\tprobability_for_predicted_class\n")
                 for sample, pred, pr in zip(Input.samples.keys(), predictions, proba):
                     out.write("%s\t%s\t%s\n" % (sample, str(pred), str(round(pr[1], 2))))

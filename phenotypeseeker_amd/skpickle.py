@@ -268,14 +268,23 @@ def load_linear_package(path):
     that are plain pickles of a (grid search over a) binary linear classifier or a linear regressor, which is what
     `modeling` writes; a two-class SVC with a Platt pair comes back as model.SVC (_svc_from_state), a two-class decision tree
     as model.DecisionTree (_tree_from_state), a two-class random forest as model.RandomForest (_forest_from_state), a two-class
-    BernoulliNB() as model.BernoulliNB (_nb_from_state).  None for anything else
-    (joblib-wrapped arrays, multi-class models, other estimators, a PCA pipeline): the caller then takes joblib.load and
-    scikit-learn itself."""
+    BernoulliNB() as model.BernoulliNB (_nb_from_state).  A package with 'pca' true (`modeling --pca`) keeps its 'PCs_to_keep' and
+    comes back with 'scaler' and 'pca_model' as model_pca.StandardScaler and model_pca.PCA (model_pca.from_state).  None for
+    anything else (joblib-wrapped arrays, multi-class models, other estimators, a scaler or PCA with other than the default
+    parameters): the caller then takes joblib.load and scikit-learn itself."""
     try:
         with open(path, "rb") as f:
             pkg = _StubUnpickler(f).load()
-        if not isinstance(pkg, dict) or pkg.get("pca") or "model" not in pkg:
+        if not isinstance(pkg, dict) or "model" not in pkg:
             return None
+        if pkg.get("pca"):
+            from . import model_pca
+            if not {"scaler", "pca_model", "PCs_to_keep"} <= set(pkg):
+                return None
+            pair = model_pca.from_state(pkg["scaler"], pkg["pca_model"])
+            if pair is None:
+                return None
+            pkg = dict(pkg, scaler=pair[0], pca_model=pair[1])
         m = pkg["model"]
         est = getattr(m, "best_estimator_", m)
         kind = type(est).__name__

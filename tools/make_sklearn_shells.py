@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Records, for the installed scikit-learn, what a default-constructed LogisticRegression / Lasso / Ridge / SVC /
-DecisionTreeClassifier / RandomForestClassifier / BernoulliNB / GridSearchCV / RandomizedSearchCV pickles as (module, class name, state) into phenotypeseeker_amd/sklearn_shells.json, keyed by the
+DecisionTreeClassifier / RandomForestClassifier / BernoulliNB / StandardScaler / PCA / GridSearchCV / RandomizedSearchCV pickles as (module, class name, state) into phenotypeseeker_amd/sklearn_shells.json, keyed by the
 scikit-learn version.  phenotypeseeker_amd/skpickle.py writes model files from these templates without importing
 scikit-learn (0.3-0.5 s, as long as the rest of a 256-genome `modeling` run); a version without a template takes the
 import.  usage: tools/make_sklearn_shells.py"""
@@ -9,10 +9,12 @@ import math
 import os
 
 import sklearn
+from sklearn.decomposition import PCA
 from sklearn.ensemble import RandomForestClassifier
 from sklearn.linear_model import Lasso, LogisticRegression, Ridge
 from sklearn.model_selection import GridSearchCV, RandomizedSearchCV
 from sklearn.naive_bayes import BernoulliNB
+from sklearn.preprocessing import StandardScaler
 from sklearn.svm import SVC
 from sklearn.tree import DecisionTreeClassifier
 
@@ -47,6 +49,8 @@ out[sklearn.__version__] = {
     # (estimator: a DecisionTreeClassifier shell, estimator_params: a tuple of names -- both filled in by model_trees.py)
     "RandomForestClassifier": shell(RandomForestClassifier(), drop=("estimator", "estimator_params")),
     "BernoulliNB": shell(BernoulliNB()),
+    "StandardScaler": shell(StandardScaler()),
+    "PCA": shell(PCA()),
     "RandomizedSearchCV": shell(RandomizedSearchCV(LogisticRegression(), {"C": [1.0]}), drop=("estimator", "param_distributions")),
     "GridSearchCV": shell(GridSearchCV(LogisticRegression(), {"C": [1.0]}), drop=("estimator", "param_grid")),
 }
