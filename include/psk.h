@@ -346,7 +346,8 @@ int psk_logreg_l2_fit(psk_ctx *ctx, const float *X, const int32_t *y01, int n, i
  *   iters_out[n_fits]    iterations taken (== max_iter: stopped at the limit); may be NULL
  * The sample x sample dot products are built once per call and shared by the fits (popcounts of bit-packed rows for
  * a 0/1 design, f64 dot products otherwise): at most 4096 samples (PSK_ERANGE beyond).  A fit whose training
- * samples are of one class is refused (PSK_EINVAL).
+ * samples are of one class is refused (PSK_EINVAL).  Decision values of rows that were not in the fit's X:
+ * psk_svc_decision (f12), in the same operation order.
  */
 int psk_svc_fit(psk_ctx *ctx, const float *X, const int32_t *y01, int n, int p, const int32_t *fold,
                 const double *fit_C, const double *fit_gamma, const int32_t *fit_fold, int n_fits, int kernel,
@@ -521,6 +522,25 @@ int psk_pca_fit(psk_ctx *ctx, const float *X, int n, int p, int n_comp, double *
                 int32_t *sweeps_out);
 int psk_pca_transform(psk_ctx *ctx, const float *X, int m, int p, const double *center, const double *scale,
                       const double *components, int k, double *scores_out);
+
+/* ---- f12: decision values of a fitted SVM (prediction) ---------------------------------------------
+ * What libsvm's svm_predict_values computes for new rows, the one prediction whose cost grows with the training set
+ * (rows x support vectors x k-mers for the rbf kernel):
+ *   dec_out[m]   dec[i] = (sum_j coef[j] K(SV_j, X_i)) - rho, libsvm's sign; coef[j] = y_j alpha_j (the package's
+ *                -dual_coef_[0]), SV[n_sv][p] the support vectors, X[m][p] the rows; kernel 0 linear, 1 rbf
+ * The order of the operations is the contract, and it is the order of the loop that ends psk_svc_fit's solver kernel, so a
+ * fit's dec_out and this call on the fit's support vectors (class 0 first, input order within a class) agree bit for bit:
+ * d = SV_j . X_i, sa = SV_j . SV_j and sb = X_i . X_i are f64 sums over the columns in ascending order (a multiplication,
+ * then an addition: nothing fused); K = d, or exp(-gamma * (sa + sb - 2 * d)); the sum starts from +0.0 and takes the
+ * rounded products coef[j] * K for j = 0, 1, ..., n_sv - 1 one after the other; then rho is subtracted.  A result depends
+ * on nothing but its row, the support vectors and the model: decision(X[lo:hi]) equals decision(X)[lo:hi] bit for bit.
+ * When every entry of X and SV is 0 or 1 both are bit-packed and the dot products are popcounts; otherwise they are f64.
+ * On 0/1 input both routes give the same bits (the sums are exact integers).  No sample x sample matrix is held, so there
+ * is no 4096 cap: m >= 1, n_sv >= 1, p >= 1, every index is 64-bit.  PSK_EINVAL: a null buffer, a kernel other than 0 or
+ * 1, a negative or non-finite gamma, a non-finite entry of X, SV, coef or rho.
+ */
+int psk_svc_decision(psk_ctx *ctx, const float *X, int m, int p, const float *SV, int n_sv, const double *coef,
+                     double rho, int kernel, double gamma, double *dec_out);
 
 /* ---- f1: fixed-dictionary counting (prediction) ---------------------------------------------
  * Replaces `gmer_counter -db <txt> <addr>` (prediction.Samples.map_samples, prediction.py:72-80):

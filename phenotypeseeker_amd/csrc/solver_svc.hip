@@ -15,11 +15,14 @@
 // Two kernels: svc_gram_kernel builds the sample x sample dot products once per call (popcounts of bit-packed rows for a
 // 0/1 design, which are exact in float; f64 dot products otherwise); svc_smo_kernel runs one workgroup of four waves per
 // fit with alpha, G, QD, the index list, the current row Q_i and the labels in LDS (33 B per training sample, 135 KB at
-// 4096 samples).
+// 4096 samples).  psk_svc_decision (svc_decision_kernel, further down) evaluates a fitted model on new rows in the order of
+// the loop that ends svc_smo_kernel, without a sample x sample matrix.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <algorithm>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "dev_utils.h"
@@ -333,6 +336,160 @@ int svc_launch_smo(psk_ctx *ctx, const T *D, const SvcArrs &b, int n, int n_fits
     return PSK_OK;
 }
 
+// ---- decision values of new rows ---------------------------------------------------------------------------------------
+// psk_svc_decision: dec[i] = (sum_j coef[j] K(SV_j, X_i)) - rho in the order of the loop that ends svc_smo_kernel.  A
+// workgroup owns DEC_ROWS rows and walks the support vectors in tiles of DEC_TILE; within a tile it walks the columns in
+// chunks staged in LDS (DEC_WORDS packed words, or DEC_COLS floats), every thread keeping the dot products of one row with
+// DEC_PER of the tile's support vectors.  The rounded products coef[j] * K then go to LDS, and ONE lane per row adds them
+// in j order: the sum of a row is serial and stays in that lane's register from the first support vector to the last.
+constexpr int DEC_THREADS = 256;
+constexpr int DEC_ROWS = 32;
+constexpr int DEC_TILE = 64;
+constexpr int DEC_GROUPS = DEC_THREADS / DEC_ROWS;   // thread t: row t % DEC_ROWS, support vectors t / DEC_ROWS + DEC_GROUPS q
+constexpr int DEC_PER = DEC_TILE / DEC_GROUPS;
+constexpr int DEC_WORDS = 16;                        // u64 words of a row per staged chunk
+constexpr int DEC_COLS = 32;                         // floats of a row per staged chunk
+
+// row norms: popcount of the packed row, or the f64 sum of squares with the columns ascending (the diagonal of the fit's
+// Gram matrix, computed the same way)
+__global__ void svc_norm_bits_kernel(const uint64_t *__restrict__ bits, int rows, int W, double *__restrict__ out)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)rows) return;
+    uint32_t s = 0;
+    for (int w = 0; w < W; w++) s += (uint32_t)__popcll(bits[i * W + w]);
+    out[i] = (double)s;
+}
+
+__global__ void svc_norm_dense_kernel(const float *__restrict__ X, int rows, int p, double *__restrict__ out)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)rows) return;
+    double s = 0.0;
+    for (int k = 0; k < p; k++) {
+        const double v = (double)X[i * p + k];
+        s += v * v;
+    }
+    out[i] = s;
+}
+
+// T = uint64_t: rows of W packed words, the dot product a popcount; T = float: rows of W floats, the dot product in f64 with
+// the columns ascending.  CH = the chunk of a row staged at a time.
+template <typename T, int CH, int KERN>
+__global__ __launch_bounds__(DEC_THREADS) void svc_decision_kernel(const T *__restrict__ X, int m, int W, const T *__restrict__ SV,
+                                                                    int n_sv, const double *__restrict__ xnorm,
+                                                                    const double *__restrict__ svnorm, const double *__restrict__ coef,
+                                                                    double rho, double gamma, double *__restrict__ dec)
+{
+    using Acc = typename std::conditional<std::is_same<T, uint64_t>::value, uint32_t, double>::type;
+    __shared__ T xs[DEC_ROWS][CH + 1], ss[DEC_TILE][CH + 1];
+    __shared__ double prod[DEC_ROWS][DEC_TILE + 1];
+    const int tid = threadIdx.x, r = tid % DEC_ROWS, g = tid / DEC_ROWS;
+    const size_t row0 = (size_t)blockIdx.x * DEC_ROWS;
+    const bool row_ok = row0 + r < (size_t)m;
+    const double sb = (KERN && row_ok) ? xnorm[row0 + r] : 0.0;
+    double sum = 0.0;   // (threads below DEC_ROWS: the decision value of row tid)
+    for (int j0 = 0; j0 < n_sv; j0 += DEC_TILE) {
+        const int tile = min(DEC_TILE, n_sv - j0);
+        Acc d[DEC_PER];
+#pragma unroll
+        for (int q = 0; q < DEC_PER; q++) d[q] = 0;
+        for (int w0 = 0; w0 < W; w0 += CH) {
+            const int wn = min(CH, W - w0);
+            for (int e = tid; e < DEC_ROWS * CH; e += DEC_THREADS) {
+                const int er = e / CH, ew = e % CH;
+                xs[er][ew] = (row0 + er < (size_t)m && ew < wn) ? X[(row0 + er) * W + w0 + ew] : T(0);
+            }
+            for (int e = tid; e < DEC_TILE * CH; e += DEC_THREADS) {
+                const int ej = e / CH, ew = e % CH;
+                ss[ej][ew] = (ej < tile && ew < wn) ? SV[(size_t)(j0 + ej) * W + w0 + ew] : T(0);
+            }
+            __syncthreads();
+            for (int w = 0; w < wn; w++) {
+                const T xv = xs[r][w];
+#pragma unroll
+                for (int q = 0; q < DEC_PER; q++) {
+                    if constexpr (std::is_same<T, uint64_t>::value) d[q] += (uint32_t)__popcll(xv & ss[g + DEC_GROUPS * q][w]);
+                    else d[q] += (double)ss[g + DEC_GROUPS * q][w] * (double)xv;
+                }
+            }
+            __syncthreads();
+        }
+#pragma unroll
+        for (int q = 0; q < DEC_PER; q++) {
+            const int jl = g + DEC_GROUPS * q;
+            if (jl < tile && row_ok) {
+                const int j = j0 + jl;
+                prod[r][jl] = coef[j] * svc_kval<KERN>((double)d[q], KERN ? svnorm[j] : 0.0, sb, gamma);
+            }
+        }
+        __syncthreads();
+        if (tid < DEC_ROWS && row_ok)
+            for (int jl = 0; jl < tile; jl++) sum += prod[tid][jl];
+        __syncthreads();
+    }
+    if (tid < DEC_ROWS && row_ok) dec[row0 + tid] = sum - rho;
+}
+
+template <typename T> bool svc_all_finite(const T *v, size_t count)
+{
+    return std::all_of(v, v + count, [](T x) { return std::isfinite(x); });
+}
+
+// one pass over a design: every entry finite (x - x is 0 only then); *binary &= every entry 0 or 1.  No early exit: the
+// loop has no branch on the data.
+bool svc_scan_design(const float *v, size_t count, bool *binary)
+{
+    unsigned bad = 0, other = 0;
+    for (size_t i = 0; i < count; i++) {
+        const float x = v[i];
+        bad |= !(x - x == 0.0f);
+        other |= (x != 0.0f) & (x != 1.0f);
+    }
+    *binary = *binary && !other;
+    return !bad;
+}
+
+// rows[count][p] of 0/1 floats -> [count][W] words, column j at bit j & 63 of word j >> 6 (the packing of psk_svc_fit),
+// a word at a time
+std::vector<uint64_t> svc_pack_rows(const float *X, size_t count, int p, int W)
+{
+    std::vector<uint64_t> bits(count * W);
+    for (size_t i = 0; i < count; i++)
+        for (int w = 0; w < W; w++) {
+            const float *x = X + i * p + (size_t)w * 64;
+            const int nb = std::min(64, p - w * 64);
+            uint64_t word = 0;
+            for (int b = 0; b < nb; b++) word |= (uint64_t)(x[b] != 0.0f) << b;
+            bits[i * W + w] = word;
+        }
+    return bits;
+}
+
+template <typename T, int CH>
+int svc_launch_decision(psk_ctx *ctx, const T *X, int m, int W, const T *SV, int n_sv, const double *coef, double rho, int kernel,
+                        double gamma, double *dec)
+{
+    FitArr<double> xnorm, svnorm;
+    if (kernel == 1) {
+        PSK_HIP(ctx, xnorm.alloc(m));
+        PSK_HIP(ctx, svnorm.alloc(n_sv));
+        if constexpr (std::is_same<T, uint64_t>::value) {
+            svc_norm_bits_kernel<<<div_up(m, 256), 256, 0, ctx->stream>>>(X, m, W, xnorm);
+            svc_norm_bits_kernel<<<div_up(n_sv, 256), 256, 0, ctx->stream>>>(SV, n_sv, W, svnorm);
+        } else {
+            svc_norm_dense_kernel<<<div_up(m, 256), 256, 0, ctx->stream>>>(X, m, W, xnorm);
+            svc_norm_dense_kernel<<<div_up(n_sv, 256), 256, 0, ctx->stream>>>(SV, n_sv, W, svnorm);
+        }
+        PSK_HIP(ctx, hipGetLastError());
+    }
+    auto kern = kernel == 0 ? svc_decision_kernel<T, CH, 0> : svc_decision_kernel<T, CH, 1>;
+    kern<<<div_up(m, DEC_ROWS), DEC_THREADS, 0, ctx->stream>>>(X, m, W, SV, n_sv, xnorm, svnorm, coef, rho, gamma, dec);
+    PSK_HIP(ctx, hipGetLastError());
+    PSK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (the norms are freed on return)
+    return PSK_OK;
+}
+
 }  // namespace
 
 extern "C" int psk_svc_fit(psk_ctx *ctx, const float *X, const int32_t *y01, int n, int p, const int32_t *fold,
@@ -405,5 +562,40 @@ extern "C" int psk_svc_fit(psk_ctx *ctx, const float *X, const int32_t *y01, int
     PSK_HIP(ctx, b.dec.download(dec_out, (size_t)n_fits * n, ctx->stream));
     if (iters_out) PSK_HIP(ctx, b.iters.download(iters_out, n_fits, ctx->stream));
     PSK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (`gam` must outlive its copy)
+    return PSK_OK;
+}
+
+extern "C" int psk_svc_decision(psk_ctx *ctx, const float *X, int m, int p, const float *SV, int n_sv, const double *coef, double rho,
+                                int kernel, double gamma, double *dec_out)
+{
+    if (!ctx) return PSK_EINVAL;
+    if (!X || !SV || !coef || !dec_out) return psk_fail(ctx, PSK_EINVAL, "null buffer");
+    if (m < 1 || p < 1 || n_sv < 1) return psk_fail(ctx, PSK_EINVAL, "bad problem shape m=%d p=%d n_sv=%d", m, p, n_sv);
+    if (kernel != 0 && kernel != 1) return psk_fail(ctx, PSK_EINVAL, "kernel must be 0 (linear) or 1 (rbf), got %d", kernel);
+    if (!std::isfinite(gamma) || gamma < 0.0) return psk_fail(ctx, PSK_EINVAL, "gamma must be finite and >= 0, got %g", gamma);
+    if (!std::isfinite(rho) || !svc_all_finite(coef, (size_t)n_sv)) return psk_fail(ctx, PSK_EINVAL, "coef and rho must be finite");
+    bool binary = true;
+    const bool x_ok = svc_scan_design(X, (size_t)m * p, &binary), sv_ok = svc_scan_design(SV, (size_t)n_sv * p, &binary);
+    if (!x_ok || !sv_ok) return psk_fail(ctx, PSK_EINVAL, "X and SV must be finite");
+
+    PSK_HIP(ctx, hipSetDevice(ctx->device));
+    FitArr<double> d_coef, d_dec;
+    PSK_HIP(ctx, d_coef.upload(coef, n_sv, ctx->stream));
+    PSK_HIP(ctx, d_dec.alloc(m));
+    if (binary) {
+        const int W = (p + 63) / 64;
+        const std::vector<uint64_t> xb = svc_pack_rows(X, m, p, W), sb = svc_pack_rows(SV, n_sv, p, W);
+        FitArr<uint64_t> d_x, d_sv;
+        PSK_HIP(ctx, d_x.upload(xb, ctx->stream));
+        PSK_HIP(ctx, d_sv.upload(sb, ctx->stream));
+        PSK_TRY((svc_launch_decision<uint64_t, DEC_WORDS>(ctx, d_x, m, W, d_sv, n_sv, d_coef, rho, kernel, gamma, d_dec)));
+    } else {
+        FitArr<float> d_x, d_sv;
+        PSK_HIP(ctx, d_x.upload(X, (size_t)m * p, ctx->stream));
+        PSK_HIP(ctx, d_sv.upload(SV, (size_t)n_sv * p, ctx->stream));
+        PSK_TRY((svc_launch_decision<float, DEC_COLS>(ctx, d_x, m, p, d_sv, n_sv, d_coef, rho, kernel, gamma, d_dec)));
+    }
+    PSK_HIP(ctx, d_dec.download(dec_out, m, ctx->stream));
+    PSK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return PSK_OK;
 }

@@ -450,6 +450,22 @@ class PskContext:
                                           _ptr(dec), _ptr(iters)), "psk_svc_fit")
         return dual, rho, dec, iters
 
+    def svc_decision(self, X, SV, coef, rho, kernel="linear", gamma=0.0):
+        """Decision values of the rows X[m][p] under a fitted SVM (psk_svc_decision): (sum_j coef[j] K(SV[j], X[i])) - rho in
+        libsvm's sign, the support vectors added one after the other as psk_svc_fit's own decision values are.  coef[n_sv]:
+        y_j alpha_j (-dual_coef_[0]).  Returns dec[m]."""
+        if kernel not in ("linear", "rbf"):
+            raise ValueError("kernel must be 'linear' or 'rbf', got %r" % (kernel,))
+        X = np.ascontiguousarray(X, dtype=np.float32)
+        SV = np.ascontiguousarray(SV, dtype=np.float32)
+        coef = np.ascontiguousarray(coef, dtype=np.float64).reshape(-1)
+        if X.ndim != 2 or SV.ndim != 2 or X.shape[1] != SV.shape[1] or len(coef) != SV.shape[0]:
+            raise ValueError("svc_decision: X[m][p], SV[n_sv][p] and coef[n_sv] do not fit together")
+        dec = np.zeros(X.shape[0])
+        self._check(self._lib.psk_svc_decision(self._h, _ptr(X), X.shape[0], X.shape[1], _ptr(SV), SV.shape[0], _ptr(coef), float(rho),
+                                               1 if kernel == "rbf" else 0, float(gamma), _ptr(dec)), "psk_svc_decision")
+        return dec
+
     TREE_NODE_CAP = 2047      # PSK_TREE_NODE_CAP of include/psk.h
 
     COUNT_MAX = 1 << 24       # the largest value of a count design (include/psk.h, f9)

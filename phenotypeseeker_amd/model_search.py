@@ -17,6 +17,7 @@ class _Estimator:
     _coef_column: what `modeling` writes into the coefficient column of its k-mer table."""
     _warns_at_max_iter = False     # `modeling` prints scikit-learn's ConvergenceWarning when a fit of the search stopped at max_iter
     _randomized = False            # searched by RandomizedSearch (n_iter candidates drawn from the grid), not by GridSearch
+    _tracking_draws_only = False   # a randomized search of it takes n_iter / grid size < 0.01 only (the forest's accepted range)
 
     def _new_search(self, params, grid, cv, n_iter):
         """The search `modeling` puts this estimator under, as the reference's get_best_model does (modeling.py:1096-1103)."""
@@ -174,11 +175,12 @@ class GridSearch:
 
 
 class RandomizedSearch(GridSearch):
-    """RandomizedSearchCV(estimator, grid of lists, n_iter, cv=int, random_state=int) with refit, for RandomForest (get_best_model,
-    modeling.py:1096-1099).  The candidates are scikit-learn's for that random_state: ParameterGrid(grid)[i] (keys sorted, the
-    last key fastest) for the i that sample_without_replacement(grid_size, n_iter, random_state) yields.  Only its tracking
-    selection is restated -- the regime n_iter / grid_size < 0.01, where the reference's default 25 of 10,692 lies; another
-    n_iter is refused."""
+    """RandomizedSearchCV(estimator, grid of lists, n_iter, cv=int, random_state=int) with refit, for RandomForest and for SVC
+    with the rbf kernel (get_best_model, modeling.py:1091-1099).  The candidates are scikit-learn's for that random_state:
+    ParameterGrid(grid)[i] (keys sorted, the last key fastest) for the i that sample_without_replacement(grid_size, n_iter,
+    random_state) yields, in each of its three selections (sampled_indices): the forest's default 25 of 10,692 is a tracking
+    selection, the rbf default 25 of 13 x 13 = 169 a permutation's head.  TRACKING_RATIO / max_n_iter: the range `modeling`
+    accepts for the forest."""
     TRACKING_RATIO = 0.01
     _sk_name = "RandomizedSearchCV"
 
@@ -206,25 +208,44 @@ class RandomizedSearch(GridSearch):
         return out
 
     def sampled_indices(self):
+        """sklearn.utils.random.sample_without_replacement(grid_size, n_iter, method="auto", random_state) as scikit-learn 1.7
+        selects (utils/_random.pyx::_sample_without_replacement), r = n_iter / grid_size in f64:
+          0.01 < r < 0.99   the first n_iter entries of RandomState.permutation(grid_size)
+          r <= 0.01         tracking selection (r < 0.2 outside the band above): draw, and draw again on a repeat
+          r >= 0.99         reservoir sampling: 0 .. n_iter - 1, entry j replaced by i when randint(0, i + 1) gives j < n_iter"""
         size = self.grid_size()
         n_iter = min(self.n_iter, size)           # scikit-learn caps n_iter at the grid size (with a warning)
-        if n_iter < 1 or not n_iter / size < self.TRACKING_RATIO:
-            raise ValueError("RandomizedSearch draws its candidates as scikit-learn does for n_iter / grid size < %g only: "
-                             "n_iter must be 1..%d for this grid of %d points, got %d"
-                             % (self.TRACKING_RATIO, self.max_n_iter(size), size, self.n_iter))
+        if n_iter < 1:
+            raise ValueError("RandomizedSearch: n_iter must be at least 1, got %d" % self.n_iter)
         rs = np.random.RandomState(int(self.random_state))
-        taken, out = set(), []
-        for _ in range(n_iter):                   # utils/_random.pyx::_sample_without_replacement_with_tracking_selection
-            j = int(rs.randint(size))
-            while j in taken:
+        ratio = n_iter / size
+        if 0.01 < ratio < 0.99:
+            return [int(i) for i in rs.permutation(size)[:n_iter]]
+        if ratio < 0.2:
+            taken, out = set(), []
+            for _ in range(n_iter):               # _sample_without_replacement_with_tracking_selection
                 j = int(rs.randint(size))
-            taken.add(j)
-            out.append(j)
+                while j in taken:
+                    j = int(rs.randint(size))
+                taken.add(j)
+                out.append(j)
+            return out
+        out = list(range(n_iter))                 # _sample_without_replacement_with_reservoir_sampling
+        for i in range(n_iter, size):
+            j = int(rs.randint(0, i + 1))
+            if j < n_iter:
+                out[j] = i
         return out
 
     def candidates(self):
         if not self.estimator._randomized:
-            raise ValueError("RandomizedSearch searches RandomForest only")
+            raise ValueError("RandomizedSearch searches an estimator that the reference puts under RandomizedSearchCV "
+                             "(RandomForest, SVC with the rbf kernel), got %r" % (self.estimator,))
+        size = self.grid_size()
+        if self.estimator._tracking_draws_only and not (1 <= min(self.n_iter, size) and min(self.n_iter, size) / size < self.TRACKING_RATIO):
+            raise ValueError("RandomizedSearch draws this estimator's candidates as scikit-learn does for n_iter / grid size < %g only: "
+                             "n_iter must be 1..%d for this grid of %d points, got %d"
+                             % (self.TRACKING_RATIO, self.max_n_iter(size), size, self.n_iter))
         return [self.grid_point(i) for i in self.sampled_indices()]
 
     def _sk_params(self):

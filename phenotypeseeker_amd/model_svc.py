@@ -2,7 +2,7 @@
 import numpy as np
 
 from . import cv as _cv
-from .model_search import _Estimator, _Twin, _fold_scores, _launch_plan_of_numbers
+from .model_search import _Estimator, _Twin, _fold_scores, _launch_plan, _launch_plan_of_numbers
 
 
 class SVC(_Estimator):
@@ -11,17 +11,26 @@ class SVC(_Estimator):
     Fitted attributes carry scikit-learn's sign and order (class 0's support vectors first; decision_function is the
     negative of libsvm's value; dual_coef_ = -y_i alpha_i; intercept_ = rho).  probability=True: libsvm fits the Platt
     sigmoid on decision values of an internal 5-fold split drawn from an unseeded generator; here the split is
-    cv.stratified_kfold(y, 5), so the pair (probA_, probB_) is the same in every run."""
+    cv.stratified_kfold(y, 5), so the pair (probA_, probB_) is the same in every run.
+    kernel='rbf' is searched over {'C', 'gamma'} by RandomizedSearch, as the reference's get_best_model does (:1091-1095);
+    random_state is that search's seed and no parameter of the exported scikit-learn SVC.  decision_function, predict and
+    predict_proba take an optional engine context: the decision values then come from psk_svc_decision."""
     _is_classifier = True
     _warns_at_max_iter = True   # scikit-learn's ConvergenceWarning when a fit stops there
     PLATT_FOLDS = 5
 
-    def __init__(self, C=1.0, kernel="rbf", gamma="scale", tol=1e-3, max_iter=-1, probability=False):
+    def __init__(self, C=1.0, kernel="rbf", gamma="scale", tol=1e-3, max_iter=-1, probability=False, random_state=None):
         if kernel not in ("linear", "rbf"):
             raise ValueError("SVC: kernel must be 'linear' or 'rbf', got %r" % (kernel,))
         self.C, self.kernel, self.gamma, self.tol, self.max_iter, self.probability = C, kernel, gamma, tol, max_iter, probability
+        self.random_state = random_state
         self.classes_ = np.array([0, 1])
         self.support_ = None
+
+    @property
+    def _randomized(self):
+        """The reference puts the rbf kernel under RandomizedSearchCV, the linear one under GridSearchCV (:1086-1095)."""
+        return self.kernel == "rbf"
 
     def __repr__(self):
         parts = []
@@ -41,7 +50,7 @@ class SVC(_Estimator):
 
     def _clone(self, **params):
         kw = dict(C=self.C, kernel=self.kernel, gamma=self.gamma, tol=self.tol, max_iter=self.max_iter,
-                  probability=self.probability)
+                  probability=self.probability, random_state=self.random_state)
         kw.update(params)
         return type(self)(**kw)
 
@@ -57,12 +66,14 @@ class SVC(_Estimator):
             raise ValueError("SVC: gamma must be 'scale', 'auto' or a number, got %r" % (self.gamma,))
         return float(self.gamma)
 
-    def _engine_fit(self, ctx, X, y, folds, fit_param, fit_fold):
+    def _engine_fit(self, ctx, X, y, folds, fit_param, fit_fold, fit_gamma=None):
+        """fit_gamma: one gamma per fit (a search over 'gamma'); None: this estimator's own for every fit."""
         y = np.asarray(y)
         if sorted(set(y.tolist())) != [0, 1]:
             raise ValueError("SVC: the two classes must be labelled 0 and 1")
         return ctx.svc_fit(X, y.astype(np.int32), folds, fit_param, fit_fold, kernel=self.kernel,
-                           fit_gamma=self._gamma_value(X), tol=self.tol, max_iter=int(self.max_iter))
+                           fit_gamma=self._gamma_value(X) if fit_gamma is None else fit_gamma, tol=self.tol,
+                           max_iter=int(self.max_iter))
 
     def fit(self, X, y, engine_ctx):
         X = np.asarray(X, dtype=np.float64)
@@ -96,9 +107,18 @@ class SVC(_Estimator):
 
     def _search(self, ctx, X, y, folds, cand, cv):
         """Every candidate x fold and every candidate's refit in one launch; a fold is scored from the decision values the
-        engine returns for every sample, held-out ones included."""
-        fit_param, fit_fold = _launch_plan_of_numbers(cand, cv)
-        dual, rho, dec, iters = self._engine_fit(ctx, X, y, folds, fit_param, fit_fold)
+        engine returns for every sample, held-out ones included.  Candidates over 'C', or over 'C' and 'gamma' (the rbf
+        kernel's grid, :1050-1056): then every fit carries its own gamma, and the refit's Platt step the chosen pair."""
+        if all(set(q) == {"C", "gamma"} for q in cand):
+            if self.kernel != "rbf":
+                raise ValueError("SVC: a grid over 'gamma' needs kernel='rbf'")
+            fit_q, fit_fold = _launch_plan(cand, cv)
+            fit_param, fit_gamma = [float(q["C"]) for q in fit_q], [float(q["gamma"]) for q in fit_q]
+        elif all(set(q) == {"C"} for q in cand):
+            (fit_param, fit_fold), fit_gamma = _launch_plan_of_numbers(cand, cv), None
+        else:
+            raise ValueError("SVC is searched over 'C', or over 'C' and 'gamma'")
+        dual, rho, dec, iters = self._engine_fit(ctx, X, y, folds, fit_param, fit_fold, fit_gamma)
         scores = _fold_scores(cand, cv, folds, lambda q, j, te: np.mean(self.classes_[(dec[j][te] <= 0).astype(int)] == y[te]))
 
         def refit(best):
@@ -135,8 +155,20 @@ class SVC(_Estimator):
         sx, ss = (X * X).sum(axis=1), (self.support_vectors_ * self.support_vectors_).sum(axis=1)
         return np.exp(-self._gamma * (sx[:, None] + ss[None, :] - 2 * D))
 
-    def _libsvm_decision(self, X):
-        """sum_j y_j alpha_j K(x_j, x) - rho, the support vectors added one after the other as svm_predict_values does."""
+    def _on_device(self, X):
+        """psk_svc_decision takes float32: whether X and the support vectors survive the round trip (what this package
+        writes always does)."""
+        X = np.asarray(X, dtype=np.float64)
+        return bool(X.ndim == 2 and X.shape[0] >= 1 and X.shape[1] == self.support_vectors_.shape[1] and len(self.support_)
+                    and np.array_equal(X.astype(np.float32).astype(np.float64), X)
+                    and np.array_equal(self.support_vectors_.astype(np.float32).astype(np.float64), self.support_vectors_))
+
+    def _libsvm_decision(self, X, engine_ctx=None):
+        """sum_j y_j alpha_j K(x_j, x) - rho, the support vectors added one after the other as svm_predict_values does; with
+        an engine context on the device (psk_svc_decision), in the same order."""
+        if engine_ctx is not None and self._on_device(X):
+            return engine_ctx.svc_decision(X, self.support_vectors_, -self.dual_coef_[0], self.intercept_[0], kernel=self.kernel,
+                                           gamma=self._gamma if self.kernel == "rbf" else 0.0)
         K = self._kernel(X)
         coef = -self.dual_coef_[0]
         s = np.zeros(K.shape[0])
@@ -144,12 +176,12 @@ class SVC(_Estimator):
             s += coef[j] * K[:, j]
         return s - self.intercept_[0]
 
-    def decision_function(self, X):
-        return -self._libsvm_decision(X)
+    def decision_function(self, X, engine_ctx=None):
+        return -self._libsvm_decision(X, engine_ctx)
 
-    def predict(self, X):
+    def predict(self, X, engine_ctx=None):
         # libsvm votes the second class on a decision value of zero
-        return self.classes_[(self._libsvm_decision(X) <= 0).astype(int)]
+        return self.classes_[(self._libsvm_decision(X, engine_ctx) <= 0).astype(int)]
 
     def score(self, X, y):
         return np.float64(np.mean(self.predict(X) == np.asarray(y)))
@@ -177,10 +209,10 @@ class SVC(_Estimator):
         self.probA_, self.probB_ = np.array([A]), np.array([B])
         return self
 
-    def predict_proba(self, X):
+    def predict_proba(self, X, engine_ctx=None):
         if not len(getattr(self, "probA_", ())):
             raise AttributeError("predict_proba is not available when probability=False")
-        return platt_predict_proba(self._libsvm_decision(X), self.probA_[0], self.probB_[0])
+        return platt_predict_proba(self._libsvm_decision(X, engine_ctx), self.probA_[0], self.probB_[0])
 
 
 def platt_sigmoid_train(dec, positive):

@@ -281,6 +281,7 @@ class RandomForest(_Estimator):
     holds k-mer counts (psk_forest_fit_counts), the engine switch of DecisionTree."""
     _is_classifier = True
     _randomized = True        # the reference searches its forest with RandomizedSearchCV (modeling.py:1096-1099)
+    _tracking_draws_only = True    # ... with n_iter / grid size < 0.01, the range its search has always taken
     PARAMS = ("bootstrap", "criterion", "max_depth", "max_features", "min_samples_leaf", "min_samples_split", "n_estimators")
     DEFAULTS = dict(bootstrap=True, criterion="gini", max_depth=None, max_features="sqrt", min_samples_leaf=1, min_samples_split=2,
                     n_estimators=100)

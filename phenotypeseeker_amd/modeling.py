@@ -344,8 +344,8 @@ class Input:
                    real_counts, omit_B, kmerDB):
         """Same positional signature as the reference (:141-183).  Options that select estimators
         outside the hot path (SVM/RF/DT/NB, L2/elastic net, saga, PCA) are rejected here; `-bc SVM`, `-bc DT`, `-bc RF` and
-        `-bc NB` pass with their knobs (PSK_SVM, PSK_DT, PSK_RF, PSK_NB), `--pca` with PSK_PCA for a binary phenotype under
-        `-bc log` and `-bc SVM`."""
+        `-bc NB` pass with their knobs (PSK_SVM, PSK_DT, PSK_RF, PSK_NB; `--kernel rbf` with PSK_SVM_RBF as well), `--pca` with
+        PSK_PCA for a binary phenotype under `-bc log` and `-bc SVM`."""
         if alphas is None:
             phenotypes.alphas = np.logspace(math.log10(alpha_min), math.log10(alpha_max), num=n_alphas)
         else:
@@ -378,9 +378,21 @@ class Input:
             phenotypes.binary_classifier = "log"
             if binary_classifier == "SVM" and _lib.env_flag("PSK_SVM"):
                 # set_model (:1025-1029): SVC(kernel, probability=True) over C = 1 / alphas.  The reference searches the rbf
-                # kernel with an unseeded RandomizedSearchCV (:1091-1095): not offered from the command line
-                if kernel != "linear":
+                # kernel over C and gamma = 1 / gammas with an unseeded RandomizedSearchCV(n_iter, cv) (:1050-1056, :1091-1095):
+                # offered with PSK_SVM_RBF, the seed is PSK_SVM_SEED and the run is scikit-learn's for that seed
+                if kernel != "linear" and not (kernel == "rbf" and _lib.env_flag("PSK_SVM_RBF")):
                     raise SystemExit("The support vector machine on the GPU engine takes --kernel linear only, got %r." % kernel)
+                if kernel == "rbf":
+                    phenotypes.svm_seed = _svm_seed()
+                    phenotypes.n_iter = int(n_iter)
+                    if phenotypes.n_iter < 1:
+                        raise SystemExit("The support vector machine's randomized search needs --n_iter of at least 1, got %d."
+                                         % phenotypes.n_iter)
+                    # _get_gammas (:221-231)
+                    if gammas is None:
+                        phenotypes.gammas = np.logspace(math.log10(gamma_min), math.log10(gamma_max), num=n_gammas)
+                    else:
+                        phenotypes.gammas = np.array(gammas)
                 phenotypes.binary_classifier, phenotypes.kernel = "SVM", kernel
                 phenotypes.model_name_long, phenotypes.model_name_short = "support vector machine", "SVM"
             elif binary_classifier == "DT" and _lib.env_flag("PSK_DT"):
@@ -461,14 +473,23 @@ RF_GRID = {"bootstrap": [True, False], "max_depth": [4, 5, 6, 7, 8, 10, 20, 100,
            "n_estimators": [10, 20, 40, 60, 80, 100, 120, 140, 160, 180, 200], "criterion": ["gini", "entropy"]}
 
 
-def _rf_seed():
-    """PSK_RF_SEED (docs/KNOBS.md): the random_state of the forest and of its randomized search, 0 .. 2^32 - 1."""
-    text = os.environ.get("PSK_RF_SEED", "")
+def _seed_value(name, text):
+    """The value of a seed knob (docs/KNOBS.md): an integer 0 .. 2^32 - 1, 0 when unset."""
     if text == "":
         return 0
     if not text.isdigit() or int(text) > 0xFFFFFFFF:
-        raise SystemExit("PSK_RF_SEED must be an integer 0 .. 4294967295, got %r." % text)
+        raise SystemExit("%s must be an integer 0 .. 4294967295, got %r." % (name, text))
     return int(text)
+
+
+def _rf_seed():
+    """PSK_RF_SEED: the random_state of the forest and of its randomized search."""
+    return _seed_value("PSK_RF_SEED", os.environ.get("PSK_RF_SEED", ""))
+
+
+def _svm_seed():
+    """PSK_SVM_SEED: the random_state of the randomized search of `-bc SVM --kernel rbf`."""
+    return _seed_value("PSK_SVM_SEED", os.environ.get("PSK_SVM_SEED", ""))
 
 
 class phenotypes:
@@ -485,6 +506,8 @@ class phenotypes:
     kernel = None
     n_iter = None
     rf_seed = 0
+    svm_seed = 0
+    gammas = None
     logreg_solver = None
     max_iter = None
     tol = None
@@ -742,6 +765,10 @@ class phenotypes:
                 return RandomForest(random_state=self.rf_seed, counts=bool(self.real_counts)), {k: list(v) for k, v in RF_GRID.items()}, None
             if self.binary_classifier == "NB":
                 return BernoulliNB(), None, None
+            if self.binary_classifier == "SVM" and self.kernel == "rbf":
+                # set_hyperparameters (:1050-1056): {'C': 1 / alphas, 'gamma': 1 / gammas}, drawn from by RandomizedSearch
+                return (SVC(kernel="rbf", probability=True, max_iter=self.max_iter, tol=self.tol, random_state=self.svm_seed),
+                        {"C": grid, "gamma": [1.0 / g for g in self.gammas]}, None)
             if self.binary_classifier == "SVM":
                 return SVC(kernel=self.kernel, probability=True, max_iter=self.max_iter, tol=self.tol), "C", grid
             if self.penalty == "L2":
@@ -892,16 +919,23 @@ class phenotypes:
         self.pca_parts = {"scaler": scaler, "pca_model": pca, "PCs_to_keep": keep}     # (:1194, :1205-1206) this phenotype's, for its package
         return scores[:, keep].astype(np.float32).astype(np.float64)
 
+    @property
+    def _rbf_svm(self):
+        return self.pred_scale == "binary" and self.model_name_short == "SVM" and self.kernel == "rbf"
+
     def _write_pc_coefficients(self, path):
         """(:1415-1420, :1445-1450) one line per kept component, the numbers as an f-string formats a numpy.float64."""
         be = self.model_fitted.best_estimator_
-        coefs = np.ravel(be._coef_column if hasattr(be, "_coef_column") else be.coef_)
+        if self._rbf_svm:       # (:1440-1441) the literal NA
+            coefs = ["NA"] * len(self.PC["names"])
+        else:
+            coefs = [np.float64(c) for c in np.ravel(be._coef_column if hasattr(be, "_coef_column") else be.coef_)]
         pc = self.PC
         with open(path, "w") as out:
             out.write("PC\tcoef._in_" + self.model_name_short + "_model\texplained_variance\texplained_variance_ratio"
                       "\tt-test_statistic\tt-test_pvalue\n")
             for i, name in enumerate(pc["names"]):
-                out.write(f"{name}\t{np.float64(coefs[i])}\t{np.float64(pc['explained_variance'][i])}"
+                out.write(f"{name}\t{coefs[i]}\t{np.float64(pc['explained_variance'][i])}"
                           f"\t{np.float64(pc['explained_variance_ratio'][i])}\t{np.float64(pc['t'][i])}\t{np.float64(pc['p'][i])}\n")
 
     def _cross_validation_results(self, out):
@@ -985,9 +1019,9 @@ class phenotypes:
             return self._write_pc_coefficients(path)
         with open(path, "w") as out:
             out.write("K-mer\tcoef._in_" + self.model_name_short + "_model\tNo._of_samples_with_k-mer\tSamples_with_k-mer\n")
-            if self.model_name_short == "NB":
-                # the coefficient column is the literal NA (:1440-1441), which psk_write_model_coefficients' column of doubles
-                # cannot say: these lines are written here
+            if self.model_name_short == "NB" or self._rbf_svm:
+                # the coefficient column is the literal NA (:1440-1441: NB, and the rbf kernel, which has no coef_), which
+                # psk_write_model_coefficients' column of doubles cannot say: these lines are written here
                 Xn, names = np.asarray(self.ML["X"]).reshape(len(self.ML["index"]), len(self.ML["kmers"])), self.ML["index"]
                 for j, km in enumerate(self.ML["kmers"]):
                     who = [names[i] for i in np.nonzero(Xn[:, j] != 0)[0]]

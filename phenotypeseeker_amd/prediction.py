@@ -97,9 +97,15 @@ class Phenotypes:
 
     def predict(self, ctx=None):
         """predictions_<pheno>.txt (:165-182).  A naive-Bayes model of this package (what the stub reader makes of an NB file)
-        takes its joint log-likelihoods from the open context (psk_nb_jll); every other model predicts as before."""
+        takes its joint log-likelihoods from the open context (psk_nb_jll), a support vector machine of this package -- bare, or
+        the best_estimator_ of a search of this package -- its decision values (psk_svc_decision); every other model predicts
+        as before."""
         from .model_nb import BernoulliNB
-        on_device = (ctx,) if ctx is not None and isinstance(self.model, BernoulliNB) else ()
+        from .model_svc import SVC
+        model = self.model
+        if isinstance(getattr(model, "best_estimator_", None), SVC):
+            model = model.best_estimator_
+        on_device = (ctx,) if ctx is not None and isinstance(model, (BernoulliNB, SVC)) else ()
         design = self.matrix
         if self.pca:
             # (:155-163) scaler.transform, pca_model.transform, [:, PCs_to_keep]: one psk_pca_transform on the open context for
@@ -107,10 +113,10 @@ class Phenotypes:
             from . import model_pca
             scaler, pca_model, keep = self.projection
             design = model_pca.project(scaler, pca_model, self.matrix, keep, ctx).astype(np.float32).astype(np.float64)
-        predictions = self.model.predict(design, *on_device)
+        predictions = model.predict(design, *on_device)
         with open("predictions_" + self.name + ".txt", "w+") as out:
             if self.pred_scale == "binary":
-                proba = self.model.predict_proba(design, *on_device)
+                proba = model.predict_proba(design, *on_device)
                 out.write("Sample_ID\tpredicted_phenotype\tprobability_for_predicted_class\n")
                 for sample, pred, pr in zip(Input.samples.keys(), predictions, proba):
                     out.write("%s\t%s\t%s\n" % (sample, str(pred), str(round(pr[1], 2))))
