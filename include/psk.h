@@ -267,6 +267,29 @@ int psk_cx_pc_shape(uint64_t n_ov, uint64_t cap_blocks, uint32_t *blocks, uint64
  * no side-kernel plan, or the knob off), *rows_overflow = the rows of the side matrix; all 0 for a scan that did not
  * take the exception-coded path.  Measurement and tests only.  Any pointer may be NULL. */
 int psk_last_scan_filter(const psk_ctx *ctx, int *filtered, uint64_t *rows_feasible, uint64_t *rows_overflow);
+/* The kernel form of the last chi2 scan set up on the context: 0 dense, 1 the mixed exception-coded kernel, 2 the side
+ * matrix alone, 3 the side matrix through its popcounts, 4 the feasible rows of the side matrix through the index by
+ * popcount (forms 3 and 4 are both "filtered" to psk_last_scan_filter); -1 before any.  Measurement and tests only. */
+int psk_last_scan_form(const psk_ctx *ctx, int *form);
+/* Where a scan's feasible rows lie in the encoder's index of the side matrix by popcount (rows grouped by popcount, bucket
+ * pc starting at the exclusive prefix of pc_hist[0 .. n_hist)): the feasible (bit pc of feas[4]), non-empty buckets as
+ * ranges [begin[i], begin[i] + len[i]) of index positions, buckets that follow each other in the index merged.  *n_runs =
+ * all ranges there are, of which the first 4 are written (the rest of begin / len: 0); *rows = the rows in all of them;
+ * *chosen = 1 when a filtered scan of a side matrix of n_ov rows would run the index form: knob_on (PSK_CX_PC_INDEX),
+ * at most 4 ranges and rows x 8 <= n_ov.  rows and chosen may be NULL.  Host code: no context, no device. */
+int psk_cx_idx_plan(const uint64_t *feas /* [4] */, const uint64_t *pc_hist, int n_hist, uint64_t n_ov, int knob_on,
+                    uint64_t *begin /* [4] */, uint64_t *len /* [4] */, int *n_runs, uint64_t *rows, int *chosen);
+/* The launch shape of the index form (chi2_scan_kernel_cx_side_idx) for n_rows feasible rows: *blocks = what one row per
+ * thread needs, at least 1, at most cap_blocks -- NOT raised to the 256 result segments; workgroup b visits rows
+ * (p * blocks + b) * threads + thread in pass p; *rows_per_block = passes x *threads; *seg_cap = the entries of a result
+ * segment that follow.  threads and seg_cap may be NULL.  Host code: no context, no device. */
+int psk_cx_idx_shape(uint64_t n_rows, uint64_t cap_blocks, uint32_t *blocks, uint64_t *rows_per_block, uint32_t *threads,
+                     uint64_t *seg_cap);
+/* Debug read-back of the encoder's index (tests): the positions of the side-matrix rows grouped by popcount into
+ * index[0 .. cap) (cap >= the overflow rows of psk_compact_info; PSK_ERANGE otherwise) and the buckets' starts, the
+ * exclusive prefix of the popcount histogram, into pc_start[0 .. n_start), n_start <= n_samples + 2.  PSK_ESTATE when
+ * the matrix has no exception-coded copy.  Either pointer may be NULL. */
+int psk_cx_pc_index(psk_ctx *ctx, uint32_t *index, uint64_t cap, uint64_t *pc_start, int n_start);
 /* The plan of the last chi2 scan launched or repeated on the context: *encoded = 1 when it took the exception-coded path
  * (else the other two are 0), *class_mask as psk_cx_plan gives it, *slots_skipped = 1 when the launch read only the side
  * matrix of overflow rows.  Measurement and tests only.  Any pointer may be NULL. */

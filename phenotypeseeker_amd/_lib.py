@@ -70,6 +70,10 @@ _SIGNATURES = {
     "psk_cx_side_shape": (c.c_int, [c.c_uint64, c.c_int, c.c_uint64, c.POINTER(c.c_uint32), _u64p, c.POINTER(c.c_uint32)]),
     "psk_cx_pc_plan": (c.c_int, [c.c_int] * 5 + [c.c_double, _u64p]),
     "psk_cx_pc_shape": (c.c_int, [c.c_uint64, c.c_uint64, c.POINTER(c.c_uint32), _u64p, c.POINTER(c.c_uint32)]),
+    "psk_cx_idx_plan": (c.c_int, [_u64p, _u64p, c.c_int, c.c_uint64, c.c_int, _u64p, _u64p, c.POINTER(c.c_int), _u64p, c.POINTER(c.c_int)]),
+    "psk_cx_idx_shape": (c.c_int, [c.c_uint64, c.c_uint64, c.POINTER(c.c_uint32), _u64p, c.POINTER(c.c_uint32), _u64p]),
+    "psk_cx_pc_index": (c.c_int, [c.c_void_p, c.c_void_p, c.c_uint64, c.c_void_p, c.c_int]),
+    "psk_last_scan_form": (c.c_int, [c.c_void_p, c.POINTER(c.c_int)]),
     "psk_last_scan_filter": (c.c_int, [c.c_void_p, c.POINTER(c.c_int), _u64p, _u64p]),
     "psk_last_scan_plan": (c.c_int, [c.c_void_p, c.POINTER(c.c_int), c.POINTER(c.c_uint32), c.POINTER(c.c_int)]),
     "psk_last_scan_ms": (c.c_double, [c.c_void_p]),

@@ -264,7 +264,7 @@ extern "C" void psk_free(psk_ctx *ctx)
     DevBuf *bufs[] = {&ctx->raw, &ctx->keysA, &ctx->keysB, &ctx->valsA, &ctx->valsB, &ctx->hist, &ctx->scan_tmp, &ctx->flags, &ctx->starts,
                       &ctx->misc, &ctx->union_words, &ctx->bits, &ctx->mask1, &ctx->phe,
                       &ctx->slot[0].res, &ctx->slot[1].res, &ctx->res_count, &ctx->res_sorted, &ctx->lut, &ctx->bs_spl, &ctx->bs_ct,
-                      &ctx->cx_slots, &ctx->cx_ov, &ctx->cx_ov_row, &ctx->cx_ov_pc};
+                      &ctx->cx_slots, &ctx->cx_ov, &ctx->cx_ov_row, &ctx->cx_ov_pc, &ctx->cx_pc_index};
     for (DevBuf *b : bufs) dev_release(*b);
     lap("matrix, union, scan buffers released");
     if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream);

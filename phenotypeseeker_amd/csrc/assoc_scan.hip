@@ -9,6 +9,8 @@
 // ttest_scan_kernel  (ttest_scan.hip) replaces conduct_t_test / get_samples_distribution_for_ttest (:716-757)
 // chi2_scan_kernel_cx  the unweighted chi2 scan over the exception-coded copy of the matrix (presence_compact.hip), when
 //                      there is one: same survivors, a third of the bytes at config 2
+// chi2_scan_kernel_cx_side, ..._side_pc, ..._side_idx  the same scan when no slot row can pass: the side matrix alone, through
+//                      its popcounts, or -- few feasible rows -- through the encoder's index of its rows by popcount
 //
 // Layout: bits[M][wpr] u64, wpr even, so a row is wpr/2 16-byte chunks.  G = next power of two
 // >= wpr/2 lanes own one row; every lane issues one 16-byte load per row (global_load_dwordx4,
@@ -449,6 +451,67 @@ __global__ __launch_bounds__(SC_THREADS) void chi2_scan_kernel_cx_side_pc(const 
     publish_segment_once(X.s.sink);
 }
 
+// ---- the feasible rows of the side matrix through the encoder's index --------------------------------------------------
+// Which rows have a given popcount is a property of the matrix, so the encoder groups the side-matrix rows by popcount
+// once (cx_pc_index, presence_compact.hip) and a scan whose feasible popcounts hold few rows (cx_idx_chosen, chi2_plan.h)
+// visits those rows alone: the T rows of at most CX_IDX_RUNS ranges of the index, one per lane, grid-stride.  Lane t
+// finds its range against the running sums of run_len, loads j = idx[...], then the row's CPR chunks AND ov_row[j]
+// together (the row id does not wait for the decision: every row here is likely to be a candidate), counts against the
+// scalar mask words and decides as PcRows does: the candidate rule by hand in the same operations, chi2_keep.  At the
+// flagship every such row survives, so the appends are taken per wave: one atomicAdd of the keepers' number, each keeper
+// at base + its rank, clamped as reserve_slot clamps (an overflow still reaches the host as a count above seg_cap).
+// As many workgroups as the rows need: the segments beyond the grid are published by workgroup 0 before its rows.
+template <int CPR>
+__global__ __launch_bounds__(CX_IDX_THREADS) void chi2_scan_kernel_cx_side_idx(const CxSideIdxArgs X)
+{
+    const ScanCuts &K = X.s.cut;
+    const ScanSink &S = X.s.sink;
+    stamp_scan_start(S);
+    if (blockIdx.x == 0) publish_unowned_segments(S);
+    const int lane = threadIdx.x & 63;
+    const uint64_t e0 = X.run_len[0], e1 = e0 + X.run_len[1], e2 = e1 + X.run_len[2], T = e2 + X.run_len[3];
+    const uint32_t seg = blockIdx.x & (SC_NSEG - 1);
+    // (t0 is the workgroup's: whole waves walk the loop, the ballot below sees all 64 lanes)
+    for (uint64_t t0 = (uint64_t)blockIdx.x * CX_IDX_THREADS; t0 < T; t0 += (uint64_t)gridDim.x * CX_IDX_THREADS) {
+        const uint64_t t = t0 + threadIdx.x;
+        const bool live = t < T;
+        uint32_t a = 0, c = 0, row = 0;
+        if (live) {
+            const uint64_t pos = t < e0 ? X.run_begin[0] + t : t < e1 ? X.run_begin[1] + (t - e0) : t < e2 ? X.run_begin[2] + (t - e1) : X.run_begin[3] + (t - e2);
+            const uint64_t j = X.idx[pos];
+            u32x4 x[CPR];
+#pragma unroll
+            for (int g = 0; g < CPR; g++) x[g] = PSK_CX_SIDE_NT ? __builtin_nontemporal_load(&X.s.ov[j * CPR + g]) : X.s.ov[j * CPR + g];
+            row = X.s.ov_row[j];
+#pragma unroll
+            for (int g = 0; g < CPR; g++) {
+                const uint64_t xa = ((uint64_t)x[g].y << 32) | x[g].x, xb = ((uint64_t)x[g].w << 32) | x[g].z;
+                a += __popcll(xa & X.s.m1[2 * g]) + __popcll(xb & X.s.m1[2 * g + 1]);
+                c += __popcll(xa & X.s.m0[2 * g]) + __popcll(xb & X.s.m0[2 * g + 1]);
+            }
+        }
+        // by hand what chi2_candidate(K, a, c, live) does (see SideRows)
+        const int n_w = (int)(a + c);
+        const int n_wo = (K.n1 - (int)a) + (K.n0 - (int)c);
+        const bool freq_ok = live && !(n_w < K.min_samples || n_wo < 2 || n_w > K.max_samples);
+        const double A = (double)a, B = (double)(K.n1 - (int)a), C = (double)c, D = (double)(K.n0 - (int)c);
+        double stat = 0.0, p = 1.0;
+        bool keep = false;
+        if (freq_ok && chi2_pretest(A, B, C, D, K.thr)) keep = chi2_keep(K, A, B, C, D, stat, p);
+        const uint64_t keepers = __ballot(keep);
+        if (keepers) {   // wave-uniform
+            uint32_t base = 0;
+            if (lane == 0) base = atomicAdd(&S.counter[seg * SC_CNT_STRIDE], (uint32_t)__popcll(keepers));
+            base = __builtin_amdgcn_readfirstlane(base);
+            if (keep) {
+                const uint32_t idx = base + (uint32_t)__popcll(keepers & ((1ull << lane) - 1ull));
+                chi2_store(S, (uint64_t)seg * S.seg_cap + (idx < S.seg_cap ? idx : S.seg_cap - 1), row, stat, p, n_w);
+            }
+        }
+    }
+    publish_segment_once(S);
+}
+
 // Second pass of the weighted chi2 scan: one workgroup per result segment, one candidate per lane.  The 2 x 2 table is
 // summed again exactly as the reference does it (modeling.py:809-823: every sample in order adds its weight to ONE of
 // the four cells; here the other three get + 0.0, and a weight times 1.0 or 0.0 is exact, so one fma per cell IS that
@@ -549,6 +612,10 @@ void launch_chi2_any(psk_ctx *ctx, const Chi2Launch &L, TimedBy ev)
 {
     const hipStream_t st = ctx->stream;
     switch (L.form) {
+    case Chi2Form::CxSideIdx:
+        if (L.cpr == 1) launch_timed(chi2_scan_kernel_cx_side_idx<1>, L.grid, CX_IDX_THREADS, 0, st, ev, L.sidx);
+        else launch_timed(chi2_scan_kernel_cx_side_idx<2>, L.grid, CX_IDX_THREADS, 0, st, ev, L.sidx);
+        break;
     case Chi2Form::CxSidePc:
         if (L.cpr == 1) launch_timed(chi2_scan_kernel_cx_side_pc<1>, L.grid, SC_THREADS, 0, st, ev, L.side);
         else launch_timed(chi2_scan_kernel_cx_side_pc<2>, L.grid, SC_THREADS, 0, st, ev, L.side);

@@ -76,12 +76,13 @@ int fill_cx_args(psk_ctx *ctx, Chi2Launch &CL, int set)
 {
     CxScanArgs &x = CL.x;
     ScanArgs &a = x.s;
-    int side_on = 1, pc_on = 1;
+    int side_on = 1, pc_on = 1, idx_on = 1;
     PSK_TRY(env_choice(ctx, "PSK_CX_SIDE_KERNEL", {0, 1}, &side_on));
     PSK_TRY(env_choice(ctx, "PSK_CX_PC_FILTER", {0, 1}, &pc_on));
+    PSK_TRY(env_choice(ctx, "PSK_CX_PC_INDEX", {0, 1}, &idx_on));
     CxPlanKey key;
     key.M = a.M; key.n_ov = ctx->cx_n_ov; key.cap = scan_grid_cap(ctx); key.side_cap = cx_side_grid_cap(ctx);
-    key.pc_cap = cx_pc_grid_cap(ctx); key.pc_filter = pc_on;
+    key.pc_cap = cx_pc_grid_cap(ctx); key.pc_filter = pc_on; key.pc_index = idx_on;
     memcpy(&key.thr_bits, &a.cut.thr, 8);
     key.n1 = a.cut.n1; key.n0 = a.cut.n0; key.n_samples = ctx->n_samples; key.cpr = a.cpr;
     key.min_samples = a.cut.min_samples; key.max_samples = a.cut.max_samples; key.side_kernel = side_on;
@@ -98,7 +99,7 @@ int fill_cx_args(psk_ctx *ctx, Chi2Launch &CL, int set)
     x.class_mask = pl.class_mask; x.corner[0] = pl.corner[0]; x.corner[1] = pl.corner[1];
     x.slot_blocks = pl.slot_blocks; x.ov_blocks = pl.ov_blocks;
     ctx->cx_last_plan = true;
-    ctx->cx_last_filtered = pl.form == Chi2Form::CxSidePc;
+    ctx->cx_last_filtered = pl.form == Chi2Form::CxSidePc || pl.form == Chi2Form::CxSideIdx;   // (which of the two: psk_last_scan_form)
     ctx->cx_last_rows_feasible = pl.rows_feasible;
     ctx->cx_last_class_mask = pl.class_mask;
     ctx->cx_last_skipped = pl.slot_blocks == 0;
@@ -112,6 +113,11 @@ int fill_cx_args(psk_ctx *ctx, Chi2Launch &CL, int set)
         memcpy(sd.m0, a.m0_inl, sizeof(sd.m0));
         sd.cut = a.cut;
         sd.sink = a.sink;
+        if (pl.form == Chi2Form::CxSideIdx) {
+            CL.sidx.s = sd;
+            CL.sidx.idx = ctx->cx_pc_index.as<uint32_t>();
+            for (int r = 0; r < CX_IDX_RUNS; r++) { CL.sidx.run_begin[r] = (uint32_t)pl.runs.begin[r]; CL.sidx.run_len[r] = (uint32_t)pl.runs.len[r]; }
+        }
     }
     return PSK_OK;
 }
@@ -123,12 +129,18 @@ int fill_chi2_args(psk_ctx *ctx, Chi2Launch &CL, int set, bool build_tables)
 {
     const ScanParams &L = ctx->last;
     ScanArgs &a = CL.x.s;
+    ctx->last_form = -1;
     fill_common_args(ctx, a);
     ScanShape sh;   // weighted: class-weight sums from a table in LDS (e0 = class 1, e1 = class 0)
     PSK_TRY(setup_table_scan(ctx, a, L.weighted ? a.tab : nullptr, 2, L.W1, L.W0, 0.0, build_tables, &sh));
     ctx->cx_last_plan = false;
-    if (ctx->cx_valid && !L.weighted && L.inline_masks && !env_flag("PSK_SCAN_DENSE")) return fill_cx_args(ctx, CL, set);
+    if (ctx->cx_valid && !L.weighted && L.inline_masks && !env_flag("PSK_SCAN_DENSE")) {
+        PSK_TRY(fill_cx_args(ctx, CL, set));
+        ctx->last_form = (int)CL.form;
+        return PSK_OK;
+    }
     CL.form = Chi2Form::Dense;
+    ctx->last_form = (int)CL.form;
     PSK_TRY(pick_chi2_mode(ctx, L.weighted, a.cut.pcut, a.cut.pcut_bonf, a.cut.omit_B, &CL.mode));
     CL.grid = sh.grid;
     return setup_results(ctx, a, CL.grid, group_lanes(a), sh.unroll, set, sh.threads);
@@ -364,6 +376,37 @@ extern "C" int psk_cx_pc_shape(uint64_t n_ov, uint64_t cap_blocks, uint32_t *blo
     *blocks = sh.blocks;
     *rows_per_block = sh.rows_per_block;
     if (batch_rows) *batch_rows = sh.batch_rows;
+    return PSK_OK;
+}
+
+extern "C" int psk_cx_idx_plan(const uint64_t *feas, const uint64_t *pc_hist, int n_hist, uint64_t n_ov, int knob_on, uint64_t *begin,
+                               uint64_t *len, int *n_runs, uint64_t *rows, int *chosen)
+{
+    if (!feas || !pc_hist || n_hist < 0 || !begin || !len || !n_runs) return PSK_EINVAL;
+    const cx_idx_runs_t r = cx_idx_runs(feas, pc_hist, (size_t)n_hist);
+    for (int i = 0; i < CX_IDX_RUNS; i++) { begin[i] = r.begin[i]; len[i] = r.len[i]; }
+    *n_runs = r.n;
+    if (rows) *rows = r.rows;
+    if (chosen) *chosen = cx_idx_chosen(r, n_ov, knob_on) ? 1 : 0;
+    return PSK_OK;
+}
+
+extern "C" int psk_cx_idx_shape(uint64_t n_rows, uint64_t cap_blocks, uint32_t *blocks, uint64_t *rows_per_block, uint32_t *threads,
+                                uint64_t *seg_cap)
+{
+    if (cap_blocks < 1 || cap_blocks > 0xffffffffull || !blocks || !rows_per_block) return PSK_EINVAL;
+    const cx_side_shape_t sh = cx_idx_shape(n_rows, cap_blocks);
+    *blocks = sh.blocks;
+    *rows_per_block = sh.rows_per_block;
+    if (threads) *threads = sh.batch_rows;
+    if (seg_cap) *seg_cap = result_seg_cap((uint64_t)sh.blocks, sh.rows_per_block);
+    return PSK_OK;
+}
+
+extern "C" int psk_last_scan_form(const psk_ctx *ctx, int *form)
+{
+    if (!ctx || !form) return PSK_EINVAL;
+    *form = ctx->last_form;
     return PSK_OK;
 }
 

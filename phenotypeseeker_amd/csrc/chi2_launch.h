@@ -33,9 +33,17 @@ struct CxSidePcArgs {
 };
 static_assert(sizeof(CxSidePcArgs) <= 256, "chi2_scan_kernel_cx_side_pc's arguments are meant to stay small");
 
+struct CxSideIdxArgs {
+    CxSideArgs s;
+    const uint32_t *idx;         // positions of the side-matrix rows, grouped by popcount (cx_pc_index)
+    uint32_t run_begin[CX_IDX_RUNS], run_len[CX_IDX_RUNS];   // the ranges of idx that hold the feasible rows (cx_idx_runs); unused: len 0
+};
+static_assert(sizeof(CxSideIdxArgs) <= 256, "chi2_scan_kernel_cx_side_idx's arguments are meant to stay small");
+
 struct Chi2Launch {
     CxScanArgs x;        // x.s: every form's arguments; the rest: chi2_scan_kernel_cx's (CxMixed)
     CxSidePcArgs side;   // side.s: chi2_scan_kernel_cx_side's (CxSide); all of it: ..._side_pc's (CxSidePc)
+    CxSideIdxArgs sidx;  // chi2_scan_kernel_cx_side_idx's (CxSideIdx)
     Chi2Form form = Chi2Form::Dense;
     int mode = 0;        // of the dense kernels (pick_chi2_mode)
     int cpr = 0;

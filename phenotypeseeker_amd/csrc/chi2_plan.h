@@ -140,6 +140,16 @@ constexpr int CX_UNROLL = PSK_CX_UNROLL;             // chi2_scan_kernel_cx: 16-
 constexpr int CX_SIDE_UNROLL = PSK_CX_SIDE_UNROLL;   // ..._cx_side: 16-byte loads in flight per lane and register set
 constexpr int CX_PC_UNROLL = PSK_CX_PC_UNROLL;       // ..._cx_side_pc: 2-byte loads in flight per lane and register set
 static_assert(CX_PC_UNROLL == 4 || CX_PC_UNROLL == 8, "a batch is 256 or 512 rows");
+#ifndef PSK_CX_IDX_THREADS
+#define PSK_CX_IDX_THREADS 64   // threads per workgroup of chi2_scan_kernel_cx_side_idx (r25 table: 64 against 256)
+#endif
+#ifndef PSK_CX_IDX_SHARE
+#define PSK_CX_IDX_SHARE 8      // the index form runs when rows_feasible * CX_IDX_SHARE <= n_ov (r25 table)
+#endif
+constexpr int CX_IDX_THREADS = PSK_CX_IDX_THREADS;   // ..._cx_side_idx: one feasible row per lane and pass
+static_assert(CX_IDX_THREADS == 64 || CX_IDX_THREADS == 256, "whole waves, at most a scan workgroup");
+constexpr uint64_t CX_IDX_SHARE = PSK_CX_IDX_SHARE;
+constexpr int CX_IDX_RUNS = 4;                       // index ranges the kernel's arguments hold
 constexpr int CX_WAVES = 4;                          // waves per workgroup (SC_THREADS / 64)
 constexpr int CX_NSEG = 256;                         // SC_NSEG: every result segment needs a workgroup to publish its count
 
@@ -198,6 +208,61 @@ inline cx_side_shape_t cx_pc_shape(uint64_t n_ov, uint64_t cap_blocks)
     return s;
 }
 
+// The indexed sweep (chi2_scan_kernel_cx_side_idx): T rows -- the feasible ones, found through the encoder's index of
+// the side matrix by popcount -- one per lane, workgroup b taking rows (p * blocks + b) * CX_IDX_THREADS + thread of pass
+// p.  As many workgroups as the rows need and no more: NOT raised to CX_NSEG, the segments beyond the grid are
+// published by workgroup 0 (publish_unowned_segments, scan_common.h).  T = 0: one workgroup, which only publishes.
+inline cx_side_shape_t cx_idx_shape(uint64_t T, uint64_t cap_blocks)
+{
+    uint64_t blocks = (T + CX_IDX_THREADS - 1) / CX_IDX_THREADS;
+    if (blocks > cap_blocks) blocks = cap_blocks;
+    if (blocks < 1) blocks = 1;
+    const uint64_t per_pass = blocks * CX_IDX_THREADS;
+    const uint64_t passes = (T + per_pass - 1) / per_pass;
+    cx_side_shape_t s;
+    s.blocks = (uint32_t)blocks;
+    s.batch_rows = (uint32_t)CX_IDX_THREADS;
+    s.rows_per_block = passes * CX_IDX_THREADS;
+    return s;
+}
+
+// Where the feasible rows lie in the encoder's index (cx_pc_index: the side-matrix rows grouped by popcount, bucket pc
+// starting at the exclusive prefix of the histogram): the feasible, non-empty buckets as ranges [begin, begin + len) of
+// index positions.  Buckets that follow each other in the index are one range -- adjacent feasible buckets, and feasible
+// buckets with only empty ones between them.  n: all ranges there are; the first CX_IDX_RUNS of them are kept (a plan
+// with more is not an index plan).  rows: what they hold, the plan's rows_feasible.
+struct cx_idx_runs_t {
+    int n = 0;
+    uint64_t rows = 0;
+    uint64_t begin[CX_IDX_RUNS] = {0, 0, 0, 0}, len[CX_IDX_RUNS] = {0, 0, 0, 0};
+};
+inline cx_idx_runs_t cx_idx_runs(const uint64_t feas[4], const uint64_t *pc_hist, size_t n_hist)
+{
+    cx_idx_runs_t r;
+    uint64_t pos = 0, end = 0;   // start of bucket pc; end of the last range
+    for (size_t pc = 0; pc < n_hist; pc++) {
+        const uint64_t h = pc_hist[pc];
+        if (h && pc < 256 && ((feas[pc >> 6] >> (pc & 63)) & 1ull)) {
+            if (r.n > 0 && end == pos) {
+                if (r.n <= CX_IDX_RUNS) r.len[r.n - 1] += h;
+            } else {
+                if (r.n < CX_IDX_RUNS) { r.begin[r.n] = pos; r.len[r.n] = h; }
+                r.n++;
+            }
+            end = pos + h;
+            r.rows += h;
+        }
+        pos += h;
+    }
+    return r;
+}
+
+// the index form is worth its launch: few ranges, and few rows against what the popcount filter would read past
+inline bool cx_idx_chosen(const cx_idx_runs_t &r, uint64_t n_ov, int knob_on)
+{
+    return knob_on && r.n <= CX_IDX_RUNS && r.rows * CX_IDX_SHARE <= n_ov;
+}
+
 struct cx_mixed_shape_t {
     uint32_t slot_blocks;     // workgroups [0, slot_blocks) stream the slots (none when no class is feasible),
     uint32_t ov_blocks;       // the next ov_blocks the side matrix; any beyond only publish their segment
@@ -243,20 +308,21 @@ inline cx_mixed_shape_t cx_mixed_shape(uint64_t M, uint64_t n_ov, int cpr, uint6
 }
 
 // ---- the plan of an exception-coded scan, kept from scan to scan ------------------------------------------------------
-// The four kernel forms of a chi2 scan: the dense kernels (chi2_scan_kernel and, weighted, its finalize pass), and over
-// the exception-coded copy the mixed kernel, the side matrix alone, and the side matrix through its popcounts.
-enum class Chi2Form { Dense, CxMixed, CxSide, CxSidePc };
+// The five kernel forms of a chi2 scan: the dense kernels (chi2_scan_kernel and, weighted, its finalize pass), and over
+// the exception-coded copy the mixed kernel, the side matrix alone, the side matrix through its popcounts, and the
+// feasible rows of the side matrix through the encoder's index by popcount.  (psk_last_scan_form reports the value.)
+enum class Chi2Form { Dense, CxMixed, CxSide, CxSidePc, CxSideIdx };
 
 // Everything a plan is a function of -- none of it derived from WHICH samples are cases.  A scan with another key
 // recomputes; a new matrix or encoded copy drops the plan.  (cpr follows from n_samples: it is here as an input.)
 struct CxPlanKey {
     uint64_t M = 0, n_ov = 0, cap = 0, side_cap = 0, pc_cap = 0, thr_bits = 0;
-    int n1 = 0, n0 = 0, n_samples = 0, cpr = 0, min_samples = 0, max_samples = 0, side_kernel = 0, pc_filter = 0;
+    int n1 = 0, n0 = 0, n_samples = 0, cpr = 0, min_samples = 0, max_samples = 0, side_kernel = 0, pc_filter = 0, pc_index = 0;
     bool operator==(const CxPlanKey &o) const
     {
         return M == o.M && n_ov == o.n_ov && cap == o.cap && side_cap == o.side_cap && pc_cap == o.pc_cap && thr_bits == o.thr_bits &&
                n1 == o.n1 && n0 == o.n0 && n_samples == o.n_samples && cpr == o.cpr && min_samples == o.min_samples &&
-               max_samples == o.max_samples && side_kernel == o.side_kernel && pc_filter == o.pc_filter;
+               max_samples == o.max_samples && side_kernel == o.side_kernel && pc_filter == o.pc_filter && pc_index == o.pc_index;
     }
 };
 struct CxPlan {
@@ -271,11 +337,13 @@ struct CxPlan {
     // have one (the encoder's histogram)
     uint64_t feas[4] = {0, 0, 0, 0};
     uint64_t rows_feasible = 0;
+    cx_idx_runs_t runs;              // CxSideIdx: where those rows lie in the index (cx_idx_runs)
 };
 
 // The plan for `key`.  The side matrix alone (CxSide) when the knob allows it and no header class is feasible; through its
 // popcounts (CxSidePc) when, in addition, the filter knob is on and the histogram (pc_hist[pc], pc < n_hist: side-matrix
-// rows of that popcount) says fewer than all rows can pass; else the mixed kernel.
+// rows of that popcount) says fewer than all rows can pass; of those plans, through the index (CxSideIdx) when the index
+// knob is on and the feasible rows are few and lie in few ranges (cx_idx_chosen); else the mixed kernel.
 inline CxPlan cx_make_plan(const CxPlanKey &key, const uint64_t *pc_hist, size_t n_hist)
 {
     CxPlan pl;
@@ -296,6 +364,10 @@ inline CxPlan cx_make_plan(const CxPlanKey &key, const uint64_t *pc_hist, size_t
         filtered = true;
 #endif
         if (filtered) pl.form = Chi2Form::CxSidePc;
+        if (filtered && key.pc_index) {
+            const cx_idx_runs_t r = cx_idx_runs(pl.feas, pc_hist, n_hist);
+            if (cx_idx_chosen(r, key.n_ov, key.pc_index)) { pl.form = Chi2Form::CxSideIdx; pl.runs = r; }
+        }
     }
     uint64_t rows_per_block;
     if (pl.form == Chi2Form::CxMixed) {
@@ -303,7 +375,8 @@ inline CxPlan cx_make_plan(const CxPlanKey &key, const uint64_t *pc_hist, size_t
         pl.grid = sh.blocks; pl.slot_blocks = sh.slot_blocks; pl.ov_blocks = sh.ov_blocks;
         rows_per_block = sh.rows_per_block;
     } else {
-        const cx_side_shape_t sh = pl.form == Chi2Form::CxSidePc ? cx_pc_shape(key.n_ov, key.pc_cap) : cx_side_shape(key.n_ov, key.cpr, key.side_cap);
+        const cx_side_shape_t sh = pl.form == Chi2Form::CxSideIdx ? cx_idx_shape(pl.runs.rows, key.pc_cap)
+                                   : pl.form == Chi2Form::CxSidePc ? cx_pc_shape(key.n_ov, key.pc_cap) : cx_side_shape(key.n_ov, key.cpr, key.side_cap);
         pl.grid = sh.blocks; pl.slot_blocks = 0; pl.ov_blocks = sh.blocks;
         rows_per_block = sh.rows_per_block;
     }

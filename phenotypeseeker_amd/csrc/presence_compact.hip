@@ -12,7 +12,10 @@
 // Beside each side-matrix row the encoder keeps its popcount (cx_ov_pc, u16) and, on the host, how many rows have each
 // popcount (cx_pc_hist): a scan's parameters rule out whole popcounts (cx_pc_plan, chi2_plan.h), and the scan then
 // reads 2 bytes of such a row instead of the row.
-// PSK_TRACE=1 prints the decision, the time of the build and the popcounts' non-zero range.
+// Which rows have a given popcount is the matrix's too, so the encoder also groups the rows' positions by popcount
+// (cx_pc_index, u32; bucket pc starts at the exclusive prefix of the histogram, cx_pc_start on the host): a scan whose
+// feasible popcounts hold few rows visits those alone (chi2_scan_kernel_cx_side_idx).
+// PSK_TRACE=1 prints the decision, the time of the build, the popcounts' non-zero range and the time of the index.
 #include "dev_utils.h"
 #include "psk_internal.h"
 
@@ -111,6 +114,52 @@ __global__ __launch_bounds__(CX_THREADS) void cx_pc_hist_kernel(const uint16_t *
         if (s_hist[i]) atomicAdd(&hist[i], s_hist[i]);
 }
 
+// cursor[pc] = rows of a smaller popcount: the exclusive scan of the histogram, one workgroup (bin 256, the last, starts
+// at the total of the others)
+static_assert(CX_HIST_BINS == CX_THREADS + 1, "one bin per thread and the last from the total");
+__global__ __launch_bounds__(CX_THREADS) void cx_pc_start_kernel(const uint32_t *__restrict__ hist, uint32_t *__restrict__ cursor)
+{
+    __shared__ uint32_t s_wave[CX_THREADS / 64];
+    uint32_t total;
+    const uint32_t pos = psk_block_excl_scan_u32<CX_THREADS>(hist[threadIdx.x], &total, s_wave);
+    cursor[threadIdx.x] = pos;
+    if (threadIdx.x == 0) cursor[CX_THREADS] = total;
+}
+
+// index = the rows' positions grouped by popcount, as cx_pc_hist_kernel counts them: a workgroup histograms its tile of
+// CX_INDEX_TILE rows in LDS, reserves its share of every non-empty bucket with ONE global atomic per bin (the popcounts
+// pile into a few bins: one atomic per row on a bucket's cursor would serialise), and places its rows with the cursors
+// in LDS.  cursor: cx_pc_start_kernel's, so a bucket's last position is start + rows of that popcount - 1 < n_ov.
+constexpr int CX_INDEX_PER_THREAD = 16, CX_INDEX_TILE = CX_THREADS * CX_INDEX_PER_THREAD;
+__global__ __launch_bounds__(CX_THREADS) void cx_pc_index_kernel(const uint16_t *__restrict__ ov_pc, uint64_t n_ov, uint32_t *__restrict__ cursor,
+                                                                uint32_t *__restrict__ index)
+{
+    __shared__ uint32_t s_cur[CX_HIST_BINS];
+    for (int i = threadIdx.x; i < CX_HIST_BINS; i += CX_THREADS) s_cur[i] = 0;
+    __syncthreads();
+    const uint64_t j0 = (uint64_t)blockIdx.x * CX_INDEX_TILE + threadIdx.x;
+    uint32_t pc[CX_INDEX_PER_THREAD];
+#pragma unroll
+    for (int u = 0; u < CX_INDEX_PER_THREAD; u++) {
+        const uint64_t j = j0 + (uint64_t)u * CX_THREADS;
+        pc[u] = 0;
+        if (j < n_ov) {
+            const uint32_t v = ov_pc[j];
+            pc[u] = v < CX_HIST_BINS ? v : CX_HIST_BINS - 1;
+            atomicAdd(&s_cur[pc[u]], 1u);
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < CX_HIST_BINS; i += CX_THREADS)
+        if (s_cur[i]) s_cur[i] = atomicAdd(&cursor[i], s_cur[i]);
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < CX_INDEX_PER_THREAD; u++) {
+        const uint64_t j = j0 + (uint64_t)u * CX_THREADS;
+        if (j < n_ov) index[atomicAdd(&s_cur[pc[u]], 1u)] = (uint32_t)j;
+    }
+}
+
 }  // namespace
 
 void compact_release(psk_ctx *ctx)
@@ -119,7 +168,9 @@ void compact_release(psk_ctx *ctx)
     dev_release(ctx->cx_ov);
     dev_release(ctx->cx_ov_row);
     dev_release(ctx->cx_ov_pc);
+    dev_release(ctx->cx_pc_index);
     ctx->cx_pc_hist.clear();
+    ctx->cx_pc_start.clear();
     ctx->cx_valid = false;
     ctx->cx_n_ov = 0;
     ctx->cx_plan.valid = false;
@@ -138,7 +189,7 @@ int compact_encode(psk_ctx *ctx)
     }
     const auto t0 = std::chrono::steady_clock::now();
     const uint64_t nb = div_up(M, CX_THREADS);
-    PSK_TRY(dev_reserve(ctx, ctx->flags, std::max<uint64_t>(nb, CX_HIST_BINS) * 4));   // the counts, then the histogram
+    PSK_TRY(dev_reserve(ctx, ctx->flags, std::max<uint64_t>(nb, 2 * CX_HIST_BINS) * 4));   // the counts, then the histogram and the buckets' cursors
     PSK_TRY(dev_reserve(ctx, ctx->misc, 64));
     uint32_t *cnt = ctx->flags.as<uint32_t>(), *d_total = ctx->misc.as<uint32_t>() + 6;
     const uint64_t *bits = ctx->bits.as<uint64_t>();
@@ -160,6 +211,7 @@ int compact_encode(psk_ctx *ctx)
     PSK_TRY(dev_reserve(ctx, ctx->cx_ov, (n_ov ? n_ov : 1) * (uint64_t)wpr * 8));
     PSK_TRY(dev_reserve(ctx, ctx->cx_ov_row, (n_ov ? n_ov : 1) * 4ull));
     PSK_TRY(dev_reserve(ctx, ctx->cx_ov_pc, (n_ov ? n_ov : 1) * 2ull));
+    PSK_TRY(dev_reserve(ctx, ctx->cx_pc_index, (n_ov ? n_ov : 1) * 4ull));
     cx_encode_kernel<<<(unsigned)nb, CX_THREADS, 0, ctx->stream>>>(bits, M, wpr, n, cnt, ctx->cx_slots.as<uint64_t>(),
                                                                   ctx->cx_ov.as<uint64_t>(), ctx->cx_ov_row.as<uint32_t>(),
                                                                   ctx->cx_ov_pc.as<uint16_t>());
@@ -173,8 +225,27 @@ int compact_encode(psk_ctx *ctx)
         PSK_HIP(ctx, hipGetLastError());
     }
     PSK_HIP(ctx, hipMemcpyAsync(hist, cnt, sizeof(hist), hipMemcpyDeviceToHost, ctx->stream));
+    // the rows grouped by popcount, behind the histogram on the same stream: no host round trip of its own
+    std::chrono::steady_clock::time_point t_idx;
+    if (n_ov) {
+        if (trace) {
+            PSK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            t_idx = std::chrono::steady_clock::now();
+        }
+        uint32_t *cursor = cnt + CX_HIST_BINS;
+        cx_pc_start_kernel<<<1, CX_THREADS, 0, ctx->stream>>>(cnt, cursor);
+        PSK_HIP(ctx, hipGetLastError());
+        cx_pc_index_kernel<<<(unsigned)div_up(n_ov, CX_INDEX_TILE), CX_THREADS, 0, ctx->stream>>>(ctx->cx_ov_pc.as<uint16_t>(), n_ov, cursor,
+                                                                                                 ctx->cx_pc_index.as<uint32_t>());
+        PSK_HIP(ctx, hipGetLastError());
+    }
     PSK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (trace && n_ov)
+        fprintf(stderr, "[psk] compact rows: index by popcount of %llu rows in %.3f ms\n", (unsigned long long)n_ov,
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_idx).count());
     ctx->cx_pc_hist.assign(hist, hist + n + 1);
+    ctx->cx_pc_start.assign(n + 2, 0);
+    for (int pc = 0; pc <= n; pc++) ctx->cx_pc_start[pc + 1] = ctx->cx_pc_start[pc] + hist[pc];
     ctx->cx_n_ov = n_ov;
     ctx->cx_valid = true;
     if (trace) {
@@ -187,6 +258,21 @@ int compact_encode(psk_ctx *ctx)
             if (ctx->cx_pc_hist[pc]) { lo = std::min(lo, pc); hi = pc; }
         if (hi < 0) fprintf(stderr, "[psk] compact rows: no overflow row, empty popcount histogram\n");
         else fprintf(stderr, "[psk] compact rows: overflow rows have popcounts %d ... %d\n", lo, hi);
+    }
+    return PSK_OK;
+}
+
+extern "C" int psk_cx_pc_index(psk_ctx *ctx, uint32_t *index, uint64_t cap, uint64_t *pc_start, int n_start)
+{
+    if (!ctx) return PSK_EINVAL;
+    if (!ctx->cx_valid) return psk_fail(ctx, PSK_ESTATE, "the matrix has no exception-coded copy");
+    if (n_start < 0 || (size_t)n_start > ctx->cx_pc_start.size()) return psk_fail(ctx, PSK_EINVAL, "the index has %zu bucket starts", ctx->cx_pc_start.size());
+    if (pc_start) std::copy(ctx->cx_pc_start.begin(), ctx->cx_pc_start.begin() + n_start, pc_start);
+    if (index) {
+        if (cap < ctx->cx_n_ov) return psk_fail(ctx, PSK_ERANGE, "buffer too small: %llu < %llu", (unsigned long long)cap, (unsigned long long)ctx->cx_n_ov);
+        PSK_HIP(ctx, hipSetDevice(ctx->device));
+        PSK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (ctx->cx_n_ov) PSK_HIP(ctx, hipMemcpy(index, ctx->cx_pc_index.p, ctx->cx_n_ov * 4, hipMemcpyDeviceToHost));
     }
     return PSK_OK;
 }

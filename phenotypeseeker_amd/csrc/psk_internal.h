@@ -208,6 +208,8 @@ struct psk_ctx {
     DevBuf cx_slots, cx_ov, cx_ov_row;
     DevBuf cx_ov_pc;                 // u16 per side-matrix row: its popcount over the valid samples
     std::vector<uint64_t> cx_pc_hist;   // [n_samples + 1] side-matrix rows of each popcount (host copy, made by the encoder)
+    DevBuf cx_pc_index;              // u32 per side-matrix row: the rows' positions j grouped by cx_ov_pc[j], any order inside a bucket
+    std::vector<uint64_t> cx_pc_start;  // [n_samples + 2] exclusive prefix of cx_pc_hist: bucket pc is cx_pc_index[start[pc] .. start[pc + 1])
     bool cx_valid = false;
     uint64_t cx_n_ov = 0;
     // the plan of the last chi2 scan set up (cx_make_plan, chi2_plan.h): did it take the exception-coded path, which header
@@ -215,6 +217,7 @@ struct psk_ctx {
     bool cx_last_plan = false, cx_last_skipped = false, cx_last_filtered = false;
     uint64_t cx_last_rows_feasible = 0;
     uint32_t cx_last_class_mask = 0;
+    int last_form = -1;              // Chi2Form of the last chi2 scan set up (psk_last_scan_form); -1: none
     CxPlan cx_plan;                  // dropped wherever the matrix or its encoded copy changes (compact_release, compact_encode, psk_begin)
 
     // scan state

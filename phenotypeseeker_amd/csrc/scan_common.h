@@ -138,6 +138,19 @@ __device__ __forceinline__ void publish_segment_once(const ScanSink &S)
     }
 }
 
+// A launch of fewer than SC_NSEG workgroups (chi2_scan_kernel_cx_side_idx) has segments that no workgroup maps to:
+// [gridDim.x, SC_NSEG).  Nothing is appended to them, so their counter lines stand at zero as the last scan's publish left
+// them; every thread of ONE workgroup calls this and thread i publishes segments gridDim.x + i, + blockDim.x, ... as
+// empty -- the compact count, the clock word, the count word -- so a wave's stores are consecutive 8-byte words.  With
+// the owned segments' publish_segment_once this leaves a result set exactly as a launch of SC_NSEG workgroups does.
+__device__ __forceinline__ void publish_unowned_segments(const ScanSink &S)
+{
+    for (uint32_t seg = gridDim.x + threadIdx.x; seg < (uint32_t)SC_NSEG; seg += blockDim.x) {
+        S.final_counts[seg] = 0;
+        stamp_segment(S, seg, 0);
+    }
+}
+
 // ---- host functions that cross the units ----------------------------------------------------------------------------
 // scan_results.hip
 int mask_words(const psk_ctx *ctx);

@@ -378,6 +378,20 @@ class PskContext:
                     "psk_last_scan_filter")
         return bool(filt.value), feas.value, n_ov.value
 
+    def last_scan_form(self):
+        """Kernel form of the last chi2 scan set up (psk_last_scan_form): one of SCAN_FORMS"""
+        form = ctypes.c_int()
+        self._check(self._lib.psk_last_scan_form(self._h, ctypes.byref(form)), "psk_last_scan_form")
+        return SCAN_FORMS[form.value] if form.value >= 0 else None
+
+    def cx_pc_index(self):
+        """(positions of the side-matrix rows grouped by popcount, u32 [n_ov]; starts of the buckets, u64 [n_samples + 2]):
+        the encoder's index as the device holds it (psk_cx_pc_index; tests)"""
+        enc, n_ov = self.compact_info()
+        index, start = np.zeros(max(n_ov, 1), np.uint32), np.zeros(self.n_samples + 2, np.uint64)
+        self._check(self._lib.psk_cx_pc_index(self._h, _ptr(index), n_ov, _ptr(start), len(start)), "psk_cx_pc_index")
+        return index[:n_ov], start
+
     def last_scan_ms(self):
         return self._lib.psk_last_scan_ms(self._h)
 
@@ -749,6 +763,37 @@ def frame_sequence(data):
     if n < 0:
         raise PskError("psk_frame_sequence failed: %d" % n)
     return out[:n].tobytes()
+
+
+SCAN_FORMS = ("dense", "cx", "cx_side", "cx_side_pc", "cx_side_idx")     # Chi2Form, csrc/chi2_plan.h
+
+
+def cx_idx_plan(feas, pc_hist, n_ov, knob_on=True):
+    """(ranges [(begin, len)] kept (at most 4), all ranges there are, rows in them, the index form is chosen) for the
+    feasible popcounts `feas` (a set) and the histogram pc_hist: psk_cx_idx_plan (host code, no device)."""
+    lib = _lib.load()
+    fw = (ctypes.c_uint64 * 4)()
+    for pc in feas:
+        fw[pc >> 6] |= 1 << (pc & 63)
+    hist = (ctypes.c_uint64 * max(len(pc_hist), 1))(*[int(h) for h in pc_hist])
+    begin, length = (ctypes.c_uint64 * 4)(), (ctypes.c_uint64 * 4)()
+    n_runs, rows, chosen = ctypes.c_int(), ctypes.c_uint64(), ctypes.c_int()
+    rc = lib.psk_cx_idx_plan(fw, hist, len(pc_hist), int(n_ov), int(bool(knob_on)), begin, length, ctypes.byref(n_runs),
+                             ctypes.byref(rows), ctypes.byref(chosen))
+    if rc < 0:
+        raise PskError("psk_cx_idx_plan failed: %d" % rc)
+    return [(begin[i], length[i]) for i in range(min(n_runs.value, 4))], n_runs.value, rows.value, bool(chosen.value)
+
+
+def cx_idx_shape(n_rows, cap_blocks):
+    """(workgroups, rows per workgroup, threads per workgroup, entries per result segment) of the index form for n_rows
+    feasible rows: psk_cx_idx_shape (host code, no device)."""
+    lib = _lib.load()
+    blocks, rpb, thr, cap = ctypes.c_uint32(), ctypes.c_uint64(), ctypes.c_uint32(), ctypes.c_uint64()
+    rc = lib.psk_cx_idx_shape(int(n_rows), int(cap_blocks), ctypes.byref(blocks), ctypes.byref(rpb), ctypes.byref(thr), ctypes.byref(cap))
+    if rc < 0:
+        raise PskError("psk_cx_idx_shape failed: %d" % rc)
+    return blocks.value, rpb.value, thr.value, cap.value
 
 
 def cx_pc_plan(n1, n0, n_samples, min_samples, max_samples, thr):
