@@ -476,6 +476,38 @@ int psk_forest_fit_counts(psk_ctx *ctx, const float *X, const int32_t *y01, int 
                           int64_t *tree_node_off_out, int32_t *nodes_out, double *impurity_out, int32_t *leaf_out,
                           double *threshold_out);
 
+/* ---- f13: `-bc DT` / `-bc RF` on a real-valued design (--pca) --------------------------------------
+ * psk_tree_fit_counts / psk_forest_fit_counts on a design of ANY finite float32 values: under --pca the reference fits its
+ * tree models on the kept principal-component scores (modeling.py:1204, then set_model :1030-1033).  Arguments, limits and
+ * outputs as the count calls (threshold_out included); what differs (csrc/solver_tree_real.hip):
+ *   X[n][p]   float32, any finite value (PSK_EINVAL, naming the call, on a NaN or an infinity)
+ * Equal values, as measured on scikit-learn 1.7.2 (its FEATURE_THRESHOLD of 1e-7 is not in effect in the search): any two
+ * float32 values that compare different are different values.  A column is constant in a node when its in-bag values all
+ * compare equal; a candidate is every place where the sorted in-bag values change (hi > lo as floats), adjacent float32 values
+ * included; -0.0 and +0.0 are one value.  The threshold is (double)lo / 2.0 + (double)hi / 2.0, replaced by (double)lo if that
+ * equals (double)hi or is infinite; (float32)x <= threshold goes left for every sample of the design.  Inside a column the first
+ * strictly larger proxy in ascending order wins.  Proxy, min_samples_leaf, the walk over the columns, n_node_samples,
+ * numbering and the reported impurities are the count calls'.  psk_tree_fit_real takes the LOWEST column index among
+ * bit-equal proxies, which is scikit-learn's tree only where its seed does not matter; psk_forest_fit_real with one tree of
+ * unit weights, max_features = p and tree_state = RandomState(s).randint(0, 2^31 - 1) is DecisionTreeClassifier(random_state=s).
+ * On a 0/1 design the results are psk_tree_fit's / psk_forest_fit's with thresholds 0.5, on a count design the count calls' in
+ * every output.
+ * Memory rule: no bit planes and no plane cap.  Besides the float design the calls keep every column's sample order (u16)
+ * and sorted values (f32), built once per call on the device: 6 n p bytes whatever the values; the search walks that order.
+ */
+int psk_tree_fit_real(psk_ctx *ctx, const float *X, const int32_t *y01, int n, int p, const int32_t *fold,
+                      const int32_t *fit_max_depth, const int32_t *fit_criterion, const int32_t *fit_fold, int n_fits,
+                      int32_t *node_count_out, int32_t *max_depth_out, int32_t *nodes_out, double *impurity_out,
+                      int32_t *leaf_out, double *frac_out, double *threshold_out);
+int psk_forest_fit_real(psk_ctx *ctx, const float *X, const int32_t *y01, int n, int p, int n_trees,
+                        const uint16_t *tree_weight, const uint32_t *tree_state, const int32_t *tree_fit,
+                        const int32_t *tree_export, int n_fits, const int32_t *fit_criterion,
+                        const int32_t *fit_max_depth, const int32_t *fit_max_features,
+                        const int32_t *fit_min_samples_leaf, const int32_t *fit_min_samples_split, double *sum0_out,
+                        double *sum1_out, int32_t *node_count_out, int32_t *max_depth_out, int64_t node_pool,
+                        int64_t *tree_node_off_out, int32_t *nodes_out, double *impurity_out, int32_t *leaf_out,
+                        double *threshold_out);
+
 /* ---- f8: the `-bc NB` estimator -------------------------------------------------------------------
  * set_model makes BernoulliNB() (modeling.py:1034-1035), but the REFERENCE CANNOT COMPLETE `-bc NB`: get_best_model
  * (:1075-1103) has no NB branch, best_model stays None (:623) and fit_model (:1216) fails on None.fit.  The yardstick is

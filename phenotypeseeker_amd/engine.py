@@ -518,7 +518,21 @@ class PskContext:
         samples, -2 at a leaf; x <= threshold goes left."""
         return self._tree_fit(True, self._count_design(X, "tree_fit_counts"), y01, fold, fit_max_depth, fit_criterion, fit_fold)
 
+    @staticmethod
+    def _real_design(X, who):
+        """The float32 design of the real calls: finite after the rounding to float32 (the library refuses the rest too)."""
+        X = np.ascontiguousarray(X, dtype=np.float32)
+        if X.ndim != 2 or not np.all(np.isfinite(X)):
+            raise ValueError("%s takes a real-valued design: every value must be finite in float32" % who)
+        return X
+
+    def tree_fit_real(self, X, y01, fold, fit_max_depth, fit_criterion, fit_fold):
+        """tree_fit_counts on a design of any finite float32 values (psk_tree_fit_real), ValueError on a NaN or an infinity.
+        The same dicts; any two different float32 values of a column make a candidate split, -0.0 and +0.0 are one value."""
+        return self._tree_fit("real", self._real_design(X, "tree_fit_real"), y01, fold, fit_max_depth, fit_criterion, fit_fold)
+
     def _tree_fit(self, counts, X, y01, fold, fit_max_depth, fit_criterion, fit_fold):
+        """counts: False (0/1 design), True (count design) or 'real' (any finite float32 values)."""
         n, p = X.shape
         y = np.ascontiguousarray(y01, dtype=np.int32)
         fold = np.ascontiguousarray(fold, dtype=np.int32)
@@ -535,7 +549,8 @@ class PskContext:
             self._check(self._lib.psk_tree_fit(*args), "psk_tree_fit")
             return [dict(self._tree_dict(nodes[j, :count[j]], imp[j, :count[j]], deepest[j], leaf[j]), frac=frac[j].copy()) for j in range(nf)]
         thr = np.zeros((nf, cap))
-        self._check(self._lib.psk_tree_fit_counts(*args, _ptr(thr)), "psk_tree_fit_counts")
+        name = "psk_tree_fit_real" if counts == "real" else "psk_tree_fit_counts"
+        self._check(getattr(self._lib, name)(*args, _ptr(thr)), name)
         return [dict(self._tree_dict(nodes[j, :count[j]], imp[j, :count[j]], deepest[j], leaf[j], thr[j, :count[j]]), frac=frac[j].copy())
                 for j in range(nf)]
 
@@ -556,6 +571,13 @@ class PskContext:
         """forest_fit on a count design (psk_forest_fit_counts): integers in 0 .. 2^24, ValueError otherwise.  The same
         results, every tree's dict with threshold by node as tree_fit_counts returns it."""
         return self._forest_fit(True, self._count_design(X, "forest_fit_counts"), y01, tree_weight, tree_state, tree_fit, fit_criterion,
+                                fit_max_depth, fit_max_features, fit_min_samples_leaf, fit_min_samples_split, export)
+
+    def forest_fit_real(self, X, y01, tree_weight, tree_state, tree_fit, fit_criterion, fit_max_depth, fit_max_features,
+                        fit_min_samples_leaf, fit_min_samples_split, export=None):
+        """forest_fit_counts on a design of any finite float32 values (psk_forest_fit_real), ValueError on a NaN or an
+        infinity.  The same results; equal values as tree_fit_real takes them."""
+        return self._forest_fit("real", self._real_design(X, "forest_fit_real"), y01, tree_weight, tree_state, tree_fit, fit_criterion,
                                 fit_max_depth, fit_max_features, fit_min_samples_leaf, fit_min_samples_split, export)
 
     def _forest_fit(self, counts, X, y01, tree_weight, tree_state, tree_fit, fit_criterion, fit_max_depth, fit_max_features,
@@ -587,7 +609,8 @@ class PskContext:
                 _ptr(msl), _ptr(mss), _ptr(sum0), _ptr(sum1), _ptr(count), _ptr(deepest), pool, _ptr(off), _ptr(nodes), _ptr(imp), _ptr(leaf))
         thr = np.zeros(max(pool, 1)) if counts else None
         if counts:
-            self._check(self._lib.psk_forest_fit_counts(*args, _ptr(thr)), "psk_forest_fit_counts")
+            name = "psk_forest_fit_real" if counts == "real" else "psk_forest_fit_counts"
+            self._check(getattr(self._lib, name)(*args, _ptr(thr)), name)
         else:
             self._check(self._lib.psk_forest_fit(*args), "psk_forest_fit")
         trees, row = [], 0

@@ -1,6 +1,8 @@
 """The tree estimators on a 0/1 design: DecisionTree over psk_tree_fit, RandomForest over psk_forest_fit with everything
 scikit-learn draws from NumPy's RandomState drawn on the host (ForestDraws).  With counts=True they take a design of k-mer
-counts through psk_tree_fit_counts / psk_forest_fit_counts and their trees carry scikit-learn's thresholds."""
+counts through psk_tree_fit_counts / psk_forest_fit_counts and their trees carry scikit-learn's thresholds; with real=True a
+design of any finite float32 values (the kept principal-component scores of --pca) through psk_tree_fit_real /
+psk_forest_fit_real."""
 import numpy as np
 
 from .model_search import _Estimator, _Twin, _fold_scores, _launch_plan
@@ -32,8 +34,9 @@ class Tree:
         self.capacity = self.node_count
 
     def apply(self, X):
-        """The leaf of every row: x <= threshold goes left."""
-        X = np.asarray(X, dtype=np.float64)
+        """The leaf of every row: (float32)x <= threshold goes left (scikit-learn's trees read X as float32; 0/1 and count
+        values are unchanged by that rounding, principal-component scores are not)."""
+        X = np.asarray(X, dtype=np.float32).astype(np.float64)
         node = np.zeros(X.shape[0], dtype=np.int64)
         rows = np.arange(X.shape[0])
         for _ in range(self.max_depth):
@@ -90,15 +93,15 @@ class DecisionTree(_Estimator):
     DecisionTreeClassifier() under {'max_depth': 1..10, 'criterion': ['gini', 'entropy']}) over psk_tree_fit:
     scikit-learn's depth-first best-split builder with its default settings.  scikit-learn breaks ties between equally good
     splits by an unseeded random feature order; here the lowest column index wins.  counts: the design
-    holds k-mer counts (psk_tree_fit_counts); a switch of the engine, not a parameter of scikit-learn's: neither the repr nor
-    the exported parameters show it."""
+    holds k-mer counts (psk_tree_fit_counts), real: it holds any finite float32 values (psk_tree_fit_real); switches of the
+    engine, not parameters of scikit-learn's: neither the repr nor the exported parameters show them."""
     _is_classifier = True
     MAX_DEPTH = 10
 
-    def __init__(self, criterion="gini", max_depth=None, counts=False):
+    def __init__(self, criterion="gini", max_depth=None, counts=False, real=False):
         if criterion not in ("gini", "entropy"):
             raise ValueError("DecisionTree: criterion must be 'gini' or 'entropy', got %r" % (criterion,))
-        self.criterion, self.max_depth, self.counts = criterion, max_depth, bool(counts)
+        self.criterion, self.max_depth, self.counts, self.real = criterion, max_depth, bool(counts), bool(real)
         self.classes_ = np.array([0, 1])
         self.tree_ = None
 
@@ -111,7 +114,7 @@ class DecisionTree(_Estimator):
         return "DecisionTreeClassifier(%s)" % ", ".join(parts)
 
     def _clone(self, **params):
-        kw = dict(criterion=self.criterion, max_depth=self.max_depth, counts=self.counts)
+        kw = dict(criterion=self.criterion, max_depth=self.max_depth, counts=self.counts, real=self.real)
         kw.update(params)
         return type(self)(**kw)
 
@@ -128,7 +131,7 @@ class DecisionTree(_Estimator):
         for c in crit:
             if c not in ("gini", "entropy"):
                 raise ValueError("DecisionTree: criterion must be 'gini' or 'entropy', got %r" % (c,))
-        engine_fit = ctx.tree_fit_counts if self.counts else ctx.tree_fit
+        engine_fit = ctx.tree_fit_real if self.real else ctx.tree_fit_counts if self.counts else ctx.tree_fit
         return engine_fit(X, y.astype(np.int32), folds, [int(dp) for dp in depth], crit, fit_fold)
 
     def fit(self, X, y, engine_ctx):
@@ -251,8 +254,8 @@ class ForestTree(DecisionTree):
     weighted_n_node_samples) and which, as in scikit-learn, knows its own seed and the forest's parameters."""
 
     def __init__(self, criterion="gini", max_depth=None, min_samples_split=2, min_samples_leaf=1, max_features="sqrt", random_state=None,
-                 counts=False):
-        super().__init__(criterion, max_depth, counts)
+                 counts=False, real=False):
+        super().__init__(criterion, max_depth, counts, real)
         self.min_samples_split, self.min_samples_leaf, self.max_features, self.random_state = (
             min_samples_split, min_samples_leaf, max_features, random_state)
 
@@ -278,7 +281,8 @@ class RandomForest(_Estimator):
     """sklearn.ensemble.RandomForestClassifier for two classes on a 0/1 design (set_model, modeling.py:1030-1031) over
     psk_forest_fit: for an integer random_state, scikit-learn 1.7.2's forest to the node.  The seven
     parameters of the reference's grid plus random_state; everything else at scikit-learn's defaults.  counts: the design
-    holds k-mer counts (psk_forest_fit_counts), the engine switch of DecisionTree."""
+    holds k-mer counts (psk_forest_fit_counts), real: any finite float32 values (psk_forest_fit_real); the engine switches of
+    DecisionTree."""
     _is_classifier = True
     _randomized = True        # the reference searches its forest with RandomizedSearchCV (modeling.py:1096-1099)
     _tracking_draws_only = True    # ... with n_iter / grid size < 0.01, the range its search has always taken
@@ -290,10 +294,10 @@ class RandomForest(_Estimator):
     SCRATCH_BYTES = 1 << 30   # per engine call: 16 bytes per tree and sample of leaf fractions
 
     def __init__(self, n_estimators=100, criterion="gini", max_depth=None, min_samples_split=2, min_samples_leaf=1,
-                 max_features="sqrt", bootstrap=True, random_state=0, counts=False):
+                 max_features="sqrt", bootstrap=True, random_state=0, counts=False, real=False):
         self.n_estimators, self.criterion, self.max_depth = n_estimators, criterion, max_depth
         self.min_samples_split, self.min_samples_leaf, self.max_features = min_samples_split, min_samples_leaf, max_features
-        self.bootstrap, self.random_state, self.counts = bootstrap, random_state, bool(counts)
+        self.bootstrap, self.random_state, self.counts, self.real = bootstrap, random_state, bool(counts), bool(real)
         self._check(self.get_params())
         self.classes_ = np.array([0, 1])
         self.estimators_ = None
@@ -319,7 +323,7 @@ class RandomForest(_Estimator):
         return _sk_repr("RandomForestClassifier", parts)
 
     def _clone(self, **params):
-        kw = dict(self.get_params(), random_state=self.random_state, counts=self.counts)
+        kw = dict(self.get_params(), random_state=self.random_state, counts=self.counts, real=self.real)
         kw.update(params)
         return type(self)(**kw)
 
@@ -359,7 +363,7 @@ class RandomForest(_Estimator):
                     weight.append(draws.weight(t, rows_key, rows, bool(q["bootstrap"])))
                     tree_fit.append(f - at)
             chunk = params[at:end]
-            engine_fit = ctx.forest_fit_counts if self.counts else ctx.forest_fit
+            engine_fit = ctx.forest_fit_real if self.real else ctx.forest_fit_counts if self.counts else ctx.forest_fit
             s0, s1, trees = engine_fit(X, y.astype(np.int32), np.array(weight), state, tree_fit, [q["criterion"] for q in chunk],
                                        [q["max_depth"] for q in chunk], [self.n_max_features(q["max_features"], p) for q in chunk],
                                        [int(q["min_samples_leaf"]) for q in chunk], [int(q["min_samples_split"]) for q in chunk],
@@ -379,7 +383,7 @@ class RandomForest(_Estimator):
 
     def _set_fit(self, trees, draws, n_features, n_samples):
         self.estimators_ = [ForestTree(self.criterion, self.max_depth, self.min_samples_split, self.min_samples_leaf, self.max_features,
-                                       draws.seeds[t], self.counts)._set_fit(fit, n_features) for t, fit in enumerate(trees)]
+                                       draws.seeds[t], self.counts, self.real)._set_fit(fit, n_features) for t, fit in enumerate(trees)]
         self.n_features_in_, self._n_samples = int(n_features), int(n_samples)
         return self
 

@@ -345,7 +345,7 @@ class Input:
         """Same positional signature as the reference (:141-183).  Options that select estimators
         outside the hot path (SVM/RF/DT/NB, L2/elastic net, saga, PCA) are rejected here; `-bc SVM`, `-bc DT`, `-bc RF` and
         `-bc NB` pass with their knobs (PSK_SVM, PSK_DT, PSK_RF, PSK_NB; `--kernel rbf` with PSK_SVM_RBF as well), `--pca` with
-        PSK_PCA for a binary phenotype under `-bc log` and `-bc SVM`."""
+        PSK_PCA for a binary phenotype under `-bc log` and `-bc SVM`, and with PSK_TREE_PCA as well under `-bc DT` and `-bc RF`."""
         if alphas is None:
             phenotypes.alphas = np.logspace(math.log10(alpha_min), math.log10(alpha_max), num=n_alphas)
         else:
@@ -398,11 +398,14 @@ class Input:
             elif binary_classifier == "DT" and _lib.env_flag("PSK_DT"):
                 # set_model (:1032-1033, :1069-1073): DecisionTreeClassifier() over max_depth 1..10 x {gini, entropy}.  The tree
                 # kernel works on the bit-packed presence matrix: principal components are not 0/1, and k-mer counts go through
-                # the count entry point only with PSK_TREE_COUNTS (docs/KNOBS.md; the reference fits the tree on the counts)
-                if real_counts and not _lib.env_flag("PSK_TREE_COUNTS"):
+                # the count entry point only with PSK_TREE_COUNTS (docs/KNOBS.md; the reference fits the tree on the counts).
+                # With PSK_TREE_PCA the kept principal-component scores go through the real-valued entry point (the reference fits
+                # the tree on them, :1204), also under --real_counts: the PCA is of the counts then and the tree sees scores
+                tree_pca = bool(pca) and _lib.env_flag("PSK_TREE_PCA")
+                if real_counts and not tree_pca and not _lib.env_flag("PSK_TREE_COUNTS"):
                     raise SystemExit("The decision tree on the GPU engine takes the 0/1 presence matrix only: "
                                      "--real_counts is not supported with -bc DT.")
-                if pca:
+                if pca and not tree_pca:
                     raise SystemExit("The decision tree on the GPU engine takes the 0/1 presence matrix only: "
                                      "--pca is not supported with -bc DT.")
                 phenotypes.binary_classifier = "DT"
@@ -410,10 +413,11 @@ class Input:
             elif binary_classifier == "RF" and _lib.env_flag("PSK_RF"):
                 # set_model (:1030-1031, :1057-1068) under get_best_model's RandomizedSearchCV(n_iter, cv) (:1096-1099).  The
                 # reference leaves every draw unseeded; here the seed is PSK_RF_SEED and the run is scikit-learn's for that seed
-                if real_counts and not _lib.env_flag("PSK_TREE_COUNTS"):
+                tree_pca = bool(pca) and _lib.env_flag("PSK_TREE_PCA")           # as for -bc DT
+                if real_counts and not tree_pca and not _lib.env_flag("PSK_TREE_COUNTS"):
                     raise SystemExit("The random forest on the GPU engine takes the 0/1 presence matrix only: "
                                      "--real_counts is not supported with -bc RF.")
-                if pca:
+                if pca and not tree_pca:
                     raise SystemExit("The random forest on the GPU engine takes the 0/1 presence matrix only: "
                                      "--pca is not supported with -bc RF.")
                 phenotypes.rf_seed = _rf_seed()
@@ -760,9 +764,10 @@ class phenotypes:
             grid = [1.0 / a for a in self.alphas]
             if self.binary_classifier == "DT":
                 # (a grid of two parameters goes to GridSearch as a dictionary, in the reference's own spelling, :1069-1073)
-                return DecisionTree(counts=bool(self.real_counts)), {"max_depth": [1, 2, 3, 4, 5, 6, 7, 8, 9, 10], "criterion": ["gini", "entropy"]}, None
+                # (under --pca the design is the kept scores whatever the PCA was taken of: the real-valued route, not the count one)
+                return DecisionTree(counts=bool(self.real_counts) and not self.pca, real=bool(self.pca)), {"max_depth": [1, 2, 3, 4, 5, 6, 7, 8, 9, 10], "criterion": ["gini", "entropy"]}, None
             if self.binary_classifier == "RF":
-                return RandomForest(random_state=self.rf_seed, counts=bool(self.real_counts)), {k: list(v) for k, v in RF_GRID.items()}, None
+                return RandomForest(random_state=self.rf_seed, counts=bool(self.real_counts) and not self.pca, real=bool(self.pca)), {k: list(v) for k, v in RF_GRID.items()}, None
             if self.binary_classifier == "NB":
                 return BernoulliNB(), None, None
             if self.binary_classifier == "SVM" and self.kernel == "rbf":
