@@ -578,7 +578,36 @@ int psk_pca_fit(psk_ctx *ctx, const float *X, int n, int p, int n_comp, double *
 int psk_pca_transform(psk_ctx *ctx, const float *X, int m, int p, const double *center, const double *scale,
                       const double *components, int k, double *scores_out);
 
-/* ---- f12: decision values of a fitted SVM (prediction) ---------------------------------------------
+/* ---- f14: the `--penalty L1+L2` regressor ---------------------------------------------------------------
+ * Replaces GridSearchCV over ElasticNet(l1_ratio, max_iter, tol) (set_model, modeling.py:1003-1006; :1041 the alpha grid;
+ * :1078-1080 the search).  The reference cannot finish this branch -- fit_model (:1211) tests the upper-cased penalty
+ * against "elasticnet" --, so the model is scikit-learn's ElasticNet as set_model configures it.  Same batching as
+ * psk_lasso_fit -- one workgroup per (alpha, fold) fit, refits included, one launch -- and the same meaning of X, y, n, p,
+ * fold, fit_fold, n_fits, tol, max_iter and the outputs; fit_alpha[j] is fit j's alpha, l1_ratio is shared by the call and
+ * must be finite and lie in [0, 1] (PSK_EINVAL otherwise; the context stays usable).
+ * Objective, over the n training rows of a fit, intercept unpenalised (X, y centred by the training rows' means):
+ *   (1/2n)||y - Xw - b||^2 + alpha l1_ratio ||w||_1 + 1/2 alpha (1 - l1_ratio) ||w||^2
+ * walked as scikit-learn's enet_coordinate_descent walks it, so a fit that stops at max_iter returns that iterate:
+ * with l1 = alpha l1_ratio n and l2 = alpha (1 - l1_ratio) n, cyclic sweeps over the columns of non-zero centred norm,
+ *   tmp = X_j'R + w_j |X_j|^2,   w_j <- sign(tmp) max(|tmp| - l1, 0) / (|X_j|^2 + l2),   R updated at once.
+ * Stop rule: after a sweep with w_max == 0 or d_w_max / w_max < tol, or the last sweep allowed, the duality gap
+ *   dual = max|X'R - l2 w|,  c = l1 / dual if dual > l1 else 1,
+ *   gap = (dual > l1 ? 1/2 R'R (1 + c^2) : R'R) + l1 ||w||_1 - c R'y + 1/2 l2 (1 + c^2) w'w
+ * is evaluated and the descent ends when gap < tol y'y.  iters_out = sweeps as scikit-learn counts them (n_iter_).
+ * intercept = mean y - sum_k mean_k w_k.  With l1_ratio = 1 every added term is an exact +0.0: the results are
+ * psk_lasso_fit's bit for bit.  With l1_ratio = 0 the gap never closes and every fit runs max_iter sweeps, as scikit-learn's.
+ * Routes and knobs are psk_lasso_fit's (PSK_NO_LASSO_COV, PSK_NO_LASSO_BITS, read per call): the covariance form for a 0/1
+ * design of up to 4,096 samples and 1,024 columns, the four-wave bit-packed kernel for other 0/1 designs that fit its LDS,
+ * the float kernel for everything else (--real_counts).  The kernels are the Lasso's, instantiated with the L2 term.
+ * Device scratch for the duration of the call: as psk_lasso_fit -- the design in one orientation and the per-fit state; the
+ * covariance form also takes the co-occurrence counts of every held-out fold, n_folds x 2 p^2 bytes (1.6 MB per fold at 907
+ * columns; the form is skipped beyond 2 GiB).
+ */
+int psk_enet_fit(psk_ctx *ctx, const float *X, const double *y, int n, int p, const int32_t *fold,
+                 const double *fit_alpha, const int32_t *fit_fold, int n_fits, double l1_ratio, double tol, int max_iter,
+                 double *coef_out, double *icpt_out, int32_t *iters_out);
+
+/* ---- f12: decision values of a fitted SVM (prediction)---------------------------------------------
  * What libsvm's svm_predict_values computes for new rows, the one prediction whose cost grows with the training set
  * (rows x support vectors x k-mers for the rbf kernel):
  *   dec_out[m]   dec[i] = (sum_j coef[j] K(SV_j, X_i)) - rho, libsvm's sign; coef[j] = y_j alpha_j (the package's

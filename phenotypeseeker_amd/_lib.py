@@ -84,6 +84,8 @@ _SIGNATURES = {
                                     c.c_void_p, c.c_int, c.c_double, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p]),
     "psk_lasso_fit": (c.c_int, [c.c_void_p, c.c_void_p, c.c_void_p, c.c_int, c.c_int, c.c_void_p, c.c_void_p,
                                 c.c_void_p, c.c_int, c.c_double, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p]),
+    "psk_enet_fit": (c.c_int, [c.c_void_p, c.c_void_p, c.c_void_p, c.c_int, c.c_int, c.c_void_p, c.c_void_p,
+                               c.c_void_p, c.c_int, c.c_double, c.c_double, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p]),
     "psk_ridge_fit": (c.c_int, [c.c_void_p, c.c_void_p, c.c_void_p, c.c_int, c.c_int, c.c_void_p, c.c_void_p,
                                 c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p]),
     "psk_logreg_l2_fit": (c.c_int, [c.c_void_p, c.c_void_p, c.c_void_p, c.c_int, c.c_int, c.c_void_p, c.c_void_p,

@@ -8,7 +8,8 @@
 //                     itself uses: outer Newton steps, inner coordinate descent with shrinking on the
 //                     quadratic model, one line search per outer step; a bit-packed form for 0/1 designs.
 //   lasso_kernel      (1/2n)||y - Xw - b||^2 + alpha ||w||_1, unpenalised intercept, cyclic
-//                     coordinate descent on the centred problem.
+//                     coordinate descent on the centred problem.  With EN = true the elastic net of psk_enet_fit (f14):
+//                     + 1/2 alpha (1 - l1_ratio) ||w||^2, the L1 weight alpha l1_ratio.
 //
 // Layout: XT[p][n] float (column-major: one k-mer's samples are contiguous), shared by all fits and
 // L2-resident; per fit the linear predictor / residual lives in LDS (global scratch beyond 4096 samples).
@@ -264,10 +265,14 @@ __global__ __launch_bounds__(SV_THREADS) void logreg_newglmnet_kernel(
 }
 #undef FLD
 
+// EN (here and in lasso_bits_kernel): the elastic net of psk_enet_fit -- threshold alpha l1_ratio n, and
+// beta = alpha (1 - l1_ratio) n in the step's divisor, in the dual norm max|X'R - beta w| and in the gap's
+// 1/2 beta (1 + c^2) w'w.  A template parameter: the Lasso's instances (EN = false) compile to what they were.
+template <bool EN>
 __global__ __launch_bounds__(SV_THREADS) void lasso_kernel(const float *__restrict__ XT, const double *__restrict__ y,
                                                             const int32_t *__restrict__ fold, int n, int p,
                                                             const double *__restrict__ fit_param,
-                                                            const int32_t *__restrict__ fit_fold, double tol, int max_iter,
+                                                            const int32_t *__restrict__ fit_fold, double tol, double l1_ratio, int max_iter,
                                                             double *__restrict__ coef, double *__restrict__ icpt,
                                                             int32_t *__restrict__ iters, double *__restrict__ work,
                                                             const int use_lds)
@@ -294,7 +299,8 @@ __global__ __launch_bounds__(SV_THREADS) void lasso_kernel(const float *__restri
         yy += d * d;
     }
     yy = psk_wave_sum_f64_dpp(yy);
-    const double an = alpha * ntrain, tol_s = tol * yy;
+    const double an = EN ? (alpha * l1_ratio) * ntrain : alpha * ntrain, tol_s = tol * yy;
+    const double beta = EN ? (alpha * (1.0 - l1_ratio)) * ntrain : 0.0;
     for (int j = 0; j < p; j++) {
         const float *col = XT + (size_t)j * n;
         double s1 = 0, s2 = 0;
@@ -324,7 +330,7 @@ __global__ __launch_bounds__(SV_THREADS) void lasso_kernel(const float *__restri
                 if (fold[i] != tf) s += ((double)col[i] - m) * r[i];
             const double rho = psk_wave_sum_f64_dpp(s) + nj * wj;
             const double mag = fabs(rho) - an;
-            const double nw = (mag > 0.0) ? ((rho > 0 ? mag : -mag) / nj) : 0.0;
+            const double nw = (mag > 0.0) ? ((rho > 0 ? mag : -mag) / (EN ? nj + beta : nj)) : 0.0;
             const double dd = nw - wj;
             if (dd != 0.0) {
                 for (int i = lane; i < n; i += SV_THREADS)
@@ -339,7 +345,7 @@ __global__ __launch_bounds__(SV_THREADS) void lasso_kernel(const float *__restri
         // scikit-learn's stop (enet_coordinate_descent): after a sweep whose largest step is below tol x the largest
         // coefficient -- or the last sweep allowed -- the duality gap is evaluated and the descent ends when gap < tol y'y
         if (wmax == 0.0 || dmax / wmax < tol || sweep == max_iter - 1) {
-            double dual = 0.0, l1 = 0.0;
+            double dual = 0.0, l1 = 0.0, ww = 0.0;
             for (int j = 0; j < p; j++) {
                 const float *col = XT + (size_t)j * n;
                 const double m = lane0_load(&xm[j], lane);
@@ -347,8 +353,12 @@ __global__ __launch_bounds__(SV_THREADS) void lasso_kernel(const float *__restri
                 for (int i = lane; i < n; i += SV_THREADS)
                     if (fold[i] != tf) s += ((double)col[i] - m) * r[i];
                 s = psk_wave_sum_f64_dpp(s);
-                dual = fmax(dual, fabs(s));
-                l1 += fabs(lane0_load(&w[j], lane));
+                const double wj = lane0_load(&w[j], lane);
+                if constexpr (EN) {
+                    dual = fmax(dual, fabs(s - beta * wj));
+                    ww += wj * wj;
+                } else dual = fmax(dual, fabs(s));
+                l1 += fabs(wj);
             }
             double rr = 0.0, ry = 0.0;
             for (int i = lane; i < n; i += SV_THREADS)
@@ -358,7 +368,8 @@ __global__ __launch_bounds__(SV_THREADS) void lasso_kernel(const float *__restri
             double cst = 1.0, gap;
             if (dual > an) { cst = an / dual; gap = 0.5 * (rr + rr * (cst * cst)); }
             else gap = rr;
-            gap += an * l1 - cst * ry;
+            if constexpr (EN) gap += (an * l1 - cst * ry) + ((0.5 * beta) * (1.0 + cst * cst)) * ww;
+            else gap += an * l1 - cst * ry;
             if (gap < tol_s) { sweep++; break; }
         }
     }
@@ -376,11 +387,11 @@ __global__ __launch_bounds__(SV_THREADS) void lasso_kernel(const float *__restri
 // threshold, same stop as lasso_kernel; column means and norms from the counts (x^2 = x).  The float kernel read a
 // column of n floats from L2 per coordinate (~2.6 us at 1,024 samples); here it is one transposed word per lane, asked
 // for a step ahead.  LDS: w | mean | norm | count, p doubles each.
-template <int WM>
+template <int WM, bool EN>
 __global__ __launch_bounds__(SV_COOP_THREADS) void lasso_bits_kernel(const uint64_t *__restrict__ colT, const double *__restrict__ y,
                                                                       const int32_t *__restrict__ fold, int n, int p, int W,
                                                                       const double *__restrict__ fit_param,
-                                                                      const int32_t *__restrict__ fit_fold, double tol, int max_iter,
+                                                                      const int32_t *__restrict__ fit_fold, double tol, double l1_ratio, int max_iter,
                                                                       double *__restrict__ coef, double *__restrict__ icpt,
                                                                       int32_t *__restrict__ iters)
 {
@@ -450,7 +461,8 @@ __global__ __launch_bounds__(SV_COOP_THREADS) void lasso_bits_kernel(const uint6
 #pragma unroll
     for (int v = 1; v < SV_COOP_WAVES; v++) { Rp += s_part[1][v]; yy += s_tot[1][v]; }
     __syncthreads();
-    const double an = alpha * ntrain, tol_s = tol * yy;
+    const double an = EN ? (alpha * l1_ratio) * ntrain : alpha * ntrain, tol_s = tol * yy;
+    const double beta = EN ? (alpha * (1.0 - l1_ratio)) * ntrain : 0.0;
     double c = 0.0;
     int sweep = 0, visit = 0;
     auto col_t = [&](int j) { return (colT[(size_t)j * 64 + lane] & tmask) >> t0; };
@@ -480,7 +492,7 @@ __global__ __launch_bounds__(SV_COOP_THREADS) void lasso_bits_kernel(const uint6
             for (int v = 1; v < SV_COOP_WAVES; v++) S1 += s_part[slot][v];
             const double rho = ((S1 + c * cj) - mj * (Rp + c * ntrain)) + nj * wj;
             const double mag = fabs(rho) - an;
-            const double nw = (mag > 0.0) ? ((rho > 0 ? mag : -mag) / nj) : 0.0;
+            const double nw = (mag > 0.0) ? ((rho > 0 ? mag : -mag) / (EN ? nj + beta : nj)) : 0.0;
             const double dd = nw - wj;
             if (dd != 0.0) {
                 const double nd = -dd;
@@ -498,7 +510,7 @@ __global__ __launch_bounds__(SV_COOP_THREADS) void lasso_bits_kernel(const uint6
         // scikit-learn's stop (see lasso_kernel): the duality gap, when it would evaluate it.  X'R of every column is one
         // more pass of masked sums (no steps), R'R and R'y come from the registers (r = r' + c on the training samples)
         if (wmax == 0.0 || dmax / wmax < tol || sweep == max_iter - 1) {
-            double dual = 0.0, l1 = 0.0;
+            double dual = 0.0, l1 = 0.0, ww = 0.0;
             uint64_t mg_next = p > 0 ? col_t(0) : 0ull;
             for (int j = 0; j < p; j++) {
                 const uint64_t x = mg_next;
@@ -518,7 +530,11 @@ __global__ __launch_bounds__(SV_COOP_THREADS) void lasso_bits_kernel(const uint6
                 double S1 = s_part[slot][0];
 #pragma unroll
                 for (int v = 1; v < SV_COOP_WAVES; v++) S1 += s_part[slot][v];
-                dual = fmax(dual, fabs((S1 + c * cntd[j]) - mean[j] * (Rp + c * ntrain)));
+                const double xr = (S1 + c * cntd[j]) - mean[j] * (Rp + c * ntrain);
+                if constexpr (EN) {
+                    dual = fmax(dual, fabs(xr - beta * w[j]));
+                    ww += w[j] * w[j];
+                } else dual = fmax(dual, fabs(xr));
                 l1 += fabs(w[j]);
             }
             double rr = 0.0, ry = 0.0;
@@ -536,7 +552,8 @@ __global__ __launch_bounds__(SV_COOP_THREADS) void lasso_bits_kernel(const uint6
             double cst = 1.0, gap;
             if (dual > an) { cst = an / dual; gap = 0.5 * (rr + rr * (cst * cst)); }
             else gap = rr;
-            gap += an * l1 - cst * ry;
+            if constexpr (EN) gap += (an * l1 - cst * ry) + ((0.5 * beta) * (1.0 + cst * cst)) * ww;
+            else gap += an * l1 - cst * ry;
             if (gap < tol_s) { sweep++; break; }
         }
     }
@@ -572,8 +589,14 @@ std::vector<int32_t> distinct_folds(const int32_t *fit_fold, int n_fits, std::ve
 }
 
 // the covariance form (solver_lasso.hip): fits of one fold share its co-occurrence counts
+// the penalty of a call: the Lasso (psk_lasso_fit), or the elastic net with its mixing parameter (psk_enet_fit)
+struct LassoPenalty {
+    bool enet;
+    double l1_ratio;
+};
+
 int lasso_cov_fit(psk_ctx *ctx, const FitArgs &a, const double *y, const std::vector<int32_t> &fold_ids,
-                  const std::vector<int32_t> &fidx, double tol, int max_iter)
+                  const std::vector<int32_t> &fidx, double tol, int max_iter, LassoPenalty pen)
 {
     const int n = a.n, p = a.p, n_fits = a.n_fits, W = (n + 63) / 64, PP = 64 * ((p + 63) / 64), F = (int)fold_ids.size();
     const std::vector<uint64_t> bits = pack_sample_bits(a.X, n, p, W, PP, false);
@@ -620,13 +643,14 @@ int lasso_cov_fit(psk_ctx *ctx, const FitArgs &a, const double *y, const std::ve
     A.bits = d_bits; A.tmask = d_tmask; A.yc = d_yc; A.fstat = d_fstat; A.C = d_C; A.Dg = d_Dg; A.q0 = d_q0;
     A.block_fit = d_bf; A.fit_param = io.fit_param; A.fit_fidx = d_fidx;
     A.n = n; A.p = p; A.PP = PP; A.W = W; A.n_folds = F; A.n_blocks = n_blocks; A.max_iter = max_iter; A.tol = tol;
+    A.enet = pen.enet; A.l1_ratio = pen.l1_ratio;
     A.coef = io.coef; A.icpt = io.icpt; A.gaps = nullptr; A.iters = io.iters; A.stream = ctx->stream;
     PSK_HIP(ctx, psk_lasso_cov_launch(A));
     return io.download(ctx, a);
 }
 
 // the four-wave kernel on the bit-packed samples; `lds`: its per-column state
-int lasso_bits_fit(psk_ctx *ctx, const FitArgs &a, const double *y, size_t lds, double tol, int max_iter)
+int lasso_bits_fit(psk_ctx *ctx, const FitArgs &a, const double *y, size_t lds, double tol, int max_iter, LassoPenalty pen)
 {
     const int n = a.n, p = a.p, W = (n + 63) / 64;
     const std::vector<uint64_t> bitsT = pack_lane_bits(a.X, n, p, false);
@@ -636,15 +660,16 @@ int lasso_bits_fit(psk_ctx *ctx, const FitArgs &a, const double *y, size_t lds, 
     PSK_TRY(io.upload(ctx, a));
     PSK_HIP(ctx, d_bitsT.upload(bitsT, ctx->stream));
     PSK_HIP(ctx, d_y.upload(y, n, ctx->stream));
-    auto kern = W <= 16 ? lasso_bits_kernel<16> : W <= 32 ? lasso_bits_kernel<32> : lasso_bits_kernel<64>;
+    auto kern = W <= 16 ? lasso_bits_kernel<16, false> : W <= 32 ? lasso_bits_kernel<32, false> : lasso_bits_kernel<64, false>;
+    if (pen.enet) kern = W <= 16 ? lasso_bits_kernel<16, true> : W <= 32 ? lasso_bits_kernel<32, true> : lasso_bits_kernel<64, true>;
     if (lds > 64 * 1024)
         PSK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    kern<<<a.n_fits, SV_COOP_THREADS, lds, ctx->stream>>>(d_bitsT, d_y, io.fold, n, p, W, io.fit_param, io.fit_fold, tol, max_iter,
-                                                          io.coef, io.icpt, io.iters);
+    kern<<<a.n_fits, SV_COOP_THREADS, lds, ctx->stream>>>(d_bitsT, d_y, io.fold, n, p, W, io.fit_param, io.fit_fold, tol, pen.l1_ratio,
+                                                          max_iter, io.coef, io.icpt, io.iters);
     return io.download(ctx, a);
 }
 
-int lasso_float_fit(psk_ctx *ctx, const FitArgs &a, const double *y, double tol, int max_iter)
+int lasso_float_fit(psk_ctx *ctx, const FitArgs &a, const double *y, double tol, int max_iter, LassoPenalty pen)
 {
     const int n = a.n, p = a.p;
     const std::vector<float> XT = transpose_f32(a.X, n, p, true);
@@ -657,8 +682,9 @@ int lasso_float_fit(psk_ctx *ctx, const FitArgs &a, const double *y, double tol,
     PSK_HIP(ctx, xt.upload(XT, ctx->stream));
     PSK_HIP(ctx, d_y.upload(y, n, ctx->stream));
     PSK_HIP(ctx, work.alloc((size_t)a.n_fits * (2 * (size_t)p + n)));
-    lasso_kernel<<<a.n_fits, SV_THREADS, lds, ctx->stream>>>(xt, d_y, io.fold, n, p, io.fit_param, io.fit_fold, tol, max_iter, io.coef,
-                                                             io.icpt, io.iters, work, use_lds);
+    auto kern = pen.enet ? lasso_kernel<true> : lasso_kernel<false>;
+    kern<<<a.n_fits, SV_THREADS, lds, ctx->stream>>>(xt, d_y, io.fold, n, p, io.fit_param, io.fit_fold, tol, pen.l1_ratio, max_iter, io.coef,
+                                                     io.icpt, io.iters, work, use_lds);
     return io.download(ctx, a);
 }
 
@@ -742,24 +768,46 @@ extern "C" int psk_logreg_l1_fit(psk_ctx *ctx, const float *X, const int32_t *y0
     return io.download(ctx, a);
 }
 
+namespace {
+
+// the route of a Lasso or elastic-net call, after its arguments are checked
+int lasso_route(psk_ctx *ctx, const FitArgs &a, const double *y, double tol, int max_iter, LassoPenalty pen)
+{
+    const int n = a.n, p = a.p;
+    PSK_HIP(ctx, hipSetDevice(ctx->device));
+    // presence/absence design (every entry 0 or 1): the covariance form up to 1,024 columns and 2 GiB of count matrices, else
+    // the four-wave kernel on the bit-packed samples while its per-column state fits in LDS; else the float kernel.
+    // PSK_NO_LASSO_COV / PSK_NO_LASSO_BITS for A/B runs
+    const bool binary = n <= 4096 && !env_flag("PSK_NO_LASSO_BITS") && design_is_binary(a.X, (size_t)n * p);
+    if (binary && p <= 1024 && !env_flag("PSK_NO_LASSO_COV")) {
+        std::vector<int32_t> fidx;
+        const std::vector<int32_t> fold_ids = distinct_folds(a.fit_fold, a.n_fits, fidx);
+        const size_t PP = 64 * (((size_t)p + 63) / 64);
+        if (fold_ids.size() * PP * PP * 2 <= ((size_t)2 << 30)) return lasso_cov_fit(ctx, a, y, fold_ids, fidx, tol, max_iter, pen);
+    }
+    const size_t lds_bits = (size_t)p * (4 * 8 + SV_COOP_WAVES * 4);
+    if (binary && lds_bits <= 150 * 1024) return lasso_bits_fit(ctx, a, y, lds_bits, tol, max_iter, pen);
+    return lasso_float_fit(ctx, a, y, tol, max_iter, pen);
+}
+
+}  // namespace
+
 extern "C" int psk_lasso_fit(psk_ctx *ctx, const float *X, const double *y, int n, int p, const int32_t *fold,
                              const double *fit_param, const int32_t *fit_fold, int n_fits, double tol, int max_iter,
                              double *coef_out, double *icpt_out, int32_t *iters_out)
 {
     const FitArgs a = {X, n, p, fold, fit_param, fit_fold, n_fits, coef_out, icpt_out, iters_out};
     PSK_TRY(check_fit_args(ctx, a, y));
-    PSK_HIP(ctx, hipSetDevice(ctx->device));
-    // presence/absence design (every entry 0 or 1): the covariance form up to 1,024 columns and 2 GiB of count matrices, else
-    // the four-wave kernel on the bit-packed samples while its per-column state fits in LDS; else the float kernel.
-    // PSK_NO_LASSO_COV / PSK_NO_LASSO_BITS for A/B runs
-    const bool binary = n <= 4096 && !env_flag("PSK_NO_LASSO_BITS") && design_is_binary(X, (size_t)n * p);
-    if (binary && p <= 1024 && !env_flag("PSK_NO_LASSO_COV")) {
-        std::vector<int32_t> fidx;
-        const std::vector<int32_t> fold_ids = distinct_folds(fit_fold, n_fits, fidx);
-        const size_t PP = 64 * (((size_t)p + 63) / 64);
-        if (fold_ids.size() * PP * PP * 2 <= ((size_t)2 << 30)) return lasso_cov_fit(ctx, a, y, fold_ids, fidx, tol, max_iter);
-    }
-    const size_t lds_bits = (size_t)p * (4 * 8 + SV_COOP_WAVES * 4);
-    if (binary && lds_bits <= 150 * 1024) return lasso_bits_fit(ctx, a, y, lds_bits, tol, max_iter);
-    return lasso_float_fit(ctx, a, y, tol, max_iter);
+    return lasso_route(ctx, a, y, tol, max_iter, LassoPenalty{false, 1.0});
+}
+
+extern "C" int psk_enet_fit(psk_ctx *ctx, const float *X, const double *y, int n, int p, const int32_t *fold,
+                            const double *fit_alpha, const int32_t *fit_fold, int n_fits, double l1_ratio, double tol,
+                            int max_iter, double *coef_out, double *icpt_out, int32_t *iters_out)
+{
+    const FitArgs a = {X, n, p, fold, fit_alpha, fit_fold, n_fits, coef_out, icpt_out, iters_out};
+    PSK_TRY(check_fit_args(ctx, a, y));
+    if (!(l1_ratio >= 0.0 && l1_ratio <= 1.0))   // (a nan fails both comparisons)
+        return psk_fail(ctx, PSK_EINVAL, "l1_ratio must lie in [0, 1], got %g", l1_ratio);
+    return lasso_route(ctx, a, y, tol, max_iter, LassoPenalty{true, l1_ratio});
 }

@@ -130,6 +130,8 @@ struct psk_lasso_cov_args {
     const int32_t *fit_fidx;   // [n_fits] index of the fit's fold
     int n, p, PP, W, n_folds, n_blocks, max_iter;
     double tol;
+    bool enet;                 // psk_enet_fit: fit_param is alpha and l1_ratio splits it (false: the Lasso, l1_ratio is not read)
+    double l1_ratio;
     double *coef, *icpt, *gaps;
     int32_t *iters;
     hipStream_t stream;

@@ -21,6 +21,12 @@
 // R'y = y'y - w'X'y), evaluated under its conditions, max_iter sweeps at most, the sweeps counted as it counts them.
 // Columns with zero centred norm are skipped as it skips them.  One deliberate difference: the step divides by
 // multiplying with 1 / |X_j|^2 (at most one ulp per step from its division).
+//
+// f14, the elastic net (psk_enet_fit; `ElasticNet(l1_ratio, max_iter, tol)`, modeling.py:1003-1006): the same kernel with
+// EN = true.  Its L2 term beta = alpha (1 - l1_ratio) n enters the step's divisor (1 / (|X_j|^2 + beta); |X_j|^2 stays as it
+// is in tmp), the dual norm max|g - beta w| and the gap's 1/2 beta (1 + c^2) w'w; R'R = R'y - w'g and R'y = y'y - w'X'y hold
+// unchanged, and a coordinate at zero inside the dead zone still takes a step of exactly 0, so the shortcuts of the block
+// walk stay exact.
 #include "solver_common.h"
 
 namespace {
@@ -111,22 +117,27 @@ struct LcRec {            // what the owner of a block leaves for everybody (slo
 };
 
 // R4: register rows per lane (blocks of 64 features per wave): p <= 256 R4
-template <int R4>
+// EN: the elastic net (psk_enet_fit): the L1 threshold is alpha l1_ratio n, and beta = alpha (1 - l1_ratio) n enters the
+// step's divisor, the dual norm max|g - beta w| and the gap's 1/2 beta (1 + c^2) w'w.  A template parameter, not one more
+// scalar: the Lasso's instances (EN = false) compile to what they were, and with beta = 0 the EN instances add exact zeros.
+template <int R4, bool EN>
 __global__ __launch_bounds__(LC_THREADS) void lasso_cov_kernel(
     const uint16_t *__restrict__ C, const double *__restrict__ Dg, const double *__restrict__ q0, const double *__restrict__ fstat,
     const int32_t *__restrict__ block_fit, const double *__restrict__ fit_param, const int32_t *__restrict__ fit_fidx, int p, int PP,
-    double tol, int max_iter, double *__restrict__ coef, double *__restrict__ icpt, int32_t *__restrict__ iters, double *__restrict__ gaps)
+    double tol, double l1_ratio, int max_iter, double *__restrict__ coef, double *__restrict__ icpt, int32_t *__restrict__ iters, double *__restrict__ gaps)
 {
     extern __shared__ double lq_all[];   // [4 waves][64 + 8][64]: the diagonal block of Q a wave steps next, staged a period or two ahead
     __shared__ LcRec rec[4];
-    __shared__ double s_red[4][4];
+    __shared__ double s_red[4][EN ? 5 : 4];
     __shared__ double s_dmax, s_wmax;
     const int fit = block_fit[blockIdx.x];
     if (fit < 0) return;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nb = PP >> 6;
     const int f = fit_fidx[fit];
     const double ym = fstat[4 * f], yy = fstat[4 * f + 1], ntr = fstat[4 * f + 2];
-    const double an = fit_param[fit] * ntr, tol_s = tol * yy, inv_n = 1.0 / ntr;
+    // (scikit-learn's l1_reg = alpha * l1_ratio * n_samples and l2_reg = alpha * (1.0 - l1_ratio) * n_samples, in its order)
+    const double an = EN ? (fit_param[fit] * l1_ratio) * ntr : fit_param[fit] * ntr, tol_s = tol * yy, inv_n = 1.0 / ntr;
+    const double beta = EN ? (fit_param[fit] * (1.0 - l1_ratio)) * ntr : 0.0;
     const uint16_t *Cf = C + (size_t)f * PP * PP;
     const double *Dgf = Dg + (size_t)f * nb * 4096;
     const double *q0f = q0 + (size_t)f * PP;
@@ -367,12 +378,15 @@ __global__ __launch_bounds__(LC_THREADS) void lasso_cov_kernel(
         if (swept) sweeps++;
         if (chk) {
             // the gap as scikit-learn evaluates it, from g = X'R, w, X'y and y'y
-            double dn = 0.0, wg = 0.0, wq = 0.0, l1 = 0.0;
+            double dn = 0.0, wg = 0.0, wq = 0.0, l1 = 0.0, ww = 0.0;
 #pragma unroll
             for (int r = 0; r < R4; r++) {
                 const int k = 64 * (4 * r + wave) + lane;
                 const double xty = (4 * r + wave < nb && k < p) ? q0f[k] : 0.0;
-                dn = fmax(dn, fabs(g[r]));
+                if constexpr (EN) {   // X'R - beta w
+                    dn = fmax(dn, fabs(g[r] - beta * wv[r]));
+                    ww += wv[r] * wv[r];
+                } else dn = fmax(dn, fabs(g[r]));
                 wg += wv[r] * g[r];
                 wq += wv[r] * xty;
                 l1 += fabs(wv[r]);
@@ -381,7 +395,9 @@ __global__ __launch_bounds__(LC_THREADS) void lasso_cov_kernel(
             wg = psk_wave_sum_f64_dpp(wg);
             wq = psk_wave_sum_f64_dpp(wq);
             l1 = psk_wave_sum_f64_dpp(l1);
+            if constexpr (EN) ww = psk_wave_sum_f64_dpp(ww);
             if (lane == 0) { s_red[wave][0] = dn; s_red[wave][1] = wg; s_red[wave][2] = wq; s_red[wave][3] = l1; }
+            if constexpr (EN) { if (lane == 0) s_red[wave][4] = ww; }
             __syncthreads();
             const double dual = fmax(fmax(s_red[0][0], s_red[1][0]), fmax(s_red[2][0], s_red[3][0]));
             const double WG = (s_red[0][1] + s_red[1][1]) + (s_red[2][1] + s_red[3][1]);
@@ -393,7 +409,10 @@ __global__ __launch_bounds__(LC_THREADS) void lasso_cov_kernel(
                 cst = an / dual;
                 gap = 0.5 * (RR + RR * (cst * cst));
             } else gap = RR;
-            gap += an * L1 - cst * Ry;
+            if constexpr (EN) {
+                const double WW = (s_red[0][4] + s_red[1][4]) + (s_red[2][4] + s_red[3][4]);
+                gap += (an * L1 - cst * Ry) + ((0.5 * beta) * (1.0 + cst * cst)) * WW;
+            } else gap += an * L1 - cst * Ry;
             __syncthreads();   // (s_red is free again)
             if (gap < tol_s) break;
         }
@@ -406,7 +425,8 @@ __global__ __launch_bounds__(LC_THREADS) void lasso_cov_kernel(
             for (int r = 0; r < R4; r++)
                 if (r == rs) { gs = g[r]; ws = wv[r]; cs = cnt[r]; ap[r] = T + 1; }   // (its own steps are applied as they are taken)
             const double ns = cs - cs * cs / ntr;                  // sum (x - mean)^2 with x^2 = x: the expression of the diagonal of Dg
-            const double is = ns > 0.0 ? 1.0 / ns : 0.0;           // (a column all 0 or all 1 on the training rows never moves)
+            // (a column all 0 or all 1 on the training rows never moves; the elastic net divides by |X_j|^2 + beta)
+            const double is = ns > 0.0 ? 1.0 / (EN ? ns + beta : ns) : 0.0;
             double ddc = 0.0;
             // a block whose coordinates are all at zero and inside the dead zone cannot move: every step would be exactly 0
             const bool quiet = (ws == 0.0 && fabs(gs) <= an) || is == 0.0;
@@ -542,11 +562,12 @@ hipError_t psk_lasso_cov_launch(const psk_lasso_cov_args &a)
     lasso_xty_kernel<<<dim3(a.PP, a.n_folds), 64, 0, a.stream>>>(a.bits, a.yc, a.q0, a.W, a.PP, a.n);
     lasso_diag_kernel<<<dim3(nb, a.n_folds), LC_THREADS, 0, a.stream>>>(a.C, a.fstat, a.Dg, a.PP);
     const int r4 = (nb + 3) / 4;
-    auto kern = r4 <= 1 ? lasso_cov_kernel<1> : r4 == 2 ? lasso_cov_kernel<2> : r4 == 3 ? lasso_cov_kernel<3> : lasso_cov_kernel<4>;
+    auto kern = r4 <= 1 ? lasso_cov_kernel<1, false> : r4 == 2 ? lasso_cov_kernel<2, false> : r4 == 3 ? lasso_cov_kernel<3, false> : lasso_cov_kernel<4, false>;
+    if (a.enet) kern = r4 <= 1 ? lasso_cov_kernel<1, true> : r4 == 2 ? lasso_cov_kernel<2, true> : r4 == 3 ? lasso_cov_kernel<3, true> : lasso_cov_kernel<4, true>;
     const size_t lds = 4 * (4096 + 512) * sizeof(double);
     const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     kern<<<a.n_blocks, LC_THREADS, lds, a.stream>>>(a.C, a.Dg, a.q0, a.fstat, a.block_fit, a.fit_param, a.fit_fidx, a.p, a.PP, a.tol,
-                                                  a.max_iter, a.coef, a.icpt, a.iters, a.gaps);
+                                                  a.l1_ratio, a.max_iter, a.coef, a.icpt, a.iters, a.gaps);
     return hipGetLastError();
 }

@@ -440,6 +440,11 @@ class PskContext:
         return self._fit(self._lib.psk_lasso_fit, "psk_lasso_fit", X, y, np.float64, fold, fit_param, fit_fold, float(tol),
                          int(max_iter))
 
+    def enet_fit(self, X, y, fold, fit_alpha, fit_fold, l1_ratio=0.5, tol=1e-4, max_iter=1000):
+        """Elastic-net fits (psk_enet_fit): same batching and routes as lasso_fit, one l1_ratio in [0, 1] for the call."""
+        return self._fit(self._lib.psk_enet_fit, "psk_enet_fit", X, y, np.float64, fold, fit_alpha, fit_fold, float(l1_ratio),
+                         float(tol), int(max_iter))
+
     def ridge_fit(self, X, y, fold, fit_param, fit_fold):
         """Ridge fits (psk_ridge_fit): same batching as lasso_fit, solved to convergence."""
         return self._fit(self._lib.psk_ridge_fit, "psk_ridge_fit", X, y, np.float64, fold, fit_param, fit_fold)

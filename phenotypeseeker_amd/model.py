@@ -16,7 +16,7 @@ psk_nb_jll, fitted directly: the reference has no search for it (and cannot comp
 The classes live in model_linear, model_svc, model_trees, model_nb and model_search (the searches, the estimator protocol they ask for
 and the export to scikit-learn objects); this module is their one public address.
 """
-from .model_linear import L1LogisticRegression, L2LogisticRegression, LassoRegression, RidgeRegression  # noqa: F401
+from .model_linear import ElasticNetRegression, L1LogisticRegression, L2LogisticRegression, LassoRegression, RidgeRegression  # noqa: F401
 from .model_nb import BernoulliNB  # noqa: F401
 from .model_search import GridSearch, RandomizedSearch  # noqa: F401
 from .model_svc import SVC, platt_predict_proba, platt_sigmoid_train  # noqa: F401

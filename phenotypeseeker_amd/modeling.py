@@ -29,7 +29,7 @@ from . import formats, metrics, _stats
 from .engine import PskContext
 from . import _lib
 from ._lib import PSK_EGZIP, PskError
-from .model import (SVC, BernoulliNB, DecisionTree, L1LogisticRegression, L2LogisticRegression, LassoRegression, RandomForest, RandomizedSearch,
+from .model import (SVC, BernoulliNB, DecisionTree, ElasticNetRegression, L1LogisticRegression, L2LogisticRegression, LassoRegression, RandomForest, RandomizedSearch,
                     RidgeRegression)
 
 RED_BANNER = "\x1b[1;1;101m%s\x1b[0m\n"
@@ -343,9 +343,10 @@ class Input:
                    n_iter, n_splits_cv_inner, testset_size, train_on_whole, logreg_solver, jump_to, pca,
                    real_counts, omit_B, kmerDB):
         """Same positional signature as the reference (:141-183).  Options that select estimators
-        outside the hot path (SVM/RF/DT/NB, L2/elastic net, saga, PCA) are rejected here; `-bc SVM`, `-bc DT`, `-bc RF` and
+        outside the hot path (SVM/RF/DT/NB, elastic net, saga, PCA) are rejected here; `-bc SVM`, `-bc DT`, `-bc RF` and
         `-bc NB` pass with their knobs (PSK_SVM, PSK_DT, PSK_RF, PSK_NB; `--kernel rbf` with PSK_SVM_RBF as well), `--pca` with
-        PSK_PCA for a binary phenotype under `-bc log` and `-bc SVM`, and with PSK_TREE_PCA as well under `-bc DT` and `-bc RF`."""
+        PSK_PCA for a binary phenotype under `-bc log` and `-bc SVM`, and with PSK_TREE_PCA as well under `-bc DT` and `-bc RF`,
+        `--penalty L1+L2` (or `elasticnet`) with `--l1_ratio` in [0, 1] with PSK_ENET for a continuous phenotype."""
         if alphas is None:
             phenotypes.alphas = np.logspace(math.log10(alpha_min), math.log10(alpha_max), num=n_alphas)
         else:
@@ -460,7 +461,24 @@ class Input:
                                      "solvers in ['liblinear', 'newton-cg', 'lbfgs', 'sag', 'saga'], "
                                      "got {}.".format(logreg_solver))
                 phenotypes.logreg_solver = logreg_solver
-        if phenotypes.penalty not in ("L1", "L2"):
+        if phenotypes.penalty in ("L1+L2", "ELASTICNET") and _lib.env_flag("PSK_ENET"):
+            # set_model (:1003-1006): ElasticNet(l1_ratio, max_iter, tol) under the Lasso's alpha grid (:1041) and search
+            # (:1078-1080).  The reference cannot finish the branch -- fit_model (:1211) compares the upper-cased penalty with
+            # "elasticnet" and never fits --, so the model is scikit-learn's estimator as set_model configures it (model_linear.py)
+            if phenotypes.pred_scale != "continuous":
+                # (:1020-1024, :1045-1047) SGDClassifier(loss='log') under a {'C': ...} grid: stochastic, not a parameter of that
+                # estimator, and a loss name scikit-learn no longer has -- there is no model to reproduce
+                raise SystemExit("--penalty %s on the GPU engine needs a continuous phenotype: for a binary one the reference "
+                                 "pairs an SGDClassifier with a grid over C, which is not one of its parameters, so there is "
+                                 "no model to reproduce." % penalty)
+            try:
+                ratio = float(l1_ratio)
+            except (TypeError, ValueError):
+                ratio = math.nan
+            if not 0.0 <= ratio <= 1.0:      # (nan fails both comparisons)
+                raise SystemExit("--l1_ratio must lie in [0, 1], got %r." % (l1_ratio,))
+            phenotypes.penalty, phenotypes.l1_ratio = "L1+L2", ratio
+        elif phenotypes.penalty not in ("L1", "L2"):
             # L1+L2 cannot complete in the reference either: GridSearchCV is handed {'C': ...} for an
             # SGDClassifier (:1020-1024, :1045-1047) and fit_model skips the ElasticNet fit (:1211-1214)
             raise SystemExit("Only the L1 and L2 penalties run on the GPU engine, got %r." % penalty)
@@ -506,6 +524,7 @@ class phenotypes:
     kmer_limit = None
     omit_B = None
     penalty = None
+    l1_ratio = None
     binary_classifier = "log"
     kernel = None
     n_iter = None
@@ -781,6 +800,9 @@ class phenotypes:
             return L1LogisticRegression(tol=self.tol, max_iter=self.max_iter), "C", grid
         if self.penalty == "L2":
             return RidgeRegression(tol=self.tol, max_iter=self.max_iter), "alpha", [np.float64(a) for a in self.alphas]
+        if self.penalty == "L1+L2":
+            return (ElasticNetRegression(l1_ratio=self.l1_ratio, tol=self.tol, max_iter=self.max_iter), "alpha",
+                    [np.float64(a) for a in self.alphas])
         # (numpy scalars, as the reference's {'alpha': np.logspace(...)} grid holds them: the summary prints the params' repr)
         return LassoRegression(tol=self.tol, max_iter=self.max_iter), "alpha", [np.float64(a) for a in self.alphas]
 
@@ -862,7 +884,7 @@ class phenotypes:
                 summary.write("\n### Outputting the model to a model file! ###\n")
         package = dict(self.model_package)
         # The reference's .pkl holds scikit-learn objects and its loader is a plain joblib.load (prediction.py:124-129):
-        # the fitted model is written as the equivalent GridSearchCV / LogisticRegression / Lasso / Ridge objects, so
+        # the fitted model is written as the equivalent GridSearchCV / LogisticRegression / Lasso / Ridge / ElasticNet objects, so
         # that the file loads where this package is absent.  PSK_NATIVE_PKL=1 keeps the package's own
         # (scikit-learn-free) classes, which is also what is written when scikit-learn is missing.
         package.update({"pca": self.pca, "pred_scale": self.pred_scale})

@@ -2,7 +2,7 @@
 loaded by a plain joblib.load, prediction.py:124-129) -- written WITHOUT importing scikit-learn.
 
 Importing scikit-learn costs 0.3-0.5 s, as much as all the GPU work of a 256-genome `modeling` run.  What a fitted
-GridSearchCV / LogisticRegression / Lasso / Ridge pickles as is its class (module + name) and its attribute
+GridSearchCV / LogisticRegression / Lasso / Ridge / ElasticNet pickles as is its class (module + name) and its attribute
 dictionary; the dictionaries of default-constructed estimators are recorded per scikit-learn version in
 sklearn_shells.json (tools/make_sklearn_shells.py), the fitted attributes come from this package's own solver.  The
 writer emits the pickle opcodes for "object of class <module>.<name> with this state" directly (GLOBAL / NEWOBJ /
@@ -315,7 +315,7 @@ def load_linear_package(path):
             if getattr(est, "multi_class", "auto") not in ("auto", "ovr", "deprecated", "warn"):
                 return None
             model = LinearModel(coef, icpt, classes)
-        elif kind in ("Lasso", "Ridge"):
+        elif kind in ("Lasso", "Ridge", "ElasticNet"):
             model = LinearModel(coef, icpt, None)
         elif kind == "SVC":
             model = _svc_from_state(est)

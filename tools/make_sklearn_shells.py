@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Records, for the installed scikit-learn, what a default-constructed LogisticRegression / Lasso / Ridge / SVC /
+"""Records, for the installed scikit-learn, what a default-constructed LogisticRegression / Lasso / ElasticNet / Ridge / SVC /
 DecisionTreeClassifier / RandomForestClassifier / BernoulliNB / StandardScaler / PCA / GridSearchCV / RandomizedSearchCV pickles as (module, class name, state) into phenotypeseeker_amd/sklearn_shells.json, keyed by the
 scikit-learn version.  phenotypeseeker_amd/skpickle.py writes model files from these templates without importing
 scikit-learn (0.3-0.5 s, as long as the rest of a 256-genome `modeling` run); a version without a template takes the
@@ -11,7 +11,7 @@ import os
 import sklearn
 from sklearn.decomposition import PCA
 from sklearn.ensemble import RandomForestClassifier
-from sklearn.linear_model import Lasso, LogisticRegression, Ridge
+from sklearn.linear_model import ElasticNet, Lasso, LogisticRegression, Ridge
 from sklearn.model_selection import GridSearchCV, RandomizedSearchCV
 from sklearn.naive_bayes import BernoulliNB
 from sklearn.preprocessing import StandardScaler
@@ -43,6 +43,7 @@ if os.path.exists(path):
 out[sklearn.__version__] = {
     "LogisticRegression": shell(LogisticRegression()),
     "Lasso": shell(Lasso()),
+    "ElasticNet": shell(ElasticNet()),
     "Ridge": shell(Ridge()),
     "SVC": shell(SVC()),
     "DecisionTreeClassifier": shell(DecisionTreeClassifier()),
