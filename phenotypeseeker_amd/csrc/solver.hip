@@ -75,6 +75,8 @@ __global__ __launch_bounds__(SV_THREADS) void logreg_newglmnet_kernel(
     double w_norm = 0.0, Gmax_old = 1e300, Gnorm1_init = -1.0, inner_eps = 1.0;
     uint32_t rng = ((uint32_t)fit + 1u) * 2654435761u | 1u;  // per-fit xorshift state of the sweep permutations (lane 0's copy counts)
     int newton = 0, floor_steps = 0;   // floor_steps: Newton steps in a row taken inside the line search's rounding noise
+    double Gbest = 1e300;              // the smallest violation of the fit so far
+    double zmin = 1e-12;               // coordinate steps below it are skipped, as liblinear skips them
     for (newton = 0; newton < max_newton; newton++) {
         double Gmax_new = 0.0, Gnorm1_new = 0.0;
         int active = P1;
@@ -111,12 +113,15 @@ __global__ __launch_bounds__(SV_THREADS) void logreg_newglmnet_kernel(
             Gnorm1_new += viol;
         }
         if (newton == 0) Gnorm1_init = Gnorm1_new;
+        const bool progressed = Gnorm1_new < 0.9 * Gbest;
+        if (Gnorm1_new < Gbest) Gbest = Gnorm1_new;
         if (Gnorm1_new <= eps * Gnorm1_init) break;
 
         // inner coordinate descent on the quadratic model
         for (int i = lane; i < n; i += SV_THREADS) xTd[i] = 0.0;
         double QP_Gmax_old = 1e300;
         int QP_active = active, iter = 0;
+        bool any_moved = false;
         while (iter < 1000) {
             // liblinear visits the active coordinates in a fresh random order every sweep (solve_l1r_lr); a fixed cyclic
             // order needs hundreds of times more sweeps on correlated columns (r01: 4.3 s against liblinear's 14 ms)
@@ -128,6 +133,7 @@ __global__ __launch_bounds__(SV_THREADS) void logreg_newglmnet_kernel(
                 }
             }
             double QP_Gmax_new = 0.0, QP_Gnorm1_new = 0.0;
+            bool moved = false;
             for (int sidx = 0; sidx < QP_active; sidx++) {
                 const int j = __builtin_amdgcn_readfirstlane(lane == 0 ? act[sidx] : 0);
                 const float *col = XT + (size_t)j * n;
@@ -162,8 +168,9 @@ __global__ __launch_bounds__(SV_THREADS) void logreg_newglmnet_kernel(
                 // liblinear skips |z| < 1e-12; a coefficient that has drifted to ~1e-17 must still be allowed to land
                 // on exactly 0, otherwise its +-1 subgradient term keeps the violation above the stopping threshold
                 // forever (r01: 5 of 143 fits of a 256 x 138 problem spun to max_iter)
-                if (fabs(z) < 1e-12 && !(z == -wp && wp != 0.0)) continue;
+                if ((fabs(z) < zmin && !(z == -wp && wp != 0.0)) || z == 0.0) continue;
                 z = fmin(fmax(z, -10.0), 10.0);
+                moved = true;
                 if (lane == 0) wpd[j] = wp + z;
                 for (int i = lane; i < n; i += SV_THREADS) {
                     if (fold[i] == tf) continue;
@@ -172,6 +179,16 @@ __global__ __launch_bounds__(SV_THREADS) void logreg_newglmnet_kernel(
                 }
             }
             iter++;
+            any_moved = any_moved || moved;
+            // Every step of a whole sweep was below the 1e-12 that is skipped: no later sweep can move anything either.  With
+            // count cells (x = 200: H ~ 4e4 D) that floor on a step leaves a gradient of ~1e-12 H, above the stop threshold of a
+            // tight tolerance (r52: 64 x 1 and 65 x 3 counts at tol = 1e-12 swept 1000 times per Newton step until max_iter, and
+            // 261 x 40 lay 1e-12 x the Hessian's condition number, 1e-8, from the optimum).  From the first such sweep on the
+            // fit takes every step that is not zero; a sweep that moves nothing even so ends the descent.
+            if (!moved && QP_active == active) {
+                if (zmin > 0.0) { zmin = 0.0; continue; }
+                break;
+            }
             if (QP_Gnorm1_new <= inner_eps * Gnorm1_init) {
                 if (QP_active == active) break;       // inner problem solved
                 QP_active = active;                   // re-check the shrunk coordinates
@@ -180,6 +197,8 @@ __global__ __launch_bounds__(SV_THREADS) void logreg_newglmnet_kernel(
             }
             QP_Gmax_old = QP_Gmax_new;
         }
+
+        if (!any_moved) { newton++; break; }   // d = 0: no coordinate can move
 
         // line search along d = wpd - w
         double delta = 0.0, w_norm_new = 0.0;
@@ -201,7 +220,10 @@ __global__ __launch_bounds__(SV_THREADS) void logreg_newglmnet_kernel(
                 const double ex = exp(xTd[i]);
                 const double en = ewx[i] * ex;
                 ewxn[i] = en;
-                cs += C * log((1.0 + en) / (ex + en));
+                // exp(w.x) = inf (a count of 200 under a coefficient of 3.6: w.x > 709): the quotient is inf / inf; its limit is
+                // exp(w.x) / (1 + exp(w.x)) of the point the step leaves.  (r52: 7 x 3 counts at C = 30, whose optimum has
+                // w.x = 1018 on one row, rejected every step from w.x = 707 on and ended 9.7 % above the optimum at max_iter.)
+                cs += C * (isinf(en) ? -log1p(1.0 / ewx[i]) : log((1.0 + en) / (ex + en)));
             }
             const double cond = w_norm_new - w_norm + negsum - sigma * delta + psk_wave_sum_f64_dpp(cs);
             // liblinear accepts when cond <= 0.  Close to the optimum the decrease the model predicts sinks below what the sum of
@@ -210,21 +232,29 @@ __global__ __launch_bounds__(SV_THREADS) void logreg_newglmnet_kernel(
             // fits at tol = 1e-12 either stopped after ~100 Newton steps or never).  A step whose cond is inside the noise is
             // taken whole -- near the optimum the quadratic model is the better judge -- and exp(w.x) is then rebuilt from w
             // (below: accepting such steps without it, the multiplicatively updated copy drifted over thousands of them and one
-            // fit "converged" 26 % away); three such steps in a row end the fit: it is where doubles can take it.  At the
+            // fit "converged" 26 % away); such steps in a row that gain nothing end the fit: it is where doubles can take it.  At the
             // tolerances the reference runs at |cond| is many orders above the noise and nothing changes.
             const bool in_noise = cond > 0.0 && cond <= 4.0 * 2.220446049250313e-16 * C * l;
-            floor_steps = in_noise ? floor_steps + 1 : (cond <= 0.0 ? 0 : floor_steps);
+            // (Counted are the steps in a row that did not bring the violation a tenth below its smallest so far, and five of
+            // them end the fit: on count designs the steps inside the noise still converge -- r52: 261 x 40 counts at tol =
+            // 1e-12 ended after three of them with the violation at 4e-7, falling, and a linear predictor 3 x its bound off.)
+            // (once the fit has met the floor of its coordinate steps, zmin = 0, every accepted step that gains nothing counts)
+            if (in_noise || (cond <= 0.0 && zmin == 0.0 && !progressed)) floor_steps = progressed ? 1 : floor_steps + 1;
+            else if (cond <= 0.0) floor_steps = 0;
             if (cond <= 0.0 || in_noise) {
                 w_norm = w_norm_new;
                 for (int j = 0; j < P1; j++) { if (lane == 0) w[j] = wpd[j]; }
+                double overflowed = 0.0;
                 for (int i = lane; i < n; i += SV_THREADS) {
                     if (fold[i] == tf) continue;
                     const double en = ewxn[i];
                     const double tt = 1.0 / (1.0 + en);
-                    ewx[i] = en; tau[i] = C * tt; D[i] = C * en * tt * tt;
+                    ewx[i] = en; tau[i] = C * tt; D[i] = isinf(en) ? 0.0 : C * en * tt * tt;
+                    if (isinf(en)) overflowed = 1.0;
                 }
                 accepted = true;
-                floor_rebuild = in_noise;
+                // an inf forgets w.x: rebuilt from w below, exp(w.x) is inf exactly on the rows whose w.x is past 709
+                floor_rebuild = in_noise || psk_wave_sum_f64_dpp(overflowed) > 0.0;
                 break;
             }
             w_norm_new = 0.0;
@@ -237,6 +267,7 @@ __global__ __launch_bounds__(SV_THREADS) void logreg_newglmnet_kernel(
             negsum *= 0.5;
             for (int i = lane; i < n; i += SV_THREADS) xTd[i] *= 0.5;
         }
+        if (!accepted && zmin == 0.0 && !progressed) floor_steps++;
         if (!accepted || floor_rebuild) {
             // the step was rejected 20 times: fall back to the current w and, as liblinear does after "too many
             // line search steps", rebuild exp(w.x) from w -- the multiplicatively updated copy has drifted and
@@ -253,11 +284,11 @@ __global__ __launch_bounds__(SV_THREADS) void logreg_newglmnet_kernel(
                 if (fold[i] == tf) continue;
                 const double en = exp(xTd[i]);
                 const double tt = 1.0 / (1.0 + en);
-                ewx[i] = en; tau[i] = C * tt; D[i] = C * en * tt * tt;
+                ewx[i] = en; tau[i] = C * tt; D[i] = isinf(en) ? 0.0 : C * en * tt * tt;
             }
         }
         if (iter == 1) inner_eps *= 0.25;
-        if (floor_steps >= 3) { newton++; break; }   // at the floor of what doubles resolve (see the line search)
+        if (floor_steps >= 5) { newton++; break; }   // at the floor of what doubles resolve (see the line search)
         Gmax_old = Gmax_new;
     }
     for (int j = 0; j < p; j++) { if (lane == 0) coef[(size_t)fit * p + j] = w[j]; }

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from helpers import GOLDEN, load_dataset, read_results_tsv, tokenizer_cases
+from l1_float_cases import objectives as _l1_objectives, stop_rule_holds as _l1_stop_rule_holds
 
 pytestmark = pytest.mark.gpu
 
@@ -596,29 +597,6 @@ def test_l1_logreg_mid_size_objectives_match_liblinear(ctx):
             # (the near-duplicate design at C = 100 stops 0.4-0.7 % above the optimum, depending on the rounding of the
             # Gram block's sums: 17 or 18 Newton steps)
             assert float(z["obj_" + tag][j]) * (1 - 1e-9) <= obj <= float(z["obj_" + tag][j]) * 1.01, (tag, C)
-
-
-def _l1_stop_rule_holds(X, ypm, fold, fp, ff, coef, icpt, iters, fits, tol=1e-4, slack=1.5):
-    """liblinear's stopping rule, for the TRUE gradient at the returned point: ||violation||_1 <= tol min(#pos, #neg) / l x
-    the violation at w = 0 (x slack: the solver tests it on its own accumulated quantities)."""
-    for j in fits:
-        tr = fold != ff[j]
-        A = np.hstack([X[tr].astype(np.float64), np.ones((tr.sum(), 1))])
-        yt = ypm[tr]
-
-        def viol(th):
-            g = -fp[j] * (A.T @ (yt / (1.0 + np.exp(yt * (A @ th)))))
-            return np.where(th > 0, np.abs(g + 1), np.where(th < 0, np.abs(g - 1),
-                                                             np.maximum(0, np.maximum(-(g + 1), g - 1)))).sum()
-        eps = tol * max(min((yt > 0).sum(), (yt < 0).sum()), 1) / tr.sum()
-        th = np.append(coef[j], icpt[j])
-        assert viol(th) <= slack * eps * viol(np.zeros_like(th)) + 1e-9, (j, fp[j], iters[j])
-
-
-def _l1_objectives(X, ypm, fold, fp, ff, coef, icpt):
-    Z = X.astype(np.float64) @ coef.T + icpt[None, :]
-    return np.array([np.abs(coef[j]).sum() + abs(icpt[j]) + fp[j] * np.logaddexp(0.0, -ypm[fold != ff[j]] * Z[fold != ff[j], j]).sum()
-                     for j in range(len(fp))])
 
 
 @pytest.mark.parametrize("n", [40, 130, 700, 2048, 3000, 4096])
