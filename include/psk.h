@@ -607,6 +607,53 @@ int psk_enet_fit(psk_ctx *ctx, const float *X, const double *y, int n, int p, co
                  const double *fit_alpha, const int32_t *fit_fold, int n_fits, double l1_ratio, double tol, int max_iter,
                  double *coef_out, double *icpt_out, int32_t *iters_out);
 
+/* ---- f15: `-a/--assembly`: the k-mers of the model assembled into longer sequences --------------------------
+ * Replaces kmer_assembler and its helpers (modeling.py:1526-1605; assembling, :1607-1622, writes the file).  The reference
+ * compares every ordered pair of a round's strings in Python and never ends on a repeat; here a round's matching runs on the
+ * device (csrc/asm.hip), the rest of the loop on the host (csrc/asm_host.h), and three caps end what cannot end by itself.
+ * The reference as it runs appends NO reverse complements to its list: kmers_for_ML is set to {} (:585) and never filled, so
+ * the map over it (:1572) is empty; both_strands chooses between the reference as it runs (0) and as it is written (1).
+ *
+ * Strings are packed two bits a base (A 0, C 1, G 2, T 3), 32 bases per u64, the first base in the two most significant bits
+ * (a k-mer word of this ABI shifted up to the top of the word); string i is the ceil(len_bases[i] / 32) words from
+ * words[word_off[i]] on; the unused low bits of its last word are not looked at.
+ *
+ * psk_asm_round: one round's matching over n strings (list positions 0 .. n - 1), 1 <= min_olap <= 31 (the reference's
+ * k - 1), every string of min_olap .. 2^24 bases, n <= 2^24 (PSK_EINVAL / PSK_ERANGE otherwise).
+ *   pairs_out[pair_cap][3]   (a, b, t) for every ordered pair of DIFFERENT list positions with an overlap: t is the largest
+ *                            t with min_olap <= t <= min(|a|, |b|) and suffix_t(a) == prefix_t(b) (t == |a|: a is a prefix
+ *                            of b; equal strings at two positions overlap by their length).  Order unspecified.
+ *   n_pairs_out              the number of such pairs
+ *   contained_out[n]         1 where string i is a substring of a string that differs from it, else 0
+ * More than pair_cap pairs: PSK_ERANGE with a message naming pair_cap; n_pairs_out is still the true number, pairs_out holds
+ * pair_cap of them, contained_out is complete, and the context stays usable.  n == 0: no pairs.  pair_cap <= 2^28.
+ *
+ * psk_assemble: the whole loop over n k-mers (2 <= k <= 32) given as 2k-bit words, as they are (not made canonical);
+ * both_strands != 0 appends the reverse complement of every k-mer behind the list.  Per round, over the current list:
+ * the strings inside a different string leave it; no pair left: stop; every string in no pair is emitted unless its reverse
+ * complement has been emitted; the next list is the set of all a + b[t:].  At the stop the remaining strings are emitted
+ * under the same rule.  Where the reference leaves the outcome to Python's set order this call has a rule: a round's list is
+ * sorted by length, then lexicographically (A < C < G < T), and offered for emission in that order -- of a string and its
+ * reverse complement the one of the earlier round wins, within a round the lexicographically smaller -- and the output is
+ * sorted by length, longest first, lexicographically among equal lengths.  The set of min(s, reverse complement of s) over
+ * the output is the reference's under every set order.
+ *   text_out[text_cap]   the sequences in that order, separated by '\n' (none after the last, no NUL)
+ *   n_seqs_out, text_len_out, rounds_out (may be NULL: rounds that merged something)
+ * text_cap too small: PSK_ERANGE naming text_cap, n_seqs_out and text_len_out are set (call again with that much room).
+ * n == 0: zero sequences.  Caps, read per call, each PSK_ERANGE with a message naming the knob and the round:
+ *   PSK_ASM_MAX_STRINGS   strings in a round's list (deduplicated, before the contained ones leave), default 1,048,576
+ *   PSK_ASM_MAX_PAIRS     overlapping pairs of a round (among the strings that stay), default 4,194,304
+ *   PSK_ASM_MAX_LEN       bases of one string, default 65,535
+ * The longest string at most doubles per round, so the length cap ends the endless growth of a repeat within about 13 rounds
+ * of the defaults; the pair and string caps end exponential branching.  The context stays usable after any of them.
+ * Device scratch for the duration of a round: the packed list, 28 bytes per string, 12 bytes per pair of the round's cap
+ * (at most n (n - 1) pairs are reserved).
+ */
+int psk_asm_round(psk_ctx *ctx, const uint64_t *words, const uint64_t *word_off, const uint32_t *len_bases, int64_t n,
+                  int min_olap, uint64_t pair_cap, int32_t *pairs_out, uint64_t *n_pairs_out, uint8_t *contained_out);
+int psk_assemble(psk_ctx *ctx, const uint64_t *kmer_words, int64_t n, int k, int both_strands, char *text_out,
+                 uint64_t text_cap, int64_t *n_seqs_out, uint64_t *text_len_out, int32_t *rounds_out);
+
 /* ---- f12: decision values of a fitted SVM (prediction)---------------------------------------------
  * What libsvm's svm_predict_values computes for new rows, the one prediction whose cost grows with the training set
  * (rows x support vectors x k-mers for the rbf kernel):

@@ -19,7 +19,8 @@ def env_flag(name):
     return os.environ.get(name, "") not in ("", "0")
 
 
-PSK_EGZIP = -6    # include/psk.h: (PSK_NO_GPU_GZ=1 only, since r05) a file input is gzip-compressed; the caller inflates it and uses the in-memory call
+PSK_ERANGE = -4   # include/psk.h: a size limit exceeded (the assembly's caps: assembly.py warns and goes on)
+PSK_EGZIP = -6   # include/psk.h: (PSK_NO_GPU_GZ=1 only, since r05) a file input is gzip-compressed; the caller inflates it and uses the in-memory call
 
 
 c = ctypes
@@ -122,6 +123,10 @@ _SIGNATURES = {
                               c.c_void_p, c.c_void_p, c.c_void_p]),
     "psk_pca_transform": (c.c_int, [c.c_void_p, c.c_void_p, c.c_int, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int,
                                     c.c_void_p]),
+    "psk_asm_round": (c.c_int, [c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_int, c.c_uint64, c.c_void_p, _u64p,
+                                c.c_void_p]),
+    "psk_assemble": (c.c_int, [c.c_void_p, c.c_void_p, c.c_int64, c.c_int, c.c_int, c.c_void_p, c.c_uint64, c.POINTER(c.c_int64), _u64p,
+                               c.POINTER(c.c_int32)]),
     "psk_count_dict": (c.c_int, [c.c_void_p, c.c_char_p, c.c_size_t, c.c_int, c.c_void_p, c.c_uint64, c.c_void_p]),
     "psk_count_dict_batch": (c.c_int, [c.c_void_p, c.c_int, c.POINTER(c.c_char_p), c.POINTER(c.c_size_t), c.c_int, c.c_void_p,
                                        c.c_uint64, c.c_void_p, c.c_int]),

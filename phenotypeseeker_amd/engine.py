@@ -18,6 +18,28 @@ def _ptr(a):
     return None if a is None else a.ctypes.data
 
 
+def pack_strings(strings):
+    """ACGT strings in the layout of psk_asm_round: (words, word_off[n], len_bases[n]) -- 32 bases per u64, the first base in
+    the two most significant bits, every string from a word of its own."""
+    lens = np.array([len(s) for s in strings], dtype=np.uint32)
+    nw = (lens.astype(np.int64) + 31) // 32
+    word_off = np.zeros(len(strings), dtype=np.uint64)
+    if len(strings) > 1:
+        word_off[1:] = np.cumsum(nw[:-1])
+    codes = np.zeros(int(nw.sum()) * 32, dtype=np.uint64)
+    lut = np.full(256, 255, dtype=np.uint8)
+    for ch, v in zip(b"ACGTUacgtu", (0, 1, 2, 3, 3) * 2):
+        lut[ch] = v
+    for s, off in zip(strings, word_off):
+        c = lut[np.frombuffer(s.encode("ascii"), dtype=np.uint8)]
+        if (c == 255).any():
+            raise ValueError("not a string of bases: %r" % s[:40])
+        codes[int(off) * 32: int(off) * 32 + len(s)] = c
+    shifts = (np.uint64(62) - np.arange(32, dtype=np.uint64) * np.uint64(2))
+    words = np.bitwise_or.reduce(codes.reshape(-1, 32) << shifts[None, :], axis=1) if len(codes) else np.zeros(0, dtype=np.uint64)
+    return np.ascontiguousarray(words, dtype=np.uint64), word_off, lens
+
+
 def _file_size(path):
     try:
         return os.stat(path).st_size
@@ -694,6 +716,47 @@ class PskContext:
         self._check(self._lib.psk_pca_transform(self._h, _ptr(X), m, p, _ptr(center), _ptr(scale), _ptr(comp), k, _ptr(scores)),
                     "psk_pca_transform")
         return scores
+
+    # -- k-mer assembly ---------------------------------------------------------------------------------
+    def asm_round(self, strings, min_olap, pair_cap=None):
+        """One round's matching of the assembly (psk_asm_round) over a list of ACGT strings: returns (pairs[n_pairs][3] int32 --
+        (a, b, t) per ordered pair of different list positions, t the largest overlap of at least min_olap bases, in no
+        particular order --, contained[n] bool: the string lies inside a different string).  pair_cap: room for that many
+        pairs, n (n - 1) when None.  More pairs than that: PskError with code PSK_ERANGE, whose n_pairs is the true number."""
+        n = len(strings)
+        words, word_off, lens = pack_strings(strings)
+        cap = n * (n - 1) if pair_cap is None else int(pair_cap)
+        pairs = np.zeros((max(cap, 1), 3), dtype=np.int32)
+        contained = np.zeros(max(n, 1), dtype=np.uint8)
+        n_pairs = ctypes.c_uint64()
+        rc = self._lib.psk_asm_round(self._h, _ptr(words), _ptr(word_off), _ptr(lens), n, int(min_olap), cap, _ptr(pairs), ctypes.byref(n_pairs),
+                                     _ptr(contained))
+        try:
+            self._check(rc, "psk_asm_round")
+        except PskError as e:
+            e.n_pairs = int(n_pairs.value)
+            raise
+        return pairs[:int(n_pairs.value)].copy(), contained[:n].astype(bool)
+
+    def assemble(self, kmer_words, k, both_strands=False):
+        """The assembly of k-mers given as 2k-bit words (psk_assemble; formats.kmer_to_word): returns (sequences in the output's
+        order -- longest first, lexicographically among equal lengths --, rounds that merged something).  A cap of the loop
+        (PSK_ASM_MAX_STRINGS, PSK_ASM_MAX_PAIRS, PSK_ASM_MAX_LEN) raises PskError with code PSK_ERANGE."""
+        words = np.ascontiguousarray(kmer_words, dtype=np.uint64)
+        n = len(words)
+        cap = max(1 << 16, 8 * n * (int(k) + 1))
+        for _ in range(2):
+            text = ctypes.create_string_buffer(cap)
+            n_seqs, text_len, rounds = ctypes.c_int64(), ctypes.c_uint64(), ctypes.c_int32()
+            rc = self._lib.psk_assemble(self._h, _ptr(words), n, int(k), 1 if both_strands else 0, text, cap, ctypes.byref(n_seqs),
+                                        ctypes.byref(text_len), ctypes.byref(rounds))
+            if rc == _lib.PSK_ERANGE and text_len.value > cap:     # the text did not fit: once more with the room it asked for
+                cap = int(text_len.value)
+                continue
+            break
+        self._check(rc, "psk_assemble")
+        seqs = text.raw[:text_len.value].decode("ascii").split("\n") if n_seqs.value else []
+        return seqs, int(rounds.value)
 
     # -- population-structure weights --------------------------------------------------------------
     def minhash_sketch(self, data, k=21, sketch_size=1000, seed=42):

@@ -1213,6 +1213,10 @@ def modeling(args):
             for j, ph in enumerate(phs):
                 ph.test_kmers_association_with_phenotype(ctx, group, phs[j + 1] if j + 1 < len(phs) else None)
             ph_t.mark("scan")      # (the survivors' all-gather inside it is moved to its own line: Phases.move)
+            if (getattr(args, "assembly", False) and _lib.env_flag("PSK_ASM") and group.rank == 0
+                    and all(name in phenotypes.no_results for name in Input.phenotypes_to_analyse)):
+                from . import assembly as _assembly
+                _assembly.run(ctx, [], int(Samples.kmer_length))       # (the run ends in the next line: -a says why it writes nothing)
             Input.pop_phenos_out_of_kmers()
         # 'modelling' / 'modeling' both run the model stage; 'PCA' runs nothing (:1689)
         if not Input.jump_to or Input.jump_to in ("modelling", "modeling"):
@@ -1228,7 +1232,15 @@ def modeling(args):
             group.barrier()
             ph_t.mark("waiting for rank 0's model")
         if getattr(args, "assembly", False):
-            _err(YELLOW % "-a/--assembly is outside the accelerated path and is skipped.")
+            if not _lib.env_flag("PSK_ASM"):
+                _err(YELLOW % "-a/--assembly is outside the accelerated path and is skipped.")
+            elif group.rank == 0:
+                # (:1700-1707) the model's k-mers of every analysed phenotype, assembled by the engine (assembly.py)
+                from . import assembly as _assembly
+                ph_t.enter("assembly of the model's k-mers")
+                _assembly.run(ctx, Input.phenotypes_to_analyse.values(), int(Samples.kmer_length), pca=bool(phenotypes.pca),
+                              model_stage=Input.jump_to in (None, "", "modelling", "modeling"))
+                ph_t.mark("assembly of the model's k-mers")
     finally:
         ph_t.enter("teardown: buffers, communicator")
         ctx.close()
