@@ -673,6 +673,61 @@ int psk_assemble(psk_ctx *ctx, const uint64_t *kmer_words, int64_t n, int k, int
 int psk_svc_decision(psk_ctx *ctx, const float *X, int m, int p, const float *SV, int n_sv, const double *coef,
                      double rho, int kernel, double gamma, double *dec_out);
 
+/* ---- f16: `-bc XGBC` / `-reg XGBR`: gradient-boosted trees ------------------------------------------
+ * The REFERENCE CANNOT COMPLETE either name: get_model_name, set_model, set_hyperparameters and get_best_model
+ * (modeling.py:186-207, :994-1103) have no case for them.  The yardstick is scikit-learn 1.7.2's GradientBoostingClassifier()
+ * / GradientBoostingRegressor() with their defaults, fitted directly, without a search (csrc/solver_gb.hip).  This is
+ * scikit-learn's gradient boosting (friedman_mse trees on the residuals of log_loss / squared_error, subsample 1.0, every
+ * feature considered, init None), NOT XGBoost's regularised objective.
+ *
+ * psk_gb_fit: X[n][p] 0/1, y[n] (0/1 for the log loss), fold / fit_fold / n_fits as psk_tree_fit (fit_fold[f] = -1: all
+ * samples).  Per fit f the IN-BAG samples are those with fold[s] != fit_fold[f], all of weight 1; held-out samples are routed
+ * and updated but never counted.  F is the raw prediction, F = init_raw[f] before stage 0 (the caller's: np.average(y) of the
+ * in-bag samples for the squared error, log(q / (1 - q)) of their class-1 share clipped to [eps32, 1 - eps32] for the log loss).
+ * Per stage:
+ *   residuals  r_s = y_s - F_s (loss 0, squared error), r_s = y_s - gb_expit(F_s) (loss 1, log loss);
+ *              gb_expit(x) = 1 / (1 + gb_exp(-x)), gb_exp this library's own function of IEEE +, -, *, /, rint and ldexp
+ *              (csrc/solver_gb_math.h: clamp to [-708, 708], Cody-Waite reduction by ln 2 in two parts, the Taylor polynomial of
+ *              degree 13 in Horner form, constants as hex floats), the same bits on the device, on the host and in NumPy
+ *   sums       EVERY sum over samples is taken in a TWO-LEVEL ORDER: within a word of 64 samples (sample s lies in word s / 64)
+ *              in ascending sample index from +0.0; then the word partials in ascending word index from +0.0
+ *   a node     with in-bag set S: w = |S|, sum = sum r, sq = sum r r, value = sum / w,
+ *              impurity = sq / w - (sum / w) * (sum / w).  A leaf when depth >= max_depth, or w < 2, or impurity <= DBL_EPSILON,
+ *              or ALL r_s, s in S, ARE BIT-EQUAL (this library's rule: the case scikit-learn's leaf rule means and its rounding
+ *              decides at random), or no column is non-constant in S
+ *   a split    of a column j that is non-constant in S: w_r = set bits in S, w_l = w - w_r, sum_r = sum r over the set bits,
+ *              sum_l = sum - sum_r, diff = w_r * sum_l - w_l * sum_r, proxy = diff * diff / (w_l * w_r)
+ *              (FriedmanMSE.proxy_impurity_improvement).  The largest proxy wins, THE LOWEST COLUMN INDEX among bit-equal maxima
+ *              (this library's rule; scikit-learn's random_state breaks such ties).  Nodes are numbered in pre-order, the left
+ *              child (bit clear) first
+ *   a leaf     loss 0: value as above.  loss 1 (_gb.py::_update_terminal_regions): with prob = y - r over S,
+ *              num = (sum r) / w, den = (sum prob * (1 - prob)) / w, value = 0 if |den| < 1e-150 else num / den
+ *   update     F_s += learning_rate * value[leaf(s)] for every sample
+ * Every expression in f64, nothing fused.  PSK_GB_NODE_CAP(max_depth) slots per tree; outputs:
+ *   node_count_out[n_fits][n_estimators]
+ *   nodes_out[n_fits][n_estimators][cap][4]   feature (-2: leaf), left, right (-1: leaf), n_node_samples (in-bag)
+ *   value_out / impurity_out[n_fits][n_estimators][cap]   (slots behind node_count are zero)
+ *   raw_out[n_fits][n]                         F of every sample after the last stage
+ *   staged_out[n_fits][n_estimators][n]        F of every sample after each stage; may be NULL
+ * PSK_ERANGE: n > 4096 (a stage's residuals and the node masks live in LDS).  PSK_EINVAL: more than 65535 fits, max_depth outside 1..10,
+ * n_estimators outside 1..1000, learning_rate not a finite number above 0, loss not 0 or 1, a non-finite y or init_raw, the log
+ * loss with a y other than 0 / 1 or with a fit whose in-bag samples are of one class, a fit without in-bag samples, a design
+ * value other than 0 or 1.
+ *
+ * psk_gb_decision: the raw predictions of the rows of X[n][p] (0/1, PSK_EINVAL otherwise; no sample cap) under one model in
+ * psk_gb_fit's layout (node_count[n_estimators], nodes[n_estimators][cap][4], value[n_estimators][cap]):
+ *   raw_out[n]   init_raw, then + learning_rate * value[leaf] stage after stage in stage order
+ * which is psk_gb_fit's raw_out bit for bit on the fit's own rows.  PSK_EINVAL also for a tree that is not pre-order (a child
+ * not behind its parent or outside node_count) or splits on a column outside 0 .. p - 1.
+ */
+#define PSK_GB_NODE_CAP(max_depth) ((2 << (max_depth)) - 1)
+int psk_gb_fit(psk_ctx *ctx, const float *X, const double *y, int n, int p, const int32_t *fold, const int32_t *fit_fold,
+               int n_fits, int loss, int n_estimators, double learning_rate, int max_depth, const double *init_raw,
+               int32_t *node_count_out, int32_t *nodes_out, double *value_out, double *impurity_out, double *raw_out,
+               double *staged_out);
+int psk_gb_decision(psk_ctx *ctx, const float *X, int n, int p, int n_estimators, int max_depth, const int32_t *node_count,
+                    const int32_t *nodes, const double *value, double init_raw, double learning_rate, double *raw_out);
+
 /* ---- f1: fixed-dictionary counting (prediction) ---------------------------------------------
  * Replaces `gmer_counter -db <txt> <addr>` (prediction.Samples.map_samples, prediction.py:72-80):
  * occurrences, both strands with multiplicity, of each dictionary k-mer (canonical words) in

@@ -683,6 +683,56 @@ class PskContext:
         self._check(self._lib.psk_nb_jll(self._h, _ptr(X), n, p, _ptr(delta), nm, _ptr(prior), _ptr(neg), _ptr(jll)), "psk_nb_jll")
         return jll[0] if one else jll
 
+    GB_LOSSES = {"squared_error": 0, "log_loss": 1}
+
+    def gb_fit(self, X, y, fold, fit_fold, loss, n_estimators, learning_rate, max_depth, init_raw, staged=True):
+        """Gradient-boosted regression trees (psk_gb_fit: scikit-learn's gradient boosting, include/psk.h f16) on a 0/1 design,
+        every fit in one call; fit_fold[j] = -1: all samples in bag.  loss: 0 / 'squared_error' or 1 / 'log_loss' (y 0/1);
+        init_raw[n_fits]: the raw prediction before stage 0.  Returns one dictionary per fit: node_count[n_estimators],
+        nodes[n_estimators][cap][4] (feature, -2 at a leaf; left; right, -1 at a leaf; in-bag n_node_samples), value and
+        impurity[n_estimators][cap], cap = 2^(max_depth + 1) - 1, raw[n] (every sample's raw prediction after the last stage)
+        and staged[n_estimators][n] (after each stage; None unless asked for)."""
+        X = np.ascontiguousarray(X, dtype=np.float32)
+        n, p = X.shape
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        fold = np.ascontiguousarray(fold, dtype=np.int32)
+        fit_fold = np.ascontiguousarray(fit_fold, dtype=np.int32)
+        init = np.ascontiguousarray(init_raw, dtype=np.float64).reshape(-1)
+        if len(y) != n or len(fold) != n or fit_fold.ndim != 1 or len(init) != len(fit_fold):
+            raise ValueError("y and fold must have one entry per row of X, fit_fold and init_raw one per fit")
+        nf, ne, depth = len(fit_fold), int(n_estimators), int(max_depth)
+        # (the library refuses these too; the output arrays are sized by them, so they are clamped for the allocation only)
+        cap = (2 << min(max(depth, 1), 10)) - 1
+        rows = min(max(ne, 1), 1000)
+        count = np.zeros((nf, rows), dtype=np.int32)
+        nodes = np.zeros((nf, rows, cap, 4), dtype=np.int32)
+        value, imp = np.zeros((nf, rows, cap)), np.zeros((nf, rows, cap))
+        raw = np.zeros((nf, n))
+        stg = np.zeros((nf, rows, n)) if staged else None
+        self._check(self._lib.psk_gb_fit(self._h, _ptr(X), _ptr(y), n, p, _ptr(fold), _ptr(fit_fold), nf, int(self.GB_LOSSES.get(loss, loss)),
+                                         ne, float(learning_rate), depth, _ptr(init), _ptr(count), _ptr(nodes), _ptr(value), _ptr(imp),
+                                         _ptr(raw), _ptr(stg)), "psk_gb_fit")
+        return [dict(node_count=count[j], nodes=nodes[j], value=value[j], impurity=imp[j], raw=raw[j], staged=stg[j] if staged else None)
+                for j in range(nf)]
+
+    def gb_decision(self, X, node_count, nodes, value, init_raw, learning_rate, max_depth):
+        """The raw predictions of the rows of a 0/1 design under one gradient-boosting model in gb_fit's layout
+        (psk_gb_decision): init_raw, then + learning_rate * value[leaf] stage after stage.  Returns raw[n]."""
+        X = np.ascontiguousarray(X, dtype=np.float32)
+        n, p = X.shape
+        depth = int(max_depth)
+        cap = (2 << min(max(depth, 1), 10)) - 1
+        count = np.ascontiguousarray(node_count, dtype=np.int32).reshape(-1)
+        ne = len(count)
+        nodes = np.ascontiguousarray(nodes, dtype=np.int32)
+        value = np.ascontiguousarray(value, dtype=np.float64)
+        if nodes.shape != (ne, cap, 4) or value.shape != (ne, cap):
+            raise ValueError("nodes must be [n_estimators][%d][4] and value [n_estimators][%d] for max_depth %d" % (cap, cap, depth))
+        raw = np.zeros(n)
+        self._check(self._lib.psk_gb_decision(self._h, _ptr(X), n, p, ne, depth, _ptr(count), _ptr(nodes), _ptr(value), float(init_raw),
+                                              float(learning_rate), _ptr(raw)), "psk_gb_decision")
+        return raw
+
     def pca_fit(self, X, n_comp=None):
         """StandardScaler + PCA of a design (psk_pca_fit): X[n][p], presence or counts; n_comp leading components, all
         min(n, p) when None.  Returns a dictionary: mean[p], var[p], scale[p], lambda[min(n, p)] (eigenvalues of Z Z',

@@ -11,11 +11,14 @@ psk_svc_fit, whose folds are scored from the decision values the engine returns,
 DecisionTree over psk_tree_fit under a two-key grid, scored from the leaves the engine returns for every sample, and `-bc RF`
 (modeling.py:1030-1031) to RandomForest over psk_forest_fit under RandomizedSearch: scikit-learn's forest and sampler for a
 given seed, the host drawing what NumPy's RandomState draws.  `-bc NB` (modeling.py:1034-1035) maps to BernoulliNB over psk_nb_fit /
-psk_nb_jll, fitted directly: the reference has no search for it (and cannot complete the branch at all, model_nb.py).
+psk_nb_jll, fitted directly: the reference has no search for it (and cannot complete the branch at all, model_nb.py).  `-bc XGBC`
+and `-reg XGBR` map to GradientBoosting over psk_gb_fit / psk_gb_decision, fitted directly too: scikit-learn's gradient boosting,
+not XGBoost (the reference names both and has no model for either, model_gb.py).
 
-The classes live in model_linear, model_svc, model_trees, model_nb and model_search (the searches, the estimator protocol they ask for
+The classes live in model_linear, model_svc, model_trees, model_nb, model_gb and model_search (the searches, the estimator protocol they ask for
 and the export to scikit-learn objects); this module is their one public address.
 """
+from .model_gb import GradientBoosting  # noqa: F401
 from .model_linear import ElasticNetRegression, L1LogisticRegression, L2LogisticRegression, LassoRegression, RidgeRegression  # noqa: F401
 from .model_nb import BernoulliNB  # noqa: F401
 from .model_search import GridSearch, RandomizedSearch  # noqa: F401

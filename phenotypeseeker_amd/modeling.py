@@ -29,7 +29,7 @@ from . import formats, metrics, _stats
 from .engine import PskContext
 from . import _lib
 from ._lib import PSK_EGZIP, PskError
-from .model import (SVC, BernoulliNB, DecisionTree, ElasticNetRegression, L1LogisticRegression, L2LogisticRegression, LassoRegression, RandomForest, RandomizedSearch,
+from .model import (SVC, BernoulliNB, DecisionTree, ElasticNetRegression, GradientBoosting, L1LogisticRegression, L2LogisticRegression, LassoRegression, RandomForest, RandomizedSearch,
                     RidgeRegression)
 
 RED_BANNER = "\x1b[1;1;101m%s\x1b[0m\n"
@@ -346,7 +346,8 @@ class Input:
         outside the hot path (SVM/RF/DT/NB, elastic net, saga, PCA) are rejected here; `-bc SVM`, `-bc DT`, `-bc RF` and
         `-bc NB` pass with their knobs (PSK_SVM, PSK_DT, PSK_RF, PSK_NB; `--kernel rbf` with PSK_SVM_RBF as well), `--pca` with
         PSK_PCA for a binary phenotype under `-bc log` and `-bc SVM`, and with PSK_TREE_PCA as well under `-bc DT` and `-bc RF`,
-        `--penalty L1+L2` (or `elasticnet`) with `--l1_ratio` in [0, 1] with PSK_ENET for a continuous phenotype."""
+        `--penalty L1+L2` (or `elasticnet`) with `--l1_ratio` in [0, 1] with PSK_ENET for a continuous phenotype, `-bc XGBC` with a
+        binary and `-reg XGBR` with a continuous phenotype with PSK_GB (scikit-learn's gradient boosting, model_gb.py)."""
         if alphas is None:
             phenotypes.alphas = np.logspace(math.log10(alpha_min), math.log10(alpha_max), num=n_alphas)
         else:
@@ -371,10 +372,18 @@ class Input:
         phenotypes.real_counts = real_counts
         phenotypes.omit_B = omit_B
         phenotypes.pca = pca
+        phenotypes.gradient_boosting = False
         if phenotypes.pred_scale == "continuous":
-            if regressor != "lin":
+            if regressor == "XGBR" and _lib.env_flag("PSK_GB"):
+                # the reference names XGBR and has no model for it (get_model_name, set_model, :186-207, :994-1103): the model is
+                # scikit-learn's GradientBoostingRegressor() fitted directly (model_gb.py), not XGBoost
+                cls._gb_design_only("-reg XGBR", "regressor", pca, real_counts)
+                phenotypes.gradient_boosting = True
+                phenotypes.model_name_long, phenotypes.model_name_short = "gradient boosting regressor", "GBR"
+            elif regressor != "lin":
                 raise SystemExit("Only the linear (Lasso) regressor runs on the GPU engine, got %r." % regressor)
-            phenotypes.model_name_long, phenotypes.model_name_short = "linear regression", "linreg"
+            else:
+                phenotypes.model_name_long, phenotypes.model_name_short = "linear regression", "linreg"
         else:
             phenotypes.binary_classifier = "log"
             if binary_classifier == "SVM" and _lib.env_flag("PSK_SVM"):
@@ -440,6 +449,12 @@ class Input:
                                      "--pca is not supported with -bc NB.")
                 phenotypes.binary_classifier = "NB"
                 phenotypes.model_name_long, phenotypes.model_name_short = "Naive Bayes", "NB"
+            elif binary_classifier == "XGBC" and _lib.env_flag("PSK_GB"):
+                # as -reg XGBR above: scikit-learn's GradientBoostingClassifier() fitted directly
+                cls._gb_design_only("-bc XGBC", "classifier", pca, real_counts)
+                phenotypes.gradient_boosting = True
+                phenotypes.binary_classifier = "XGBC"
+                phenotypes.model_name_long, phenotypes.model_name_short = "gradient boosting classifier", "GBC"
             elif binary_classifier != "log":
                 raise SystemExit("Only the logistic-regression classifier runs on the GPU engine, got %r "
                                  "(SVM/RF/DT/NB are outside the accelerated path)." % binary_classifier)
@@ -461,6 +476,8 @@ class Input:
                                      "solvers in ['liblinear', 'newton-cg', 'lbfgs', 'sag', 'saga'], "
                                      "got {}.".format(logreg_solver))
                 phenotypes.logreg_solver = logreg_solver
+        if phenotypes.gradient_boosting:
+            return      # --penalty, --alphas and -cv2 play no part in a model that is not searched (as for -bc NB)
         if phenotypes.penalty in ("L1+L2", "ELASTICNET") and _lib.env_flag("PSK_ENET"):
             # set_model (:1003-1006): ElasticNet(l1_ratio, max_iter, tol) under the Lasso's alpha grid (:1041) and search
             # (:1078-1080).  The reference cannot finish the branch -- fit_model (:1211) compares the upper-cased penalty with
@@ -487,6 +504,15 @@ class Input:
         if pca and phenotypes.pred_scale == "continuous":
             # PCA_analysis (:1178-1193) keeps the components whose scores differ between phenotype == 1 and phenotype == 0
             raise SystemExit("--pca on the GPU engine needs a binary phenotype: its t-test compares the two classes.")
+
+
+    @staticmethod
+    def _gb_design_only(flag, kind, pca, real_counts):
+        """The boosting kernel works on the bit-packed presence matrix; threshold planes for counts are not built for it."""
+        for given, name in ((pca, "--pca"), (real_counts, "--real_counts")):
+            if given:
+                raise SystemExit("The gradient boosting %s on the GPU engine takes the 0/1 presence matrix only: "
+                                 "%s is not supported with %s." % (kind, name, flag))
 
 
 # set_model's hyper-parameters of the random forest, in the reference's own spelling and order (:1057-1068)
@@ -526,6 +552,7 @@ class phenotypes:
     penalty = None
     l1_ratio = None
     binary_classifier = "log"
+    gradient_boosting = False     # -bc XGBC / -reg XGBR behind PSK_GB: model.GradientBoosting, fitted directly
     kernel = None
     n_iter = None
     rf_seed = 0
@@ -779,6 +806,8 @@ class phenotypes:
         self.n_splits_cv_inner = int(min(least, n_splits_cv_inner))
 
     def _new_estimator(self):
+        if self.gradient_boosting:
+            return GradientBoosting("log_loss" if self.pred_scale == "binary" else "squared_error"), None, None
         if self.pred_scale == "binary":
             grid = [1.0 / a for a in self.alphas]
             if self.binary_classifier == "DT":
@@ -809,7 +838,7 @@ class phenotypes:
     def _fit(self, ctx, X, y):
         est, pname, grid = self._new_estimator()
         self.model = est
-        if self.binary_classifier == "NB" and self.pred_scale == "binary":
+        if self.gradient_boosting or (self.binary_classifier == "NB" and self.pred_scale == "binary"):
             # no search: the fitted estimator itself is the model, and it is what the .pkl holds (the reference's fit_model, :1216,
             # would fit best_model directly too).  The reports below predict on the host, in the device's order of summation
             self.model_fitted = est.fit(X, y, ctx)
@@ -966,8 +995,11 @@ class phenotypes:
                           f"\t{np.float64(pc['explained_variance_ratio'][i])}\t{np.float64(pc['t'][i])}\t{np.float64(pc['p'][i])}\n")
 
     def _cross_validation_results(self, out):
-        """(:1219-1237); nothing for NB, which is not searched (:1220)"""
+        """(:1219-1237); nothing for NB, which is not searched (:1220); the parameters alone for gradient boosting"""
         if self.model_name_short == "NB":
+            return
+        if self.gradient_boosting:
+            out.write("Parameters:\n%s\n\n" % self.model)
             return
         out.write("Parameters:\n%s\n\n" % self.model)
         out.write("Grid scores (%s) on development set: \n" %
@@ -985,8 +1017,9 @@ class phenotypes:
         out.write("\nModel predictions on samples:\nSample_ID Acutal_phenotype Predicted_phenotype\n")
         # the printed value is a ONE-ROW prediction, as the reference computes it (:1245-1249): a regressor's last digit is the
         # BLAS sum's, which is not the same for a row alone and for the row inside the matrix; the metrics use `pred`
+        # (a boosted model adds a row's stage values in stage order whatever rows stand beside it: pred[i] is that value)
         for i, (name, actual) in enumerate(zip(index, y)):
-            out.write("%s %s %s\n" % (name, actual, self.model_fitted.predict(X[i:i + 1])[0]))
+            out.write("%s %s %s\n" % (name, actual, pred[i] if self.gradient_boosting else self.model_fitted.predict(X[i:i + 1])[0]))
         out.write("\n")
 
         def keep(key, value):
@@ -1054,7 +1087,7 @@ class phenotypes:
                     who = [names[i] for i in np.nonzero(Xn[:, j] != 0)[0]]
                     out.write("%s\tNA\t%d\t| %s\n" % (km, len(who), " ".join(who)))
                 return
-        be = self.model_fitted.best_estimator_
+        be = getattr(self.model_fitted, "best_estimator_", self.model_fitted)     # (a model that is not searched is its own)
         # what the estimator declares; a scikit-learn linear model handed over in the fit's place: its coef_ as one row
         coefs = be._coef_column if hasattr(be, "_coef_column") else np.ravel(be.coef_)
         X, index, kmers = self.ML["X"], self.ML["index"], self.ML["kmers"]

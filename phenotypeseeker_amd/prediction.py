@@ -98,14 +98,18 @@ class Phenotypes:
     def predict(self, ctx=None):
         """predictions_<pheno>.txt (:165-182).  A naive-Bayes model of this package (what the stub reader makes of an NB file)
         takes its joint log-likelihoods from the open context (psk_nb_jll), a support vector machine of this package -- bare, or
-        the best_estimator_ of a search of this package -- its decision values (psk_svc_decision); every other model predicts
-        as before."""
+        the best_estimator_ of a search of this package -- its decision values (psk_svc_decision), a gradient-boosting model of the
+        kind `modeling` writes (scikit-learn's object from joblib.load, taken over by model_gb.from_sklearn) its raw values
+        (psk_gb_decision); every other model predicts as before."""
+        from .model_gb import GradientBoosting, from_sklearn
         from .model_nb import BernoulliNB
         from .model_svc import SVC
         model = self.model
         if isinstance(getattr(model, "best_estimator_", None), SVC):
             model = model.best_estimator_
-        on_device = (ctx,) if ctx is not None and isinstance(model, (BernoulliNB, SVC)) else ()
+        if type(model).__name__ in ("GradientBoostingClassifier", "GradientBoostingRegressor"):
+            model = from_sklearn(model) or model
+        on_device = (ctx,) if ctx is not None and isinstance(model, (BernoulliNB, SVC, GradientBoosting)) else ()
         design = self.matrix
         if self.pca:
             # (:155-163) scaler.transform, pca_model.transform, [:, PCs_to_keep]: one psk_pca_transform on the open context for
