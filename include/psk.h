@@ -198,7 +198,13 @@ int psk_chi2_scan(psk_ctx *ctx, const int8_t *pheno, const double *weights, int 
  * psk_get_results, psk_export_survivors, psk_export_survivors_async on any stream, the next scans -- sees all of
  * them: each is ordered behind the scan on the device.  It does NOT mean that the scan's dispatch has retired: an
  * unweighted scan is ended by the words its kernel writes to pinned memory (PSK_SCAN_WAIT, docs/KNOBS.md), which
- * arrive as its last workgroups finish.  A caller that reads the context's device buffers by means of its own, on a
+ * arrive as its last workgroups finish.  Of a launch of at most 64 workgroups (the index form of the side-matrix scan)
+ * psk_scan_end reads one summary line -- n_pass, the scan's end clock, an overflow flag -- written by the last
+ * workgroup to publish a segment (PSK_SCAN_SUMMARY; a larger launch is waited for segment by segment); the per-segment
+ * counts are read, and checked to be this scan's and to add up to n_pass, by the first result call made on the scan,
+ * which may therefore be the call that reports PSK_ESTATE for a scan whose words never arrived.  PSK_ERANGE (a segment
+ * overflowed) still comes from psk_scan_end: the summary says so.  A scan whose set is taken by a later
+ * psk_chi2_scan_begin before any result call never has its counts read.  A caller that reads the context's device buffers by means of its own, on a
  * stream of its own, synchronises with the context first (any blocking call of this library does).  Once
  * psk_export_survivors_async has been called on a context its scans are ended by events again (the dispatch has
  * completed when psk_scan_end returns), so the export never waits for a later scan already queued. */
@@ -294,8 +300,9 @@ int psk_cx_pc_index(psk_ctx *ctx, uint32_t *index, uint64_t cap, uint64_t *pc_st
  * (else the other two are 0), *class_mask as psk_cx_plan gives it, *slots_skipped = 1 when the launch read only the side
  * matrix of overflow rows.  Measurement and tests only.  Any pointer may be NULL. */
 int psk_last_scan_plan(const psk_ctx *ctx, int *encoded, uint32_t *class_mask, int *slots_skipped);
-/* Duration of the last scan in milliseconds (for bench.py): from the clock words its kernel stamped (an unweighted chi2
- * scan ended by psk_scan_end; PSK_SCAN_WAIT=0: its event pair), else the HIP-event duration of its kernel launches. */
+/* Duration of the last scan in milliseconds (for bench.py): from the start and end clock words its kernel stamped (an
+ * unweighted chi2 scan ended by psk_scan_end: its first instruction to the publish of its last segment; PSK_SCAN_WAIT=0:
+ * its event pair), else the HIP-event duration of its kernel launches. */
 double psk_last_scan_ms(const psk_ctx *ctx);
 /* Re-launches the last chi2 scan `reps` times back to back on the context's stream and
  * returns the mean kernel duration in ms measured with HIP events on that stream. */

@@ -461,6 +461,8 @@ __global__ __launch_bounds__(SC_THREADS) void chi2_scan_kernel_cx_side_pc(const 
 // flagship every such row survives, so the appends are taken per wave: one atomicAdd of the keepers' number, each keeper
 // at base + its rank, clamped as reserve_slot clamps (an overflow still reaches the host as a count above seg_cap).
 // As many workgroups as the rows need: the segments beyond the grid are published by workgroup 0 before its rows.
+// Up to SC_NSEG one-wave workgroups (the flagship: 28), each is its segment's only writer and counts its keepers in a
+// register: the append and the publish atomics above are the launches' of more workgroups than segments (r31).
 template <int CPR>
 __global__ __launch_bounds__(CX_IDX_THREADS) void chi2_scan_kernel_cx_side_idx(const CxSideIdxArgs X)
 {
@@ -471,6 +473,11 @@ __global__ __launch_bounds__(CX_IDX_THREADS) void chi2_scan_kernel_cx_side_idx(c
     const int lane = threadIdx.x & 63;
     const uint64_t e0 = X.run_len[0], e1 = e0 + X.run_len[1], e2 = e1 + X.run_len[2], T = e2 + X.run_len[3];
     const uint32_t seg = blockIdx.x & (SC_NSEG - 1);
+    // A workgroup of one wave in a launch of at most SC_NSEG workgroups is its segment's only writer, so the wave keeps the
+    // segment's count itself (r31): no atomic per append, none to publish -- the segment's counter line is never touched
+    // and stands at zero for the next scan -- and the one atomic round trip left in its tail is the summary's ticket.
+    const bool sole = CX_IDX_THREADS == 64 && gridDim.x <= (uint32_t)SC_NSEG;
+    uint32_t n_own = 0;   // wave-uniform
     // (t0 is the workgroup's: whole waves walk the loop, the ballot below sees all 64 lanes)
     for (uint64_t t0 = (uint64_t)blockIdx.x * CX_IDX_THREADS; t0 < T; t0 += (uint64_t)gridDim.x * CX_IDX_THREADS) {
         const uint64_t t = t0 + threadIdx.x;
@@ -500,16 +507,24 @@ __global__ __launch_bounds__(CX_IDX_THREADS) void chi2_scan_kernel_cx_side_idx(c
         if (freq_ok && chi2_pretest(A, B, C, D, K.thr)) keep = chi2_keep(K, A, B, C, D, stat, p);
         const uint64_t keepers = __ballot(keep);
         if (keepers) {   // wave-uniform
-            uint32_t base = 0;
-            if (lane == 0) base = atomicAdd(&S.counter[seg * SC_CNT_STRIDE], (uint32_t)__popcll(keepers));
-            base = __builtin_amdgcn_readfirstlane(base);
+            uint32_t base = n_own;
+            if (sole) n_own += (uint32_t)__popcll(keepers);
+            else {
+                if (lane == 0) base = atomicAdd(&S.counter[seg * SC_CNT_STRIDE], (uint32_t)__popcll(keepers));
+                base = __builtin_amdgcn_readfirstlane(base);
+            }
             if (keep) {
                 const uint32_t idx = base + (uint32_t)__popcll(keepers & ((1ull << lane) - 1ull));
                 chi2_store(S, (uint64_t)seg * S.seg_cap + (idx < S.seg_cap ? idx : S.seg_cap - 1), row, stat, p, n_w);
             }
         }
     }
-    publish_segment_once(S);
+    if (sole) {   // (the wave's own stores need no barrier before its own publish)
+        if (threadIdx.x == 0) {
+            S.final_counts[seg] = n_own;
+            stamp_segment(S, seg, n_own);
+        }
+    } else publish_segment_once(S);
 }
 
 // Second pass of the weighted chi2 scan: one workgroup per result segment, one candidate per lane.  The 2 x 2 table is

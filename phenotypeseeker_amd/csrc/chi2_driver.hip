@@ -160,8 +160,13 @@ int chi2_scan_launch(psk_ctx *ctx, const int8_t *pheno, const double *weights, i
     // its kernel writes to pinned memory -- the dispatch carries no events; 0: from an event pair on the dispatch.  The
     // weighted scan is two kernels and keeps its events either way, and so do the scans of a context whose survivors are
     // exported on another stream (psk_export_survivors_async: that export needs the scan COMPLETE, not merely published).
-    int wait_by_stamps = 1;
+    // A stamped scan of few enough workgroups (stamp_summary_used) is ended by the summary line its last publisher writes,
+    // and its per-segment counts are read when a result call asks (PSK_SCAN_SUMMARY=1); 0: psk_scan_end waits for the 256
+    // count words as well, sums them itself and keeps them -- the A/B switch of the host's side within one build (the
+    // kernel writes the same words either way).  A larger launch writes no summary and is waited for word by word.
+    int wait_by_stamps = 1, end_by_summary = 1;
     PSK_TRY(env_choice(ctx, "PSK_SCAN_WAIT", {0, 1}, &wait_by_stamps));
+    PSK_TRY(env_choice(ctx, "PSK_SCAN_SUMMARY", {0, 1}, &end_by_summary));
     PSK_HIP(ctx, hipSetDevice(ctx->device));
     const int N = ctx->n_samples, wpr = mask_words(ctx);   // masks and tables: whole 16-byte chunks, also for 8-byte rows
     // one pinned staging block [m1 | m0 | w1 | w0] and ONE stream-ordered upload (weights only when given)
@@ -216,11 +221,14 @@ int chi2_scan_launch(psk_ctx *ctx, const int8_t *pheno, const double *weights, i
         launch_chi2_any(ctx, CL, stamped ? TimedBy{} : TimedBy{sl.ev0, sl.ev1});   // (the events ride on the dispatch: one command per scan)
         PSK_HIP(ctx, hipGetLastError());
         sl.stamped = stamped;
+        sl.has_summary = stamped && stamp_summary_used(CL.grid.x);   // (the kernel decides by the same function of its grid)
+        sl.by_summary = sl.has_summary && end_by_summary == 1;
         sl.in_flight = true;
         ctx->n_in_flight++;
     } else {  // nothing to scan: an empty result, at once
         ctx->n_pass = 0;
         ctx->seg_counts.assign(SC_NSEG, 0);
+        ctx->counts_pending = false;
         ctx->res_set = set;
         ctx->results_valid = true;
     }
@@ -247,21 +255,28 @@ int rescan(psk_ctx *ctx, int reps, double *mean_ms, double *ms_each)
     return PSK_OK;
 }
 
-// Waits for the stamps of the scan in flight on result set `set` (launched without events) and takes its time from
-// their clocks.  The host spins on pinned memory -- the words arrive while the kernel's last workgroups end --, asks the
-// stream now and then whether the scan has failed or ended without a word, and gives up after WAIT_LIMIT: it never
-// loops without a bound.
-int wait_stamps(psk_ctx *ctx, int set)
+}  // namespace
+
+// Waits for words that the scan bound to result set `set` (launched without events) stamps into pinned memory: its summary
+// line, which the scan's last publisher writes -- the scan has ended, n_pass and the clocks are there --, its count
+// words, both, or -- a launch too large for the summary -- its count words and the clock beside each (StampWait,
+// scan_common.h).  The host spins on pinned memory -- the words arrive while the kernel's last
+// workgroups end --, asks the stream now and then whether the scan has failed or ended without a word, and gives up
+// after WAIT_LIMIT: it never loops without a bound.  With clocks awaited, the scan's time is taken from them.
+int wait_stamps(psk_ctx *ctx, int set, StampWait what)
 {
     using clk = std::chrono::steady_clock;
     constexpr auto QUERY_EVERY = std::chrono::microseconds(20), YIELD_AFTER = std::chrono::microseconds(50);
     constexpr auto WAIT_LIMIT = std::chrono::seconds(30);
-    const volatile uint64_t *counts = scan_stamp_words(ctx, set), *clocks = counts + STAMP_NSEG;
+    const volatile uint64_t *words = scan_stamp_words(ctx, set);
     const uint32_t seq = (uint32_t)ctx->slot[set].seq;
-    int nc = 0, nk = 0;   // words seen so far: a stamp that has arrived stays
+    const bool want_summary = what == STAMP_WAIT_SUMMARY || what == STAMP_WAIT_ALL, want_counts = what != STAMP_WAIT_SUMMARY;
+    int nc = want_counts ? 0 : STAMP_NSEG;   // count words seen so far: a stamp that has arrived stays
+    int nk = what == STAMP_WAIT_SEGMENTS ? 0 : STAMP_CLOCKS;   // ... and clock words
     auto all_here = [&] {
-        nc = stamp_counts_missing(counts, seq, nc);
-        if (nc == STAMP_NSEG) nk = stamp_clocks_missing(clocks, seq, nk);
+        if (want_summary && !stamp_summary_ready(words, seq)) return false;
+        if (nc < STAMP_NSEG) nc = stamp_counts_missing(words, seq, nc);
+        if (nc == STAMP_NSEG && nk < STAMP_CLOCKS) nk = stamp_clocks_missing(words + STAMP_NSEG, seq, nk);
         return nc == STAMP_NSEG && nk == STAMP_CLOCKS;
     };
     if (!all_here()) {
@@ -275,6 +290,7 @@ int wait_stamps(psk_ctx *ctx, int set)
                 const hipError_t e = hipStreamQuery(ctx->stream);
                 if (e == hipSuccess) {   // everything queued has ended: the words are there now, or never will be
                     if (all_here()) break;
+                    if (want_summary && !stamp_summary_ready(words, seq)) return psk_fail(ctx, PSK_ESTATE, "scan ended without publishing (summary of scan %u)", seq);
                     return psk_fail(ctx, PSK_ESTATE, "scan ended without publishing (segment %d of scan %u)", nc < STAMP_NSEG ? nc : nk, seq);
                 }
                 if (e != hipErrorNotReady) return psk_fail(ctx, PSK_EHIP, "hipStreamQuery failed while scan %u was awaited: %s", seq, hipGetErrorString(e));
@@ -285,11 +301,10 @@ int wait_stamps(psk_ctx *ctx, int set)
             if (now - t0 > YIELD_AFTER) sched_yield();
         }
     }
-    ctx->last_scan_ms = (double)stamp_scan_ticks(clocks) / ctx->wall_clock_khz;
+    if (want_summary) ctx->last_scan_ms = (double)stamp_summary_ticks(words) / ctx->wall_clock_khz;
+    if (what == STAMP_WAIT_SEGMENTS) ctx->last_scan_ms = (double)stamp_scan_ticks(words + STAMP_NSEG) / ctx->wall_clock_khz;
     return PSK_OK;
 }
-
-}  // namespace
 
 extern "C" int psk_chi2_scan_begin(psk_ctx *ctx, const int8_t *pheno, const double *weights, int min_samples,
                                    int max_samples, double pvalue_cutoff, int omit_B, uint64_t n_kmers_global)
@@ -305,11 +320,24 @@ extern "C" int psk_scan_end(psk_ctx *ctx, uint64_t *n_pass)
         int set = ctx->slot[0].in_flight ? 0 : 1;
         if (ctx->slot[0].in_flight && ctx->slot[1].in_flight && ctx->slot[1].seq < ctx->slot[0].seq) set = 1;
         ScanSlot &sl = ctx->slot[set];
+        bool counts_later = false;
         if (sl.stamped) {
-            const int rc = wait_stamps(ctx, set);   // the kernel's own words: no event on the dispatch, no runtime call when the GPU is ahead
+            // the kernel's own words: no event on the dispatch, no runtime call when the GPU is ahead
+            const int rc = wait_stamps(ctx, set, sl.by_summary ? STAMP_WAIT_SUMMARY : sl.has_summary ? STAMP_WAIT_ALL : STAMP_WAIT_SEGMENTS);
             sl.in_flight = false;
             ctx->n_in_flight--;
             PSK_TRY(rc);
+            if (sl.by_summary) {
+                // one line says it all: n_pass, and whether a segment overflowed.  Only then are the count words waited
+                // for and read here, so that PSK_ERANGE comes from this call as it always has (fetch_counts).
+                const volatile uint64_t *words = scan_stamp_words(ctx, set);
+                const uint64_t hi = stamp_load(words + STAMP_SUM_HI);
+                if (stamp_sum_overflow(hi)) PSK_TRY(wait_stamps(ctx, set, STAMP_WAIT_COUNTS));
+                else {
+                    hold_results_unread(ctx, set, stamp_sum_n_pass(stamp_load(words + STAMP_SUM_LO), hi));
+                    counts_later = true;
+                }
+            }
         } else {
             PSK_HIP(ctx, hipEventSynchronize(sl.ev1));  // its kernels have written the counts to pinned memory
             sl.in_flight = false;
@@ -318,7 +346,7 @@ extern "C" int psk_scan_end(psk_ctx *ctx, uint64_t *n_pass)
             PSK_HIP(ctx, hipEventElapsedTime(&ms, sl.ev0, sl.ev1));
             ctx->last_scan_ms = ms;
         }
-        PSK_TRY(fetch_counts(ctx, set));
+        if (!counts_later) PSK_TRY(fetch_counts(ctx, set));
         ctx->dense_hint = ctx->n_pass * 1000 > ctx->n_kmers ? 1 : 0;  // only chi2 scans come through here
     }
     if (n_pass) *n_pass = ctx->n_pass;

@@ -123,6 +123,8 @@ struct ScanSlot {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;   // around the scan's kernels (scans that are waited for by event)
     bool stamped = false;            // the set's last scan carried no events: psk_scan_end waits (waited) for its stamps, and its
                                      // dispatch may still be retiring when that returns -- see psk_export_survivors_async
+    bool has_summary = false;        // ... in a launch small enough to write a summary line (stamp_summary_used, scan_stamps.h)
+    bool by_summary = false;         // ... which psk_scan_end polls alone (PSK_SCAN_SUMMARY=1, read when the scan was launched)
     hipEvent_t ev_ended = nullptr;   // recorded on ctx->stream when another stream has to be ordered behind a stamped scan
     hipEvent_t ev_export = nullptr;  // recorded on the caller's stream after an asynchronous export of this set
     bool export_pending = false;     // the next scan that writes this set waits for ev_export on the device
@@ -227,7 +229,8 @@ struct psk_ctx {
     bool lut6_valid = false;             // ... in its six-bit f32 form (row_moments_f32)
     uint64_t n_pass = 0;
     uint64_t res_seg_cap = 0;            // entries per result segment of the last scan
-    std::vector<uint32_t> seg_counts;    // survivors per segment
+    std::vector<uint32_t> seg_counts;    // survivors per segment; read through held_seg_counts (scan_results.hip) only
+    bool counts_pending = false;         // psk_scan_end took n_pass from the scan's summary line: seg_counts is read on the first result call
     int last_scan_kind = 0;  // 1 chi2, 2 ttest
     int dense_hint = -1;     // did the last chi2 scan of this matrix keep > 0.1 % of the rows?  (-1: no scan yet)
     double last_scan_ms = 0;

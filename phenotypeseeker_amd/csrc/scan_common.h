@@ -86,11 +86,42 @@ __device__ __forceinline__ void stamp_store(uint64_t *p, uint64_t v) { __hip_ato
 __device__ __forceinline__ void stamp_clock(const ScanSink &S, int slot) { stamp_store(S.host_counts + STAMP_NSEG + slot, stamp_clock_word(S.seq, (uint64_t)wall_clock64())); }
 // a segment's count (the finalize kernels of the two-kernel scans: they are waited for and timed by events)
 __device__ __forceinline__ void stamp_count(const ScanSink &S, uint32_t seg, uint32_t c) { stamp_store(S.host_counts + seg, stamp_count_word(S.seq, c)); }
-// ... with the clock just before it: the single-kernel chi2 scans, whose time is the last of these less the start clock
+// The ticket line of the single-kernel chi2 scans (scan_stamps.h: stamp_ticket_*): one more 128-byte counter line behind
+// the two sets' final_counts, part of the same allocation and of its one memset (bind_results), shared by both result
+// sets as the segment counters are -- the scans of a context run one after the other on its stream.
+constexpr int SC_TICKET_OFFSET = SC_NSEG * SC_CNT_STRIDE + 2 * SC_NSEG;   // u32 from ScanSink::counter
+constexpr int SC_COUNTER_WORDS = SC_TICKET_OFFSET + SC_CNT_STRIDE;        // u32 of the whole counter block
+static_assert(SC_TICKET_OFFSET % SC_CNT_STRIDE == 0, "the ticket line starts a 128-byte line");
+// Called by the one thread that has just published segment count c (a segment some workgroup maps to: the unowned
+// segments of a short launch take no ticket).  One 64-bit atomic adds the count and a ticket and returns the scan's sum
+// so far; whoever draws the last ticket therefore holds n_pass -- every other publisher added its count in the same
+// atomic that took its ticket, so, as in publish_segment_once, no fence is needed -- and writes the summary line the
+// host polls: the end clock and n_pass in two words, each tagged.  It re-arms the line for the next scan with one store,
+// at device scope and not a plain one as publish_segment_once's: a segment's workgroups need not share an L2 with this
+// line's other writers.  Nothing waits here: a publisher that is not the last simply ends.
+__device__ __forceinline__ void publish_summary(const ScanSink &S, uint32_t c)
+{
+    unsigned long long *line = reinterpret_cast<unsigned long long *>(S.counter + SC_TICKET_OFFSET);
+    const uint64_t add = stamp_ticket_addend(c, S.seg_cap);
+    const uint64_t before = atomicAdd(line, (unsigned long long)add);
+    if (!stamp_ticket_is_last(before, stamp_ticket_publishers(gridDim.x))) return;
+    __hip_atomic_store(line, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint64_t after = before + add;
+    stamp_store(S.host_counts + STAMP_SUM_END, stamp_clock_word(S.seq, (uint64_t)wall_clock64()));
+    stamp_store(S.host_counts + STAMP_SUM_LO, stamp_sum_lo_word(S.seq, stamp_ticket_total(after)));
+    stamp_store(S.host_counts + STAMP_SUM_HI, stamp_sum_hi_word(S.seq, stamp_ticket_total(after), stamp_ticket_overflow(after)));
+}
+// a published segment of a single-kernel chi2 scan: its count word, and in a launch small enough for the summary
+// (stamp_summary_used) its ticket; in a larger one the clock just before the count, as until r31
 __device__ __forceinline__ void stamp_segment(const ScanSink &S, uint32_t seg, uint32_t c)
 {
-    stamp_clock(S, (int)seg);
-    stamp_count(S, seg, c);
+    if (stamp_summary_used(gridDim.x)) {
+        stamp_count(S, seg, c);
+        publish_summary(S, c);
+    } else {
+        stamp_clock(S, (int)seg);
+        stamp_count(S, seg, c);
+    }
 }
 // first thing in a single-kernel chi2 scan: the start clock
 __device__ __forceinline__ void stamp_scan_start(const ScanSink &S)
@@ -141,13 +172,17 @@ __device__ __forceinline__ void publish_segment_once(const ScanSink &S)
 // A launch of fewer than SC_NSEG workgroups (chi2_scan_kernel_cx_side_idx) has segments that no workgroup maps to:
 // [gridDim.x, SC_NSEG).  Nothing is appended to them, so their counter lines stand at zero as the last scan's publish left
 // them; every thread of ONE workgroup calls this and thread i publishes segments gridDim.x + i, + blockDim.x, ... as
-// empty -- the compact count, the clock word, the count word -- so a wave's stores are consecutive 8-byte words.  With
-// the owned segments' publish_segment_once this leaves a result set exactly as a launch of SC_NSEG workgroups does.
+// empty -- the compact count and the count word -- so a wave's stores are consecutive 8-byte words.  They take no ticket
+// (publish_summary counts min(gridDim.x, SC_NSEG) publishers); in a launch too large for the summary they get their clock
+// word as well.  With the owned segments' publish_segment_once this leaves a result set exactly as a launch of SC_NSEG
+// workgroups does.
 __device__ __forceinline__ void publish_unowned_segments(const ScanSink &S)
 {
+    const bool clocks = !stamp_summary_used(gridDim.x);
     for (uint32_t seg = gridDim.x + threadIdx.x; seg < (uint32_t)SC_NSEG; seg += blockDim.x) {
         S.final_counts[seg] = 0;
-        stamp_segment(S, seg, 0);
+        if (clocks) stamp_clock(S, (int)seg);
+        stamp_count(S, seg, 0);
     }
 }
 
@@ -163,7 +198,17 @@ int setup_results_rows(psk_ctx *ctx, ScanSink &s, dim3 grid, uint64_t rows_per_b
 int setup_results(psk_ctx *ctx, ScanArgs &a, dim3 grid, int G, int unroll, int set, int threads = SC_THREADS);
 int pick_result_set(psk_ctx *ctx, int *set_out, bool keep_results = false);
 int fetch_counts(psk_ctx *ctx, int set);
+void hold_results_unread(psk_ctx *ctx, int set, uint64_t n_pass);
+int held_seg_counts(psk_ctx *ctx, const std::vector<uint32_t> **counts);
 const volatile uint64_t *scan_stamp_words(const psk_ctx *ctx, int set);
+// chi2_driver.hip: the bounded wait for words of result set `set` that its scan's kernel stamps
+enum StampWait {
+    STAMP_WAIT_SUMMARY,   // the summary line: the scan has ended, n_pass and its time are there
+    STAMP_WAIT_COUNTS,    // the STAMP_NSEG count words
+    STAMP_WAIT_ALL,       // both (PSK_SCAN_SUMMARY=0: the counts are summed by the host, the time is the summary's)
+    STAMP_WAIT_SEGMENTS,  // the count words and the STAMP_CLOCKS clock words of a launch too large for the summary: as until r31
+};
+int wait_stamps(psk_ctx *ctx, int set, StampWait what);
 // ttest_scan.hip: the moment tables (their two building kernels live there, for both scans)
 struct ScanShape {   // what a scan launches with
     dim3 grid;

@@ -41,9 +41,9 @@ int bind_results(psk_ctx *ctx, ScanSink &s, uint64_t seg_cap, int set)
         a.res_mx = reinterpret_cast<double *>(b + cap * 24);
         a.res_my = reinterpret_cast<double *>(b + cap * 32);
         a.res_nw = reinterpret_cast<int32_t *>(b + cap * 40);
-        if (!ctx->res_count.p) {  // counters re-arm themselves at the end of every scan: zeroed once
-            PSK_TRY(dev_reserve(ctx, ctx->res_count, (SC_NSEG * SC_CNT_STRIDE + 2 * SC_NSEG) * 4));
-            PSK_HIP(ctx, hipMemsetAsync(ctx->res_count.p, 0, (SC_NSEG * SC_CNT_STRIDE + 2 * SC_NSEG) * 4, ctx->stream));
+        if (!ctx->res_count.p) {  // counters (the ticket line among them) re-arm themselves at the end of every scan: zeroed once
+            PSK_TRY(dev_reserve(ctx, ctx->res_count, SC_COUNTER_WORDS * 4));
+            PSK_HIP(ctx, hipMemsetAsync(ctx->res_count.p, 0, SC_COUNTER_WORDS * 4, ctx->stream));
         }
         if (!ctx->cnt_pinned) {
             // coherent, said explicitly: the host reads the stamps while the kernel that writes them still runs.  Zeroed:
@@ -75,7 +75,10 @@ int bind_results(psk_ctx *ctx, ScanSink &s, uint64_t seg_cap, int set)
     s = sl.sink;
     s.seq = (uint32_t)sl.seq;
     sl.seg_cap = seg_cap;
-    if (set == ctx->res_set) ctx->results_valid = false;  // the last ended scan's results are about to go
+    if (set == ctx->res_set) {  // the last ended scan's results are about to go, its count words with them, read or not
+        ctx->results_valid = false;
+        ctx->counts_pending = false;
+    }
     return PSK_OK;
 }
 
@@ -122,6 +125,39 @@ int fetch_counts(psk_ctx *ctx, int set)
     ctx->res_set = set;
     ctx->res_seg_cap = seg_cap;
     ctx->results_valid = true;
+    ctx->counts_pending = false;
+    return PSK_OK;
+}
+
+// What psk_scan_end leaves of a scan it ended by the summary line alone (chi2_driver.hip): n_pass and the set, with the
+// per-segment counts still where the kernel wrote them.
+void hold_results_unread(psk_ctx *ctx, int set, uint64_t n_pass)
+{
+    ctx->n_pass = n_pass;
+    ctx->res_set = set;
+    ctx->res_seg_cap = ctx->slot[set].seg_cap;
+    ctx->results_valid = true;
+    ctx->counts_pending = true;
+}
+
+// The one way to the per-segment counts of the held results (the caller has checked results_valid).  The first call after
+// a scan that was ended by its summary reads the set's count words -- a word may still be on its way when the summary has
+// arrived: the same bounded wait as psk_scan_end's, then fetch_counts and its tag check -- and they must add up to the
+// summary's n_pass.  A set that is bound to a new scan before anyone asks is never read.
+int held_seg_counts(psk_ctx *ctx, const std::vector<uint32_t> **counts)
+{
+    if (ctx->counts_pending) {
+        const uint64_t n_summary = ctx->n_pass;
+        const int set = ctx->res_set;
+        PSK_TRY(wait_stamps(ctx, set, STAMP_WAIT_COUNTS));
+        PSK_TRY(fetch_counts(ctx, set));
+        if (ctx->n_pass != n_summary) {
+            ctx->results_valid = false;
+            return psk_fail(ctx, PSK_ESTATE, "the segments of scan %u hold %llu survivors, its summary said %llu", (uint32_t)ctx->slot[set].seq,
+                            (unsigned long long)ctx->n_pass, (unsigned long long)n_summary);
+        }
+    }
+    if (counts) *counts = &ctx->seg_counts;
     return PSK_OK;
 }
 
@@ -200,16 +236,18 @@ extern "C" int psk_get_results(psk_ctx *ctx, uint64_t *row_idx, uint64_t *words,
                                  (unsigned long long)n);
     if (n == 0) return PSK_OK;
     PSK_HIP(ctx, hipSetDevice(ctx->device));
+    const std::vector<uint32_t> *seg_counts = nullptr;
+    PSK_TRY(held_seg_counts(ctx, &seg_counts));
     // pack the segments into contiguous SoA arrays of n entries
     {
         std::vector<uint64_t> offs(SC_NSEG);
         uint64_t acc = 0;
-        for (int sgm = 0; sgm < SC_NSEG; sgm++) { offs[sgm] = acc; acc += ctx->seg_counts[sgm]; }
+        for (int sgm = 0; sgm < SC_NSEG; sgm++) { offs[sgm] = acc; acc += (*seg_counts)[sgm]; }
         PSK_TRY(dev_reserve(ctx, ctx->res_sorted, n * 52 + 128 + SC_NSEG * 12));
         uint8_t *aux = ctx->res_sorted.as<uint8_t>() + ((n * 52 + 63) & ~63ull);
         uint32_t *d_cnt = reinterpret_cast<uint32_t *>(aux + SC_NSEG * 8);
         PSK_HIP(ctx, hipMemcpyAsync(aux, offs.data(), SC_NSEG * 8, hipMemcpyHostToDevice, ctx->stream));
-        PSK_HIP(ctx, hipMemcpyAsync(d_cnt, ctx->seg_counts.data(), SC_NSEG * 4, hipMemcpyHostToDevice, ctx->stream));
+        PSK_HIP(ctx, hipMemcpyAsync(d_cnt, seg_counts->data(), SC_NSEG * 4, hipMemcpyHostToDevice, ctx->stream));
         pack_segments_kernel<<<SC_NSEG, 256, 0, ctx->stream>>>(ctx->slot[ctx->res_set].res.as<uint8_t>(), ctx->res_seg_cap * SC_NSEG,
                                                              (uint32_t)ctx->res_seg_cap, d_cnt,
                                                              reinterpret_cast<const uint64_t *>(aux),
@@ -304,6 +342,7 @@ extern "C" int psk_export_survivors(psk_ctx *ctx, void *device_dst, uint64_t cap
     if (!ctx->results_valid) return psk_fail(ctx, PSK_ESTATE, "no ended scan whose results are still held (psk_scan_end first)");
     if (!device_dst || cap_records < 1) return psk_fail(ctx, PSK_EINVAL, "bad destination");
     PSK_HIP(ctx, hipSetDevice(ctx->device));
+    PSK_TRY(held_seg_counts(ctx, nullptr));   // (the kernel reads the device's compact counts; the host's copy is checked as psk_scan_end used to)
     if (n_records) *n_records = ctx->n_pass;
     export_records_kernel<<<SC_NSEG, SC_NSEG, 0, ctx->stream>>>(
         ctx->slot[ctx->res_set].res.as<uint8_t>(), ctx->res_seg_cap * SC_NSEG, (uint32_t)ctx->res_seg_cap,
@@ -325,6 +364,7 @@ extern "C" int psk_export_survivors_async(psk_ctx *ctx, void *device_dst, uint64
     if (!ctx->results_valid) return psk_fail(ctx, PSK_ESTATE, "no ended scan whose results are still held (psk_scan_end first)");
     if (!device_dst || cap_records < 1) return psk_fail(ctx, PSK_EINVAL, "bad destination");
     PSK_HIP(ctx, hipSetDevice(ctx->device));
+    PSK_TRY(held_seg_counts(ctx, nullptr));   // (the kernel reads the device's compact counts; the host's copy is checked as psk_scan_end used to)
     hipStream_t st = static_cast<hipStream_t>(stream);
     ScanSlot &sl = ctx->slot[ctx->res_set];
     // A scan that psk_scan_end waited for by its event has completed: its rows and counts are visible to any stream.  A

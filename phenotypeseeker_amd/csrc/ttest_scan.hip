@@ -593,6 +593,7 @@ extern "C" int psk_ttest_scan(psk_ctx *ctx, const double *pheno, const uint8_t *
         PSK_TRY(fetch_counts(ctx, set));
     } else {
         ctx->seg_counts.assign(SC_NSEG, 0);
+        ctx->counts_pending = false;
         ctx->res_set = set;
         ctx->results_valid = true;
     }
