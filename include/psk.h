@@ -726,6 +726,36 @@ int psk_svc_decision(psk_ctx *ctx, const float *X, int m, int p, const float *SV
  *   raw_out[n]   init_raw, then + learning_rate * value[leaf] stage after stage in stage order
  * which is psk_gb_fit's raw_out bit for bit on the fit's own rows.  PSK_EINVAL also for a tree that is not pre-order (a child
  * not behind its parent or outside node_count) or splits on a column outside 0 .. p - 1.
+ *
+ * psk_gb_fit_counts: psk_gb_fit on a COUNT design (`--real_counts`; the yardstick is the same scikit-learn estimator fitted on the
+ * float32 count matrix).  X[n][p] holds integers in 0 .. 2^24 (PSK_EINVAL otherwise, in the words of psk_tree_fit_counts, which
+ * name sample and column).  Every other argument, limit and refusal is psk_gb_fit's, and so is the arithmetic, with the columns
+ * replaced by THRESHOLD PLANES:
+ *   planes     built per call over all n samples (csrc/solver_tree_common.h, tree_pack_counts): a column with the distinct values
+ *              g_0 < g_1 < ... has plane k with bit s = (x_sj >= g_(k+1)); planes are ordered by (column, k); a column that is
+ *              constant over all samples has none.  More than PSK_TREE_PLANE_CAP planes: PSK_ERANGE
+ *   candidate  a plane whose set bits within the node's in-bag set S number c with 0 < c < w.  w_r = c; sum_r = the sum of r over
+ *              the plane's set bits in S, EACH PLANE'S SUM TAKEN ON ITS OWN in the two-level order (within a word of 64 samples
+ *              ascending from +0.0, then the word partials ascending), never accumulated across the nested planes of a column;
+ *              sum_l, diff and proxy as above
+ *   winner     the largest proxy, THE LOWEST PLANE INDEX among bit-equal maxima.  Planes of one column that lie between the same
+ *              two values present in S select the same samples and give bit-equal proxies, so the rule reads "lowest column, then
+ *              lowest threshold": scikit-learn's walk over the gaps between the values present in the node
+ *   threshold  lo / 2.0 + hi / 2.0, lo the largest value below the winning plane's g and hi the smallest value at or above it,
+ *              both among the node's IN-BAG samples
+ *   routing    the children's masks come from the plane k of that column with g_k <= threshold < g_(k+1) over all samples' values,
+ *              not from the plane that won: a held-out sample whose value lies inside the gap goes by x <= threshold (a node with
+ *              in-bag values {0, 3} splits at 1.5, a held-out 1 goes left)
+ *   leaves     leaf rules, Newton leaf values, pre-order numbering, the update of F and the held-out rule are unchanged; a design
+ *              without planes gives single-leaf stages
+ * Outputs as psk_gb_fit, with nodes_out[..][0] the design COLUMN of a split (not the plane) and
+ *   threshold_out[n_fits][n_estimators][cap]   the threshold at a split; -2.0 at a leaf and in the slots behind node_count
+ * On a 0/1 design every output equals psk_gb_fit's and every split threshold is 0.5.
+ *
+ * psk_gb_decision_counts: psk_gb_decision for such a model, threshold[n_estimators][cap] beside nodes and value.  One thread per
+ * sample reads the float design: X[s][feature] <= threshold goes left.  X must be a count design as above; no planes are made and
+ * there is no sample cap.  PSK_EINVAL as psk_gb_decision, and for a split whose threshold is not finite.  On the fit's own rows
+ * raw_out is psk_gb_fit_counts's raw_out bit for bit.
  */
 #define PSK_GB_NODE_CAP(max_depth) ((2 << (max_depth)) - 1)
 int psk_gb_fit(psk_ctx *ctx, const float *X, const double *y, int n, int p, const int32_t *fold, const int32_t *fit_fold,
@@ -734,6 +764,13 @@ int psk_gb_fit(psk_ctx *ctx, const float *X, const double *y, int n, int p, cons
                double *staged_out);
 int psk_gb_decision(psk_ctx *ctx, const float *X, int n, int p, int n_estimators, int max_depth, const int32_t *node_count,
                     const int32_t *nodes, const double *value, double init_raw, double learning_rate, double *raw_out);
+int psk_gb_fit_counts(psk_ctx *ctx, const float *X, const double *y, int n, int p, const int32_t *fold, const int32_t *fit_fold,
+                      int n_fits, int loss, int n_estimators, double learning_rate, int max_depth, const double *init_raw,
+                      int32_t *node_count_out, int32_t *nodes_out, double *value_out, double *impurity_out,
+                      double *threshold_out, double *raw_out, double *staged_out);
+int psk_gb_decision_counts(psk_ctx *ctx, const float *X, int n, int p, int n_estimators, int max_depth,
+                           const int32_t *node_count, const int32_t *nodes, const double *value, const double *threshold,
+                           double init_raw, double learning_rate, double *raw_out);
 
 /* ---- f1: fixed-dictionary counting (prediction) ---------------------------------------------
  * Replaces `gmer_counter -db <txt> <addr>` (prediction.Samples.map_samples, prediction.py:72-80):

@@ -123,6 +123,11 @@ _SIGNATURES = {
                              c.c_double, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]),
     "psk_gb_decision": (c.c_int, [c.c_void_p, c.c_void_p, c.c_int, c.c_int, c.c_int, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p,
                                   c.c_double, c.c_double, c.c_void_p]),
+    "psk_gb_fit_counts": (c.c_int, [c.c_void_p, c.c_void_p, c.c_void_p, c.c_int, c.c_int, c.c_void_p, c.c_void_p, c.c_int, c.c_int,
+                                    c.c_int, c.c_double, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
+                                    c.c_void_p, c.c_void_p]),
+    "psk_gb_decision_counts": (c.c_int, [c.c_void_p, c.c_void_p, c.c_int, c.c_int, c.c_int, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p,
+                                         c.c_void_p, c.c_double, c.c_double, c.c_void_p]),
     "psk_pca_fit": (c.c_int, [c.c_void_p, c.c_void_p, c.c_int, c.c_int, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
                               c.c_void_p, c.c_void_p, c.c_void_p]),
     "psk_pca_transform": (c.c_int, [c.c_void_p, c.c_void_p, c.c_int, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int,

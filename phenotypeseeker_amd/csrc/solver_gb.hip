@@ -24,6 +24,11 @@
 // Kernels: tree_pack_kernel (solver_tree_common.h) packs the design; gb_fit_kernel runs one workgroup per fit through all
 // stages, with the stage's residuals (f64, 4096 samples = 32 KB) and the routing masks of the current path in LDS and F in
 // global memory; gb_decision_kernel walks a fitted model with one thread per sample.
+// COUNT DESIGNS (psk_gb_fit_counts / psk_gb_decision_counts, include/psk.h f16): the columns above become the threshold planes of
+// tree_pack_counts (solver_tree_common.h), scanned in plane order, each plane's sum of residuals taken on its own in the
+// two-level order; the node record gets the winning plane's column, the threshold comes from the node's in-bag values
+// (tree_node_threshold) and the children are routed by the plane of tree_route_plane.  gb_decision_counts_kernel reads the
+// float design itself: x <= threshold goes left.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
@@ -54,12 +59,15 @@ struct GbRec { int parent, depth, is_left; };
 // the totals of a node, made by one lane over the word partials
 struct GbNode { double sum, sq, hess; int w, all_equal; };
 
-template <int LOSS>
+// COUNTS: `bits` holds the P threshold planes of a count design and p is P, so the scan below is the lowest column, then the
+// lowest threshold (tree_build of solver_tree.hip does the same); thr_out gets scikit-learn's threshold, -2.0 at a leaf.
+template <int LOSS, bool COUNTS>
 __global__ __launch_bounds__(GB_THREADS) void gb_fit_kernel(
     const uint64_t *__restrict__ bits, const double *__restrict__ y, const int32_t *__restrict__ fold, int n, int p, int W,
     const int32_t *__restrict__ fit_fold, const double *__restrict__ init_raw, int n_estimators, double learning_rate, int max_depth,
     int cap, int32_t *__restrict__ node_count, int32_t *__restrict__ nodes, double *__restrict__ value_out,
-    double *__restrict__ imp_out, double *__restrict__ raw, double *__restrict__ staged)
+    double *__restrict__ imp_out, double *__restrict__ raw, double *__restrict__ staged, const TreePlaneView<COUNTS> pv,
+    double *__restrict__ thr_out)
 {
     __shared__ double r[GB_MAX_N];
     __shared__ uint64_t mask[GB_MAX_DEPTH + 1][GB_MAX_W];
@@ -71,6 +79,7 @@ __global__ __launch_bounds__(GB_THREADS) void gb_fit_kernel(
     __shared__ double red_v[GB_WAVES];
     __shared__ int red_i[GB_WAVES];
     __shared__ GbNode node;
+    __shared__ int gap[2];   // (COUNTS: the two values around a split, tree_node_threshold)
 
     const int fit = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int tf = fit_fold[fit];
@@ -90,6 +99,7 @@ __global__ __launch_bounds__(GB_THREADS) void gb_fit_kernel(
         const size_t tree = (size_t)fit * n_estimators + stage;
         int32_t *nd = nodes + tree * cap * GB_NODE_FIELDS;
         double *vo = value_out + tree * cap, *io = imp_out + tree * cap;
+        double *to = COUNTS ? thr_out + tree * cap : nullptr;
         __syncthreads();   // every read of the stage before
         for (int s = tid; s < n; s += GB_THREADS) r[s] = LOSS == 0 ? y[s] - F[s] : y[s] - gb_expit(F[s]);
         if (tid == 0) stack[0] = GbRec{-1, 0, 0};
@@ -192,6 +202,18 @@ __global__ __launch_bounds__(GB_THREADS) void gb_fit_kernel(
                 else feat = bi;
             }
             const int id = next_id++;
+            int route = feat;
+            if constexpr (COUNTS) {
+                // (is_leaf is the workgroup's: every thread takes the same side, so the barriers inside are met by all)
+                double thr = -2.0;
+                if (!is_leaf) {
+                    const int col = pv.plane_col[feat];
+                    thr = tree_node_threshold(pv.X, n, pv.p, col, pv.plane_val[feat], MT, gap);
+                    route = tree_route_plane(pv.col_first, pv.plane_val, col, thr);
+                    feat = col;
+                }
+                if (tid == 0) to[id] = thr;
+            }
             double val = mean;
             if (LOSS == 1 && is_leaf) {
                 // _gb.py::_update_terminal_regions, compute_update of the binomial loss, with _safe_divide
@@ -215,7 +237,7 @@ __global__ __launch_bounds__(GB_THREADS) void gb_fit_kernel(
             } else {
                 // (the barrier of the reduction lies between every thread's read of `rec` and these writes)
                 if (tid == 0) {
-                    path_feat[d] = feat;
+                    path_feat[d] = route;
                     stack[sp] = GbRec{id, d + 1, 0};       // the right child, taken after the whole left subtree
                     stack[sp + 1] = GbRec{id, d + 1, 1};
                 }
@@ -252,6 +274,31 @@ __global__ __launch_bounds__(256) void gb_decision_kernel(const uint64_t *__rest
     out[s] = F;
 }
 
+// The same walk on a count design: the float design itself, x <= threshold goes left (a count is exact in f32 and in f64).
+// The host has also checked that a split's threshold is finite.
+__global__ __launch_bounds__(256) void gb_decision_counts_kernel(const float *__restrict__ X, int n, int p, int n_estimators, int cap,
+                                                                 const int32_t *__restrict__ nodes, const double *__restrict__ value,
+                                                                 const double *__restrict__ threshold, double init_raw,
+                                                                 double learning_rate, double *__restrict__ out)
+{
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    const float *x = X + (size_t)s * p;
+    double F = init_raw;
+    for (int t = 0; t < n_estimators; t++) {
+        const int32_t *nd = nodes + (size_t)t * cap * GB_NODE_FIELDS;
+        const double *th = threshold + (size_t)t * cap;
+        int node = 0;
+        for (int step = 0; step < cap; step++) {
+            const int f = nd[(size_t)node * GB_NODE_FIELDS];
+            if (f < 0) break;
+            node = nd[(size_t)node * GB_NODE_FIELDS + ((double)x[f] <= th[node] ? 1 : 2)];
+        }
+        F += learning_rate * value[(size_t)t * cap + node];
+    }
+    out[s] = F;
+}
+
 int gb_check_model_shape(psk_ctx *ctx, const char *who, int n_estimators, int max_depth)
 {
     if (max_depth < 1 || max_depth > GB_MAX_DEPTH)
@@ -261,33 +308,60 @@ int gb_check_model_shape(psk_ctx *ctx, const char *who, int n_estimators, int ma
     return PSK_OK;
 }
 
-}  // namespace
-
-extern "C" int psk_gb_fit(psk_ctx *ctx, const float *X, const double *y, int n, int p, const int32_t *fold, const int32_t *fit_fold,
-                          int n_fits, int loss, int n_estimators, double learning_rate, int max_depth, const double *init_raw,
-                          int32_t *node_count_out, int32_t *nodes_out, double *value_out, double *impurity_out, double *raw_out,
-                          double *staged_out)
+// What both decision calls check before the kernel walks the model: the walk trusts that a split's column exists, that its
+// children lie behind it (pre-order) and inside the tree and, with thresholds, that a split's threshold is finite.
+int gb_check_model(psk_ctx *ctx, const char *who, const float *X, int n, int p, int n_estimators, int max_depth, const int32_t *node_count,
+                   const int32_t *nodes, const double *value, const double *threshold, bool counts, const double *raw_out)
 {
     if (!ctx) return PSK_EINVAL;
-    if (!X || !y || !fold || !fit_fold || !init_raw || !node_count_out || !nodes_out || !value_out || !impurity_out || !raw_out)
-        return psk_fail(ctx, PSK_EINVAL, "psk_gb_fit: null buffer");
+    if (!X || !node_count || !nodes || !value || !raw_out || (counts && !threshold)) return psk_fail(ctx, PSK_EINVAL, "%s: null buffer", who);
+    if (n < 1 || p < 1) return psk_fail(ctx, PSK_EINVAL, "%s: bad problem shape n=%d p=%d", who, n, p);
+    if (const int rc = gb_check_model_shape(ctx, who, n_estimators, max_depth)) return rc;
+    const int cap = (2 << max_depth) - 1;
+    for (int t = 0; t < n_estimators; t++) {
+        const int count = node_count[t];
+        if (count < 1 || count > cap)
+            return psk_fail(ctx, PSK_EINVAL, "%s: stage %d has %d nodes, a tree of depth %d has 1..%d", who, t, count, max_depth, cap);
+        for (int k = 0; k < count; k++) {
+            const int32_t *nd = nodes + ((size_t)t * cap + k) * GB_NODE_FIELDS;
+            if (nd[0] < 0) continue;
+            if (nd[0] >= p || nd[1] <= k || nd[1] >= count || nd[2] <= k || nd[2] >= count)
+                return psk_fail(ctx, PSK_EINVAL, "%s: node %d of stage %d is not a split of a pre-order tree on %d columns", who, k, t, p);
+            if (counts && !std::isfinite(threshold[(size_t)t * cap + k]))
+                return psk_fail(ctx, PSK_EINVAL, "%s: node %d of stage %d splits at a threshold that is not finite", who, k, t);
+        }
+    }
+    return PSK_OK;
+}
+
+// psk_gb_fit (COUNTS false: threshold_out unused) and psk_gb_fit_counts; `who` names the entry point in messages
+template <bool COUNTS>
+int gb_fit_call(psk_ctx *ctx, const char *who, const float *X, const double *y, int n, int p, const int32_t *fold, const int32_t *fit_fold,
+                int n_fits, int loss, int n_estimators, double learning_rate, int max_depth, const double *init_raw,
+                int32_t *node_count_out, int32_t *nodes_out, double *value_out, double *impurity_out, double *threshold_out,
+                double *raw_out, double *staged_out)
+{
+    if (!ctx) return PSK_EINVAL;
+    if (!X || !y || !fold || !fit_fold || !init_raw || !node_count_out || !nodes_out || !value_out || !impurity_out || !raw_out ||
+        (COUNTS && !threshold_out))
+        return psk_fail(ctx, PSK_EINVAL, "%s: null buffer", who);
     if (n < 1 || p < 1 || n_fits < 1 || n_fits > 65535)
-        return psk_fail(ctx, PSK_EINVAL, "psk_gb_fit: bad problem shape n=%d p=%d fits=%d", n, p, n_fits);
+        return psk_fail(ctx, PSK_EINVAL, "%s: bad problem shape n=%d p=%d fits=%d", who, n, p, n_fits);
     if (n > GB_MAX_N)
-        return psk_fail(ctx, PSK_ERANGE, "psk_gb_fit keeps a stage's residuals and a node's sample mask in LDS: at most %d samples, got %d",
-                        GB_MAX_N, n);
-    if (const int rc = gb_check_model_shape(ctx, "psk_gb_fit", n_estimators, max_depth)) return rc;
+        return psk_fail(ctx, PSK_ERANGE, "%s keeps a stage's residuals and a node's sample mask in LDS: at most %d samples, got %d",
+                        who, GB_MAX_N, n);
+    if (const int rc = gb_check_model_shape(ctx, who, n_estimators, max_depth)) return rc;
     if (!(learning_rate > 0.0) || !std::isfinite(learning_rate))
-        return psk_fail(ctx, PSK_EINVAL, "psk_gb_fit: learning_rate must be a finite number above 0, got %g", learning_rate);
+        return psk_fail(ctx, PSK_EINVAL, "%s: learning_rate must be a finite number above 0, got %g", who, learning_rate);
     if (loss != 0 && loss != 1)
-        return psk_fail(ctx, PSK_EINVAL, "psk_gb_fit: loss must be 0 (squared error) or 1 (log loss), got %d", loss);
+        return psk_fail(ctx, PSK_EINVAL, "%s: loss must be 0 (squared error) or 1 (log loss), got %d", who, loss);
     for (int i = 0; i < n; i++) {
         if (loss == 1 && y[i] != 0.0 && y[i] != 1.0)
-            return psk_fail(ctx, PSK_EINVAL, "psk_gb_fit: the log loss takes labels 0 and 1, sample %d holds %g", i, y[i]);
-        if (!std::isfinite(y[i])) return psk_fail(ctx, PSK_EINVAL, "psk_gb_fit: sample %d has no finite target", i);
+            return psk_fail(ctx, PSK_EINVAL, "%s: the log loss takes labels 0 and 1, sample %d holds %g", who, i, y[i]);
+        if (!std::isfinite(y[i])) return psk_fail(ctx, PSK_EINVAL, "%s: sample %d has no finite target", who, i);
     }
     for (int f = 0; f < n_fits; f++) {
-        if (!std::isfinite(init_raw[f])) return psk_fail(ctx, PSK_EINVAL, "psk_gb_fit: fit %d has no finite init_raw", f);
+        if (!std::isfinite(init_raw[f])) return psk_fail(ctx, PSK_EINVAL, "%s: fit %d has no finite init_raw", who, f);
         int in_bag = 0;
         bool has0 = false, has1 = false;
         for (int i = 0; i < n; i++)
@@ -295,9 +369,9 @@ extern "C" int psk_gb_fit(psk_ctx *ctx, const float *X, const double *y, int n, 
                 in_bag++;
                 (y[i] != 0.0 ? has1 : has0) = true;
             }
-        if (!in_bag) return psk_fail(ctx, PSK_EINVAL, "psk_gb_fit: fit %d has no in-bag sample", f);
+        if (!in_bag) return psk_fail(ctx, PSK_EINVAL, "%s: fit %d has no in-bag sample", who, f);
         if (loss == 1 && !(has0 && has1))
-            return psk_fail(ctx, PSK_EINVAL, "psk_gb_fit: the in-bag samples of fit %d are of one class", f);
+            return psk_fail(ctx, PSK_EINVAL, "%s: the in-bag samples of fit %d are of one class", who, f);
     }
 
     PSK_HIP(ctx, hipSetDevice(ctx->device));
@@ -305,9 +379,16 @@ extern "C" int psk_gb_fit(psk_ctx *ctx, const float *X, const double *y, int n, 
     const size_t trees = (size_t)n_fits * n_estimators, slots = trees * cap;
     FitArr<uint64_t> bits, ymask;
     FitArr<int32_t> d_fold, d_fit_fold, count, d_nodes;
-    FitArr<double> d_y, d_init, d_val, d_imp, d_raw, d_staged;
+    FitArr<double> d_y, d_init, d_val, d_imp, d_raw, d_staged, d_thr;
     const std::vector<int32_t> no_labels((size_t)n, 0);   // (the packing kernel takes 0/1 labels; nothing reads their mask here)
-    if (const int rc = tree_pack_design(ctx, "psk_gb_fit", X, no_labels.data(), n, p, bits, ymask)) return rc;
+    TreePlanes pl;
+    TreePlaneView<COUNTS> pv;
+    if constexpr (COUNTS) {
+        if (const int rc = tree_pack_counts(ctx, who, X, no_labels.data(), n, p, pl, ymask)) return rc;
+        pv = TreePlaneView<true>{pl.x, pl.col_first, pl.plane_col, pl.col_order, pl.plane_val, p};
+    } else {
+        if (const int rc = tree_pack_design(ctx, who, X, no_labels.data(), n, p, bits, ymask)) return rc;
+    }
     PSK_HIP(ctx, d_y.upload(y, n, ctx->stream));
     PSK_HIP(ctx, d_fold.upload(fold, n, ctx->stream));
     PSK_HIP(ctx, d_fit_fold.upload(fit_fold, n_fits, ctx->stream));
@@ -318,17 +399,24 @@ extern "C" int psk_gb_fit(psk_ctx *ctx, const float *X, const double *y, int n, 
     PSK_HIP(ctx, d_imp.alloc(slots));
     PSK_HIP(ctx, d_raw.alloc((size_t)n_fits * n));
     PSK_HIP(ctx, d_staged.alloc(staged_out ? trees * n : 0));
+    PSK_HIP(ctx, d_thr.alloc(COUNTS ? slots : 0));
     // (slots behind a tree's node_count read as zeros)
     PSK_HIP(ctx, d_nodes.zero(ctx->stream));
     PSK_HIP(ctx, d_val.zero(ctx->stream));
     PSK_HIP(ctx, d_imp.zero(ctx->stream));
+    if (COUNTS) PSK_HIP(ctx, d_thr.zero(ctx->stream));
     double *staged = staged_out ? (double *)d_staged : nullptr;
+    // (the count kernel scans the P planes where the 0/1 kernel scans the p columns)
+    const uint64_t *d_bits = COUNTS ? (const uint64_t *)pl.bits : (const uint64_t *)bits;
+    const int cols = COUNTS ? pl.P : p;
     if (loss == 0)
-        gb_fit_kernel<0><<<n_fits, GB_THREADS, 0, ctx->stream>>>(bits, d_y, d_fold, n, p, W, d_fit_fold, d_init, n_estimators, learning_rate,
-                                                                 max_depth, cap, count, d_nodes, d_val, d_imp, d_raw, staged);
+        gb_fit_kernel<0, COUNTS><<<n_fits, GB_THREADS, 0, ctx->stream>>>(d_bits, d_y, d_fold, n, cols, W, d_fit_fold, d_init, n_estimators,
+                                                                         learning_rate, max_depth, cap, count, d_nodes, d_val, d_imp, d_raw,
+                                                                         staged, pv, d_thr);
     else
-        gb_fit_kernel<1><<<n_fits, GB_THREADS, 0, ctx->stream>>>(bits, d_y, d_fold, n, p, W, d_fit_fold, d_init, n_estimators, learning_rate,
-                                                                 max_depth, cap, count, d_nodes, d_val, d_imp, d_raw, staged);
+        gb_fit_kernel<1, COUNTS><<<n_fits, GB_THREADS, 0, ctx->stream>>>(d_bits, d_y, d_fold, n, cols, W, d_fit_fold, d_init, n_estimators,
+                                                                         learning_rate, max_depth, cap, count, d_nodes, d_val, d_imp, d_raw,
+                                                                         staged, pv, d_thr);
     PSK_HIP(ctx, hipGetLastError());
     PSK_HIP(ctx, count.download(node_count_out, trees, ctx->stream));
     PSK_HIP(ctx, d_nodes.download(nodes_out, slots * GB_NODE_FIELDS, ctx->stream));
@@ -336,30 +424,40 @@ extern "C" int psk_gb_fit(psk_ctx *ctx, const float *X, const double *y, int n, 
     PSK_HIP(ctx, d_imp.download(impurity_out, slots, ctx->stream));
     PSK_HIP(ctx, d_raw.download(raw_out, (size_t)n_fits * n, ctx->stream));
     if (staged_out) PSK_HIP(ctx, d_staged.download(staged_out, trees * n, ctx->stream));
+    if (COUNTS) PSK_HIP(ctx, d_thr.download(threshold_out, slots, ctx->stream));
     PSK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (COUNTS)   // a slot behind a tree's node_count holds what a leaf holds
+        for (size_t t = 0; t < trees; t++)
+            for (int k = node_count_out[t]; k < cap; k++) threshold_out[t * cap + k] = -2.0;
     return PSK_OK;
+}
+
+}  // namespace
+
+extern "C" int psk_gb_fit(psk_ctx *ctx, const float *X, const double *y, int n, int p, const int32_t *fold, const int32_t *fit_fold,
+                          int n_fits, int loss, int n_estimators, double learning_rate, int max_depth, const double *init_raw,
+                          int32_t *node_count_out, int32_t *nodes_out, double *value_out, double *impurity_out, double *raw_out,
+                          double *staged_out)
+{
+    return gb_fit_call<false>(ctx, "psk_gb_fit", X, y, n, p, fold, fit_fold, n_fits, loss, n_estimators, learning_rate, max_depth, init_raw,
+                              node_count_out, nodes_out, value_out, impurity_out, nullptr, raw_out, staged_out);
+}
+
+extern "C" int psk_gb_fit_counts(psk_ctx *ctx, const float *X, const double *y, int n, int p, const int32_t *fold,
+                                 const int32_t *fit_fold, int n_fits, int loss, int n_estimators, double learning_rate, int max_depth,
+                                 const double *init_raw, int32_t *node_count_out, int32_t *nodes_out, double *value_out,
+                                 double *impurity_out, double *threshold_out, double *raw_out, double *staged_out)
+{
+    return gb_fit_call<true>(ctx, "psk_gb_fit_counts", X, y, n, p, fold, fit_fold, n_fits, loss, n_estimators, learning_rate, max_depth,
+                             init_raw, node_count_out, nodes_out, value_out, impurity_out, threshold_out, raw_out, staged_out);
 }
 
 extern "C" int psk_gb_decision(psk_ctx *ctx, const float *X, int n, int p, int n_estimators, int max_depth, const int32_t *node_count,
                                const int32_t *nodes, const double *value, double init_raw, double learning_rate, double *raw_out)
 {
-    if (!ctx) return PSK_EINVAL;
-    if (!X || !node_count || !nodes || !value || !raw_out) return psk_fail(ctx, PSK_EINVAL, "psk_gb_decision: null buffer");
-    if (n < 1 || p < 1) return psk_fail(ctx, PSK_EINVAL, "psk_gb_decision: bad problem shape n=%d p=%d", n, p);
-    if (const int rc = gb_check_model_shape(ctx, "psk_gb_decision", n_estimators, max_depth)) return rc;
+    if (const int rc = gb_check_model(ctx, "psk_gb_decision", X, n, p, n_estimators, max_depth, node_count, nodes, value, nullptr, false, raw_out))
+        return rc;
     const int cap = (2 << max_depth) - 1;
-    // the walk of the kernel trusts these: a split's column exists, its children lie behind it (pre-order) and inside the tree
-    for (int t = 0; t < n_estimators; t++) {
-        const int count = node_count[t];
-        if (count < 1 || count > cap)
-            return psk_fail(ctx, PSK_EINVAL, "psk_gb_decision: stage %d has %d nodes, a tree of depth %d has 1..%d", t, count, max_depth, cap);
-        for (int k = 0; k < count; k++) {
-            const int32_t *nd = nodes + ((size_t)t * cap + k) * GB_NODE_FIELDS;
-            if (nd[0] < 0) continue;
-            if (nd[0] >= p || nd[1] <= k || nd[1] >= count || nd[2] <= k || nd[2] >= count)
-                return psk_fail(ctx, PSK_EINVAL, "psk_gb_decision: node %d of stage %d is not a split of a pre-order tree on %d columns", k, t, p);
-        }
-    }
 
     PSK_HIP(ctx, hipSetDevice(ctx->device));
     const size_t slots = (size_t)n_estimators * cap;
@@ -372,6 +470,40 @@ extern "C" int psk_gb_decision(psk_ctx *ctx, const float *X, int n, int p, int n
     PSK_HIP(ctx, d_val.upload(value, slots, ctx->stream));
     PSK_HIP(ctx, d_out.alloc(n));
     gb_decision_kernel<<<div_up(n, 256), 256, 0, ctx->stream>>>(bits, n, p, n_estimators, cap, d_nodes, d_val, init_raw, learning_rate, d_out);
+    PSK_HIP(ctx, hipGetLastError());
+    PSK_HIP(ctx, d_out.download(raw_out, n, ctx->stream));
+    PSK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return PSK_OK;
+}
+
+extern "C" int psk_gb_decision_counts(psk_ctx *ctx, const float *X, int n, int p, int n_estimators, int max_depth, const int32_t *node_count,
+                                      const int32_t *nodes, const double *value, const double *threshold, double init_raw,
+                                      double learning_rate, double *raw_out)
+{
+    const char *who = "psk_gb_decision_counts";
+    if (const int rc = gb_check_model(ctx, who, X, n, p, n_estimators, max_depth, node_count, nodes, value, threshold, true, raw_out)) return rc;
+    const int cap = (2 << max_depth) - 1;
+    // (the words of tree_pack_counts: the rows of a count design, whichever call takes them)
+    for (int i = 0; i < n; i++)
+        for (int j = 0; j < p; j++) {
+            const float v = X[(size_t)i * p + j];
+            if (!(v >= 0.0f && v <= TREE_COUNT_MAX && v == floorf(v)))
+                return psk_fail(ctx, PSK_EINVAL, "%s takes a count design (integers in 0 .. 2^24): sample %d, column %d holds %g", who, i, j,
+                                (double)v);
+        }
+
+    PSK_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t slots = (size_t)n_estimators * cap;
+    FitArr<float> x;
+    FitArr<int32_t> d_nodes;
+    FitArr<double> d_val, d_thr, d_out;
+    PSK_HIP(ctx, x.upload(X, (size_t)n * p, ctx->stream));
+    PSK_HIP(ctx, d_nodes.upload(nodes, slots * GB_NODE_FIELDS, ctx->stream));
+    PSK_HIP(ctx, d_val.upload(value, slots, ctx->stream));
+    PSK_HIP(ctx, d_thr.upload(threshold, slots, ctx->stream));
+    PSK_HIP(ctx, d_out.alloc(n));
+    gb_decision_counts_kernel<<<div_up(n, 256), 256, 0, ctx->stream>>>(x, n, p, n_estimators, cap, d_nodes, d_val, d_thr, init_raw,
+                                                                       learning_rate, d_out);
     PSK_HIP(ctx, hipGetLastError());
     PSK_HIP(ctx, d_out.download(raw_out, n, ctx->stream));
     PSK_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -692,7 +692,17 @@ class PskContext:
         nodes[n_estimators][cap][4] (feature, -2 at a leaf; left; right, -1 at a leaf; in-bag n_node_samples), value and
         impurity[n_estimators][cap], cap = 2^(max_depth + 1) - 1, raw[n] (every sample's raw prediction after the last stage)
         and staged[n_estimators][n] (after each stage; None unless asked for)."""
-        X = np.ascontiguousarray(X, dtype=np.float32)
+        return self._gb_fit(False, np.ascontiguousarray(X, dtype=np.float32), y, fold, fit_fold, loss, n_estimators, learning_rate,
+                            max_depth, init_raw, staged)
+
+    def gb_fit_counts(self, X, y, fold, fit_fold, loss, n_estimators, learning_rate, max_depth, init_raw, staged=True):
+        """gb_fit on a count design (psk_gb_fit_counts): integers in 0 .. 2^24, ValueError otherwise.  The same dictionaries,
+        nodes[..][0] the design column of a split, plus threshold[n_estimators][cap]: scikit-learn's midpoint between the two
+        values around the split among the node's in-bag samples, -2 at a leaf and behind node_count; x <= threshold goes left."""
+        return self._gb_fit(True, self._count_design(X, "gb_fit_counts"), y, fold, fit_fold, loss, n_estimators, learning_rate, max_depth,
+                            init_raw, staged)
+
+    def _gb_fit(self, counts, X, y, fold, fit_fold, loss, n_estimators, learning_rate, max_depth, init_raw, staged):
         n, p = X.shape
         y = np.ascontiguousarray(y, dtype=np.float64)
         fold = np.ascontiguousarray(fold, dtype=np.int32)
@@ -709,16 +719,32 @@ class PskContext:
         value, imp = np.zeros((nf, rows, cap)), np.zeros((nf, rows, cap))
         raw = np.zeros((nf, n))
         stg = np.zeros((nf, rows, n)) if staged else None
-        self._check(self._lib.psk_gb_fit(self._h, _ptr(X), _ptr(y), n, p, _ptr(fold), _ptr(fit_fold), nf, int(self.GB_LOSSES.get(loss, loss)),
-                                         ne, float(learning_rate), depth, _ptr(init), _ptr(count), _ptr(nodes), _ptr(value), _ptr(imp),
-                                         _ptr(raw), _ptr(stg)), "psk_gb_fit")
-        return [dict(node_count=count[j], nodes=nodes[j], value=value[j], impurity=imp[j], raw=raw[j], staged=stg[j] if staged else None)
+        head = (self._h, _ptr(X), _ptr(y), n, p, _ptr(fold), _ptr(fit_fold), nf, int(self.GB_LOSSES.get(loss, loss)), ne, float(learning_rate),
+                depth, _ptr(init), _ptr(count), _ptr(nodes), _ptr(value), _ptr(imp))
+        if not counts:
+            self._check(self._lib.psk_gb_fit(*head, _ptr(raw), _ptr(stg)), "psk_gb_fit")
+        else:
+            thr = np.zeros((nf, rows, cap))
+            self._check(self._lib.psk_gb_fit_counts(*head, _ptr(thr), _ptr(raw), _ptr(stg)), "psk_gb_fit_counts")
+        fits = [dict(node_count=count[j], nodes=nodes[j], value=value[j], impurity=imp[j], raw=raw[j], staged=stg[j] if staged else None)
                 for j in range(nf)]
+        if counts:
+            for j in range(nf):
+                fits[j]["threshold"] = thr[j]
+        return fits
 
     def gb_decision(self, X, node_count, nodes, value, init_raw, learning_rate, max_depth):
         """The raw predictions of the rows of a 0/1 design under one gradient-boosting model in gb_fit's layout
         (psk_gb_decision): init_raw, then + learning_rate * value[leaf] stage after stage.  Returns raw[n]."""
-        X = np.ascontiguousarray(X, dtype=np.float32)
+        return self._gb_decision(np.ascontiguousarray(X, dtype=np.float32), node_count, nodes, value, None, init_raw, learning_rate, max_depth)
+
+    def gb_decision_counts(self, X, node_count, nodes, value, threshold, init_raw, learning_rate, max_depth):
+        """gb_decision for a model of gb_fit_counts on the rows of a count design (psk_gb_decision_counts): x <= threshold goes
+        left.  threshold[n_estimators][cap] beside nodes and value.  Returns raw[n]."""
+        return self._gb_decision(self._count_design(X, "gb_decision_counts"), node_count, nodes, value, threshold, init_raw, learning_rate,
+                                 max_depth)
+
+    def _gb_decision(self, X, node_count, nodes, value, threshold, init_raw, learning_rate, max_depth):
         n, p = X.shape
         depth = int(max_depth)
         cap = (2 << min(max(depth, 1), 10)) - 1
@@ -729,8 +755,15 @@ class PskContext:
         if nodes.shape != (ne, cap, 4) or value.shape != (ne, cap):
             raise ValueError("nodes must be [n_estimators][%d][4] and value [n_estimators][%d] for max_depth %d" % (cap, cap, depth))
         raw = np.zeros(n)
-        self._check(self._lib.psk_gb_decision(self._h, _ptr(X), n, p, ne, depth, _ptr(count), _ptr(nodes), _ptr(value), float(init_raw),
-                                              float(learning_rate), _ptr(raw)), "psk_gb_decision")
+        if threshold is None:
+            self._check(self._lib.psk_gb_decision(self._h, _ptr(X), n, p, ne, depth, _ptr(count), _ptr(nodes), _ptr(value), float(init_raw),
+                                                  float(learning_rate), _ptr(raw)), "psk_gb_decision")
+            return raw
+        thr = np.ascontiguousarray(threshold, dtype=np.float64)
+        if thr.shape != (ne, cap):
+            raise ValueError("threshold must be [n_estimators][%d] for max_depth %d" % (cap, depth))
+        self._check(self._lib.psk_gb_decision_counts(self._h, _ptr(X), n, p, ne, depth, _ptr(count), _ptr(nodes), _ptr(value), _ptr(thr),
+                                                     float(init_raw), float(learning_rate), _ptr(raw)), "psk_gb_decision_counts")
         return raw
 
     def pca_fit(self, X, n_comp=None):

@@ -6,7 +6,9 @@ GradientBoostingClassifier() / GradientBoostingRegressor() with their default pa
 gradient boosting, NOT XGBoost's regularised objective.  The engine fits every stage in one launch in a
 stated arithmetic (include/psk.h, f16); the initial raw prediction, the loss per stage (train_score_), the importances and the
 scikit-learn export are taken here on the host.  A raw prediction is init + the stages' learning_rate * value[leaf] added in stage
-order: raw_in_order() below and psk_gb_decision give the same bits, so a prediction does not depend on where it was computed."""
+order: raw_in_order() below and psk_gb_decision give the same bits, so a prediction does not depend on where it was computed.
+With counts=True the design holds k-mer counts (`--real_counts`): psk_gb_fit_counts / psk_gb_decision_counts, and every split
+carries scikit-learn's threshold, x <= threshold going left."""
 import numpy as np
 
 from .model_search import _Estimator
@@ -16,9 +18,10 @@ LOSSES = ("squared_error", "log_loss")
 MAX_DEPTH, MAX_STAGES = 10, 1000
 
 
-def raw_in_order(X, node_count, nodes, value, init_raw, learning_rate, max_depth):
-    """psk_gb_decision in NumPy: X[n][p] (non-zero = present), the model in the engine's layout -> raw[n]."""
-    X = np.asarray(X) != 0
+def raw_in_order(X, node_count, nodes, value, init_raw, learning_rate, max_depth, threshold=None):
+    """psk_gb_decision in NumPy: X[n][p] (non-zero = present), the model in the engine's layout -> raw[n].  With threshold
+    [n_estimators][cap] psk_gb_decision_counts: X holds counts and x <= threshold goes left."""
+    X = np.asarray(X) != 0 if threshold is None else np.asarray(X, dtype=np.float64)
     n = X.shape[0]
     rows = np.arange(n)
     F = np.full(n, float(init_raw))
@@ -28,6 +31,8 @@ def raw_in_order(X, node_count, nodes, value, init_raw, learning_rate, max_depth
             f = nd[node, 0]
             inner = f >= 0
             bit = X[rows, np.where(inner, f, 0)]
+            if threshold is not None:
+                bit = ~(bit <= threshold[t][node])
             node = np.where(inner, np.where(bit, nd[node, 2], nd[node, 1]), node)
         F = F + float(learning_rate) * value[t, node]
     return F
@@ -63,9 +68,11 @@ class GradientBoosting(_Estimator):
     """sklearn.ensemble.GradientBoostingClassifier (loss='log_loss', two classes labelled 0 and 1) or GradientBoostingRegressor
     (loss='squared_error') on a 0/1 design; every other parameter at scikit-learn's default (criterion 'friedman_mse',
     subsample 1.0, min_samples_split 2, min_samples_leaf 1, max_features None, init None).  It is not searched: `modeling` fits
-    it directly.  scikit-learn breaks ties between equally good splits by random_state; here the lowest column index wins."""
+    it directly.  scikit-learn breaks ties between equally good splits by random_state; here the lowest column index wins, then
+    the lowest threshold.  counts: the design holds k-mer counts (psk_gb_fit_counts); a switch of the engine, not a parameter of
+    scikit-learn's: neither the repr nor the exported parameters show it."""
 
-    def __init__(self, loss, n_estimators=100, learning_rate=0.1, max_depth=3):
+    def __init__(self, loss, n_estimators=100, learning_rate=0.1, max_depth=3, counts=False):
         if loss not in LOSSES:
             raise ValueError("GradientBoosting: loss must be 'squared_error' or 'log_loss', got %r" % (loss,))
         if isinstance(n_estimators, bool) or int(n_estimators) != n_estimators or not 1 <= int(n_estimators) <= MAX_STAGES:
@@ -75,6 +82,7 @@ class GradientBoosting(_Estimator):
         if not (np.isfinite(learning_rate) and learning_rate > 0):
             raise ValueError("GradientBoosting: learning_rate must be a finite number above 0, got %r" % (learning_rate,))
         self.loss, self.n_estimators, self.learning_rate, self.max_depth = loss, int(n_estimators), float(learning_rate), int(max_depth)
+        self.counts, self.threshold_ = bool(counts), None
         self.classes_ = np.array([0, 1]) if self._is_classifier else None
 
     @property
@@ -94,7 +102,7 @@ class GradientBoosting(_Estimator):
         return "%s(%s)" % (self._sk_name, ", ".join("%s=%r" % kv for kv in changed))
 
     def _clone(self, **params):
-        kw = dict(self._sklearn_params(), loss=self.loss)
+        kw = dict(self._sklearn_params(), loss=self.loss, counts=self.counts)
         kw.update(params)
         return type(self)(**kw)
 
@@ -106,8 +114,10 @@ class GradientBoosting(_Estimator):
         if self._is_classifier and not set(y.tolist()) <= {0, 1}:
             raise ValueError("GradientBoosting: the two classes must be labelled 0 and 1")
         init = init_raw_prediction(y, self.loss)
-        fit = engine_ctx.gb_fit(Xb.astype(np.float32), y.astype(np.float64), np.zeros(len(y), dtype=np.int32), [-1], self.loss,
-                                self.n_estimators, self.learning_rate, self.max_depth, [init], staged=True)[0]
+        # (the count call takes the float64 values: it checks their range before the rounding to float32 would hide 2^24 + 1)
+        engine_fit, Xe = (engine_ctx.gb_fit_counts, Xb.astype(np.float64)) if self.counts else (engine_ctx.gb_fit, Xb.astype(np.float32))
+        fit = engine_fit(Xe, y.astype(np.float64), np.zeros(len(y), dtype=np.int32), [-1], self.loss,
+                         self.n_estimators, self.learning_rate, self.max_depth, [init], staged=True)[0]
         return self._set_fit(fit, Xb.shape[1], init, y)
 
     def _set_fit(self, fit, n_features, init, y):
@@ -118,6 +128,7 @@ class GradientBoosting(_Estimator):
         self.nodes_ = np.array(fit["nodes"], dtype=np.int32)
         self.value_ = np.array(fit["value"], dtype=np.float64)
         self.impurity_ = np.array(fit["impurity"], dtype=np.float64)
+        self.threshold_ = np.array(fit["threshold"], dtype=np.float64) if self.counts else None
         self.n_estimators_ = len(self.node_count_)
         y = np.asarray(y, dtype=np.float64)
         if self._is_classifier:
@@ -139,7 +150,7 @@ class GradientBoosting(_Estimator):
             k = int(self.node_count_[t])
             nd = self.nodes_[t, :k]
             tree = Tree(self.n_features_in_, nd[:, 0], nd[:, 1], nd[:, 2], nd[:, 3], np.zeros((k, 2)), self.impurity_[t, :k],
-                        _depth(nd[:, 1], nd[:, 2]))
+                        _depth(nd[:, 1], nd[:, 2]), threshold=self.threshold_[t, :k] if self.counts else None)
             tree.value = self.value_[t, :k].reshape(-1, 1, 1).copy()
             trees.append(tree)
         return trees
@@ -162,10 +173,16 @@ class GradientBoosting(_Estimator):
         return self.node_count_, self.nodes_, self.value_, self.init_raw_, self.learning_rate, self.max_depth
 
     def raw(self, X, engine_ctx=None):
-        """raw[n]; on the device (psk_gb_decision) when given an engine context, else in NumPy in the same order: the same bits."""
+        """raw[n]; on the device (psk_gb_decision, psk_gb_decision_counts for a counts model) when given an engine context, else
+        in NumPy in the same order: the same bits."""
         X = np.asarray(X)
         if X.ndim != 2 or X.shape[1] != self.n_features_in_:
             raise ValueError("Expected input with %d features, got %d instead" % (self.n_features_in_, X.shape[-1]))
+        if self.counts:
+            count, nodes, value, init, rate, depth = self._model()
+            if engine_ctx is not None:
+                return engine_ctx.gb_decision_counts(X.astype(np.float64), count, nodes, value, self.threshold_, init, rate, depth)
+            return raw_in_order(X, count, nodes, value, init, rate, depth, self.threshold_)
         if engine_ctx is not None:
             return engine_ctx.gb_decision((X != 0).astype(np.float32), *self._model())
         return raw_in_order(X, *self._model())
@@ -173,7 +190,9 @@ class GradientBoosting(_Estimator):
     def staged_raw(self, X):
         """[n_estimators][n]: the raw predictions after each stage (NumPy, the order of raw())."""
         count, nodes, value, init, rate, depth = self._model()
-        return np.array([raw_in_order(X, count[:t + 1], nodes[:t + 1], value[:t + 1], init, rate, depth) for t in range(self.n_estimators_)])
+        thr = self.threshold_
+        return np.array([raw_in_order(X, count[:t + 1], nodes[:t + 1], value[:t + 1], init, rate, depth, None if thr is None else thr[:t + 1])
+                         for t in range(self.n_estimators_)])
 
     def predict_proba(self, X, engine_ctx=None):
         if not self._is_classifier:
@@ -245,9 +264,10 @@ class GradientBoosting(_Estimator):
 
 def from_sklearn(est):
     """GradientBoosting from a fitted scikit-learn GradientBoostingClassifier / GradientBoostingRegressor of the kind this
-    package writes (two classes 0 / 1 or squared error, init None, one tree per stage, every split at threshold 0.5, depth and
-    stages within the engine's limits): what `prediction` turns a loaded model file into, so that its raw values come from
-    psk_gb_decision.  None for anything else: scikit-learn itself then predicts."""
+    package writes (two classes 0 / 1 or squared error, init None, one tree per stage, depth and stages within the engine's
+    limits): what `prediction` turns a loaded model file into, so that its raw values come from psk_gb_decision -- or, when a
+    split's threshold is not 0.5 (a model of a count design), a counts=True model whose raw values come from
+    psk_gb_decision_counts.  None for anything else: scikit-learn itself then predicts."""
     try:
         name = type(est).__name__
         if name not in ("GradientBoostingClassifier", "GradientBoostingRegressor"):
@@ -261,13 +281,16 @@ def from_sklearn(est):
         cap, p = (2 << m.max_depth) - 1, int(est.n_features_in_)
         ne = len(est.estimators_)
         count, nodes = np.zeros(ne, dtype=np.int32), np.zeros((ne, cap, 4), dtype=np.int32)
-        value, imp = np.zeros((ne, cap)), np.zeros((ne, cap))
+        value, imp, thr = np.zeros((ne, cap)), np.zeros((ne, cap)), np.full((ne, cap), -2.0)
+        counts = False
         for t in range(ne):
             tr = est.estimators_[t, 0].tree_
             k = int(tr.node_count)
             split = tr.children_left != -1
-            if k > cap or np.any(tr.threshold[split] != 0.5) or np.any(tr.children_left[split] != np.nonzero(split)[0] + 1):
+            if k > cap or not np.all(np.isfinite(tr.threshold[split])) or np.any(tr.children_left[split] != np.nonzero(split)[0] + 1):
                 return None
+            thr[t, :k] = np.where(split, tr.threshold, -2.0)
+            counts = counts or bool(np.any(tr.threshold[split] != 0.5))
             count[t] = k
             nodes[t, :k, 0] = np.where(split, tr.feature, -2)
             nodes[t, :k, 1], nodes[t, :k, 2], nodes[t, :k, 3] = tr.children_left, tr.children_right, tr.n_node_samples
@@ -280,6 +303,8 @@ def from_sklearn(est):
             init = float(np.asarray(est.init_.constant_).reshape(-1)[0])
         m.n_features_in_, m.init_raw_, m.node_count_, m.nodes_, m.value_, m.impurity_ = p, init, count, nodes, value, imp
         m.n_estimators_ = ne
+        if counts:
+            m.counts, m.threshold_ = True, thr
         m.train_score_ = np.array(est.train_score_, dtype=np.float64)
         return m
     except (AttributeError, IndexError, TypeError, ValueError):

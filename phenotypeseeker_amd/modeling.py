@@ -347,7 +347,8 @@ class Input:
         `-bc NB` pass with their knobs (PSK_SVM, PSK_DT, PSK_RF, PSK_NB; `--kernel rbf` with PSK_SVM_RBF as well), `--pca` with
         PSK_PCA for a binary phenotype under `-bc log` and `-bc SVM`, and with PSK_TREE_PCA as well under `-bc DT` and `-bc RF`,
         `--penalty L1+L2` (or `elasticnet`) with `--l1_ratio` in [0, 1] with PSK_ENET for a continuous phenotype, `-bc XGBC` with a
-        binary and `-reg XGBR` with a continuous phenotype with PSK_GB (scikit-learn's gradient boosting, model_gb.py)."""
+        binary and `-reg XGBR` with a continuous phenotype with PSK_GB (scikit-learn's gradient boosting, model_gb.py), and
+        `--real_counts` with either of the two with PSK_GB_COUNTS as well."""
         if alphas is None:
             phenotypes.alphas = np.logspace(math.log10(alpha_min), math.log10(alpha_max), num=n_alphas)
         else:
@@ -508,8 +509,9 @@ class Input:
 
     @staticmethod
     def _gb_design_only(flag, kind, pca, real_counts):
-        """The boosting kernel works on the bit-packed presence matrix; threshold planes for counts are not built for it."""
-        for given, name in ((pca, "--pca"), (real_counts, "--real_counts")):
+        """The boosting kernel works on the bit-packed presence matrix; k-mer counts go through the count entry point (threshold
+        planes, psk_gb_fit_counts) only with PSK_GB_COUNTS (docs/KNOBS.md); principal components are neither."""
+        for given, name in ((pca, "--pca"), (real_counts and not _lib.env_flag("PSK_GB_COUNTS"), "--real_counts")):
             if given:
                 raise SystemExit("The gradient boosting %s on the GPU engine takes the 0/1 presence matrix only: "
                                  "%s is not supported with %s." % (kind, name, flag))
@@ -807,7 +809,7 @@ class phenotypes:
 
     def _new_estimator(self):
         if self.gradient_boosting:
-            return GradientBoosting("log_loss" if self.pred_scale == "binary" else "squared_error"), None, None
+            return GradientBoosting("log_loss" if self.pred_scale == "binary" else "squared_error", counts=bool(self.real_counts)), None, None
         if self.pred_scale == "binary":
             grid = [1.0 / a for a in self.alphas]
             if self.binary_classifier == "DT":
