@@ -341,6 +341,22 @@ int psk_lasso_fit(psk_ctx *ctx, const float *X, const double *y, int n, int p, c
                   const double *fit_param, const int32_t *fit_fold, int n_fits, double tol, int max_iter,
                   double *coef_out, double *icpt_out, int32_t *iters_out);
 
+/* ---- f17: L1 logistic regression with a free intercept (`--penalty L1 --logreg_solver saga`) --------
+ * Replaces GridSearchCV over LogisticRegression(penalty='l1', solver='saga') (set_model, modeling.py:1011-1014,
+ * get_logreg_solver :245-264).  Same batching, argument meaning, routes, placements and form knobs as
+ * psk_logreg_l1_fit; the objective is the one saga minimises,
+ *   ||w||_1 + C sum log(1+exp(-y(w.x+b))),   the intercept b unpenalised,
+ * and the contract is its optimum reached to liblinear's stopping rule at the caller's tolerance (saga's own
+ * stochastic iterate is no target: it stops at its iteration limit above the optimum, or after a few epochs):
+ * ||violation||_1 <= tol min(#pos, #neg) / l x ||violation at w = 0, b = 0||_1, the intercept's violation being
+ * |d/db|.  Same scheme as psk_logreg_l1_fit (outer Newton steps, inner coordinate descent with shrinking, one
+ * Armijo line search); the intercept is never shrunk, stepped by -G / H without a soft threshold and left out of
+ * the line search's ||w||_1.  iters_out = Newton steps.  A fit whose training samples are of one class has no
+ * minimiser (b runs off to infinity) and is refused (PSK_EINVAL, naming the fit). */
+int psk_logreg_l1_free_fit(psk_ctx *ctx, const float *X, const int32_t *y01, int n, int p, const int32_t *fold,
+                           const double *fit_param, const int32_t *fit_fold, int n_fits, double tol, int max_iter,
+                           double *coef_out, double *icpt_out, int32_t *iters_out);
+
 /* ---- f4: the `--penalty L2` estimators --------------------------------------------------------
  * Replaces GridSearchCV over Ridge (set_model, modeling.py:1001-1002) and over
  * LogisticRegression(penalty='l2', solver=<-ls>) (modeling.py:1015-1019, get_logreg_solver :256-264).

@@ -49,7 +49,7 @@ _MODELING = {
                                         help='The regressor: "lin" (linear regression; default) ...')),
         (("--kernel",), dict(metavar="", type=str, default="linear", help="SVM kernel.")),
         (("--logreg_solver", "-ls"), dict(metavar="", type=str, default=None,
-                                           help="Logistic regression solver ('liblinear' for L1).")),
+                                           help="Logistic regression solver ('liblinear' for L1; 'saga' for L1 with PSK_L1_SAGA=1).")),
         (("--l1_ratio",), dict(metavar="", type=float, default=0.5, help="The elastic net mixing parameter.")),
         (("-tow", "--train_on_whole"), dict(action="store_true",
                                              help="Train the output model on the whole dataset given.")),

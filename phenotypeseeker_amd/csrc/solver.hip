@@ -7,6 +7,7 @@
 //                     (intercept = penalised constant-1 feature) by the improved GLMNET scheme liblinear
 //                     itself uses: outer Newton steps, inner coordinate descent with shrinking on the
 //                     quadratic model, one line search per outer step; a bit-packed form for 0/1 designs.
+//                     With PI = false the same without |b|, the free intercept of psk_logreg_l1_free_fit (saga's objective).
 //   lasso_kernel      (1/2n)||y - Xw - b||^2 + alpha ||w||_1, unpenalised intercept, cyclic
 //                     coordinate descent on the centred problem.  With EN = true the elastic net of psk_enet_fit (f14):
 //                     + 1/2 alpha (1 - l1_ratio) ||w||^2, the L1 weight alpha l1_ratio.
@@ -33,7 +34,12 @@ namespace {
 // ||violation||_1 <= tol * min(#pos, #neg)/l * ||violation at w = 0||_1.
 // Per-fit state: five feature arrays (w, w+d, diag H, grad, sum of C*x over the y=-1 rows) and five sample
 // arrays (exp(w.x), its trial value, tau, D, x.d), in LDS when they fit (up to 160 KiB per workgroup).
+// PI (here and in logreg_newglmnet_bits_kernel): the intercept is penalised -- liblinear's objective, psk_logreg_l1_fit.  With
+// PI = false it is free (psk_logreg_l1_free_fit): its subgradient term is 0 in the violations, in the shrinking tests (which
+// then never pass for it) and in the inner step (-G / H, no soft threshold), and it is left out of the line search's ||w||_1.
+// A template parameter: the penalised instances compile to what they were.
 #define FLD(ptr) (f_lds ? *(ptr) : lane0_load((ptr), lane))
+template <bool PI>
 __global__ __launch_bounds__(SV_THREADS) void logreg_newglmnet_kernel(
     const float *__restrict__ XT, const int8_t *__restrict__ ypm, const int32_t *__restrict__ fold, int n, int p,
     const double *__restrict__ fit_param, const int32_t *__restrict__ fit_fold, double tol, int max_newton,
@@ -95,7 +101,8 @@ __global__ __launch_bounds__(SV_THREADS) void logreg_newglmnet_kernel(
             tmp = psk_wave_sum_f64_dpp(tmp);
             const double grad = -tmp + FLD(&xjneg[j]);
             const double wj = FLD(&w[j]);
-            const double Gp = grad + 1.0, Gn = grad - 1.0;
+            const double pen = (PI || j < p) ? 1.0 : 0.0;   // (PI false: the intercept, coordinate p, is free)
+            const double Gp = grad + pen, Gn = grad - pen;
             double viol = 0.0;
             if (wj == 0.0) {
                 if (Gp < 0) viol = -Gp;
@@ -146,7 +153,8 @@ __global__ __launch_bounds__(SV_THREADS) void logreg_newglmnet_kernel(
                     if (x != 0.0) G += x * D[i] * xTd[i];
                 }
                 G = psk_wave_sum_f64_dpp(G) + FLD(&Gr[j]) + (wp - FLD(&w[j])) * nu;
-                const double Gp = G + 1.0, Gn = G - 1.0;
+                const double pen = (PI || j < p) ? 1.0 : 0.0;
+                const double Gp = G + pen, Gn = G - pen;
                 double viol = 0.0;
                 if (wp == 0.0) {
                     if (Gp < 0) viol = -Gp;
@@ -205,7 +213,7 @@ __global__ __launch_bounds__(SV_THREADS) void logreg_newglmnet_kernel(
         for (int j = 0; j < P1; j++) {
             const double wp = FLD(&wpd[j]);
             delta += FLD(&Gr[j]) * (wp - FLD(&w[j]));
-            w_norm_new += fabs(wp);
+            if (PI || j < p) w_norm_new += fabs(wp);
         }
         delta += (w_norm_new - w_norm);
         double negsum = 0.0;
@@ -261,7 +269,7 @@ __global__ __launch_bounds__(SV_THREADS) void logreg_newglmnet_kernel(
             for (int j = 0; j < P1; j++) {
                 const double v = 0.5 * (FLD(&w[j]) + FLD(&wpd[j]));
                 if (lane == 0) wpd[j] = v;
-                w_norm_new += fabs(v);
+                if (PI || j < p) w_norm_new += fabs(v);
             }
             delta *= 0.5;
             negsum *= 0.5;
@@ -719,14 +727,12 @@ int lasso_float_fit(psk_ctx *ctx, const FitArgs &a, const double *y, double tol,
     return io.download(ctx, a);
 }
 
-}  // namespace
-
-extern "C" int psk_logreg_l1_fit(psk_ctx *ctx, const float *X, const int32_t *y01, int n, int p, const int32_t *fold,
-                                 const double *fit_param, const int32_t *fit_fold, int n_fits, double tol, int max_iter,
-                                 double *coef_out, double *icpt_out, int32_t *iters_out)
+// psk_logreg_l1_fit (pen_icpt: liblinear's penalised intercept) and psk_logreg_l1_free_fit (the free one) after their
+// arguments are checked: the same knobs, routes and placements, the kernels' PI instances apart
+int logreg_l1_route(psk_ctx *ctx, const FitArgs &a, const int32_t *y01, double tol, int max_iter, bool pen_icpt)
 {
-    const FitArgs a = {X, n, p, fold, fit_param, fit_fold, n_fits, coef_out, icpt_out, iters_out};
-    PSK_TRY(check_fit_args(ctx, a, y01));
+    const float *X = a.X;
+    const int n = a.n, p = a.p, n_fits = a.n_fits;
     // form knobs, validated before anything is allocated
     psk_l1_knobs k;
     int knob_cg_max = 16, knob_polish_from = 32;
@@ -776,6 +782,7 @@ extern "C" int psk_logreg_l1_fit(psk_ctx *ctx, const float *X, const int32_t *y0
         L.gg_sl = P.gg_sl; L.gg_q = ggq; L.gg_stride = P.gg_stride;
         L.gg_polish_from = knob_polish_from;   // first polish of a descent after this many sweeps
         L.wmreg = P.wmreg; L.all_lds = P.all_lds; L.lds_bytes = P.lds_bytes; L.stream = ctx->stream;
+        L.pen_icpt = pen_icpt ? 1 : 0;
         // two kernels, compiled apart (solver_l1_bits.h): the Gram matrix in global memory, or the LDS Gram block / array forms
         PSK_HIP(ctx, P.gg_sl ? psk_l1_bits_launch_gg(L) : psk_l1_bits_launch_gram(L));
         return io.download(ctx, a);   // (synchronises: `bits` and `bitsT` outlive their copies)
@@ -791,12 +798,40 @@ extern "C" int psk_logreg_l1_fit(psk_ctx *ctx, const float *X, const int32_t *y0
     const std::vector<float> XT = transpose_f32(X, n, p, true);
     FitArr<float> xt;
     PSK_HIP(ctx, xt.upload(XT, ctx->stream));
+    auto kern = pen_icpt ? logreg_newglmnet_kernel<true> : logreg_newglmnet_kernel<false>;
     if (lds > 64 * 1024)
-        PSK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(logreg_newglmnet_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    logreg_newglmnet_kernel<<<n_fits, SV_THREADS, lds, ctx->stream>>>(xt, y, io.fold, n, p, io.fit_param, io.fit_fold, tol, max_iter, io.coef,
-                                                                      io.icpt, io.iters, work, iwork, f_lds, s_lds);
+        PSK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    kern<<<n_fits, SV_THREADS, lds, ctx->stream>>>(xt, y, io.fold, n, p, io.fit_param, io.fit_fold, tol, max_iter, io.coef, io.icpt, io.iters,
+                                                   work, iwork, f_lds, s_lds);
     return io.download(ctx, a);
+}
+
+}  // namespace
+
+extern "C" int psk_logreg_l1_fit(psk_ctx *ctx, const float *X, const int32_t *y01, int n, int p, const int32_t *fold,
+                                 const double *fit_param, const int32_t *fit_fold, int n_fits, double tol, int max_iter,
+                                 double *coef_out, double *icpt_out, int32_t *iters_out)
+{
+    const FitArgs a = {X, n, p, fold, fit_param, fit_fold, n_fits, coef_out, icpt_out, iters_out};
+    PSK_TRY(check_fit_args(ctx, a, y01));
+    return logreg_l1_route(ctx, a, y01, tol, max_iter, true);
+}
+
+extern "C" int psk_logreg_l1_free_fit(psk_ctx *ctx, const float *X, const int32_t *y01, int n, int p, const int32_t *fold,
+                                      const double *fit_param, const int32_t *fit_fold, int n_fits, double tol, int max_iter,
+                                      double *coef_out, double *icpt_out, int32_t *iters_out)
+{
+    const FitArgs a = {X, n, p, fold, fit_param, fit_fold, n_fits, coef_out, icpt_out, iters_out};
+    PSK_TRY(check_fit_args(ctx, a, y01));
+    // a free intercept runs off to infinity on a training set of one class: there is no minimiser
+    for (int f = 0; f < n_fits; f++) {
+        int c0 = 0, c1 = 0;
+        for (int i = 0; i < n; i++)
+            if (fold[i] != fit_fold[f]) { if (y01[i]) c1++; else c0++; }
+        if (!c0 || !c1)
+            return psk_fail(ctx, PSK_EINVAL, "psk_logreg_l1_free_fit: fit %d trains on one class only (%d of class 0, %d of class 1)", f, c0, c1);
+    }
+    return logreg_l1_route(ctx, a, y01, tol, max_iter, false);
 }
 
 namespace {

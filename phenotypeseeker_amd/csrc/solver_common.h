@@ -108,6 +108,7 @@ struct psk_l1_bits_launch {
     double *coef, *icpt, *work;
     int32_t *iters, *iwork;
     int f_lds, s_lds, c_lds, q_doubles, cg_max, polish_reps, gg_sl, gg_polish_from, wmreg, all_lds;
+    int pen_icpt;              // 1: liblinear's penalised intercept (psk_logreg_l1_fit), 0: the free one (psk_logreg_l1_free_fit)
     float *gg_q;
     size_t gg_stride, lds_bytes;
     hipStream_t stream;

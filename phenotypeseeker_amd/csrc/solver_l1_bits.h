@@ -19,6 +19,16 @@ namespace {
 // inside the loops, only the LDS-resident per-sample arrays.  (The float form pays an L2 round trip per
 // 64 samples, ~7 us per coordinate at n = 2048 on a lone wave; this form ~0.3 us.)
 #define FLD(ptr) (f_lds ? *(ptr) : lane0_load((ptr), lane))
+// The inner tolerance of the Gram-global descent under a free intercept (PI = false), as a share of the array forms'.  The
+// unpenalised intercept trades against the columns along a nearly flat valley; the descent on the approximate Gram matrix, whose
+// books run an interval behind and which ends a few visits late, left the Newton step short along it and the fit stopped inside
+// the rule but further from the optimum than the array forms (130 x 250, C = 1: 1.56e-5 above it against 1.27e-6; intercepts
+// -4.232 against -4.2595).  A visit costs this form little next to the Gram build of every Newton step: at a tenth of the
+// tolerance the same fit ends 4.5e-6 above (intercept -4.2596), and the 143-fit launches take 120 / 24 / 259 ms against
+// 121 / 37 / 249 ms (a quarter: 121 / 46 / 260 ms).
+#ifndef PSK_GG_FREE_INNER
+#define PSK_GG_FREE_INNER 0.1
+#endif
 // repeats of the Gram-global form's accelerator at a call after `sweeps` sweeps of the descent: polish_reps > 0: that many;
 // polish_reps < 0: as many as the descent has needed sweeps so far, at most -polish_reps
 __device__ __forceinline__ int gg_polish_repeats(int polish_reps, int sweeps)
@@ -32,7 +42,10 @@ __device__ __forceinline__ int gg_polish_repeats(int polish_reps, int sweeps)
 // WMREG: 0, or the number of sample words per lane the register form of the descent holds (16, 32 or 64, a quarter of them in each of its four waves; see cd_coop) --
 // a template parameter so that its 2 x WMREG doubles per lane do not weigh on the register allocation of the other forms.
 // FORM: 0 = the LDS Gram block and the array forms, 1 = the Gram matrix in global memory (gg_run; four waves).
-template <bool ALL_LDS, int WMREG, int FORM>
+// PI: the intercept (coordinate p) is penalised, liblinear's objective; false: it is free (see logreg_newglmnet_kernel) -- every
+// site that adds the subgradient's +-1 takes the coordinate's penalty `pen`, 1 or 0, in its place, and the two accelerators keep
+// the free intercept in their smooth problem without a sign term.  The PI = true instances compile to what they were.
+template <bool ALL_LDS, int WMREG, int FORM, bool PI>
 __global__ __launch_bounds__(WMREG > 0 ? SV_COOP_THREADS : SV_THREADS) void logreg_newglmnet_bits_kernel(
     const uint64_t *__restrict__ colbits, const int8_t *__restrict__ ypm, const int32_t *__restrict__ fold, int n, int p,
     int W, const double *__restrict__ fit_param, const int32_t *__restrict__ fit_fold, double tol, int max_newton,
@@ -196,7 +209,8 @@ __global__ __launch_bounds__(WMREG > 0 ? SV_COOP_THREADS : SV_THREADS) void logr
 #pragma unroll
                 for (int v = 1; v < SV_COOP_WAVES; v++) Gs += s_part[slot][v];
                 const double G = Gs + FLD(&Gr[j]) + (wp - FLD(&w[j])) * nu;
-                const double Gp = G + 1.0, Gn = G - 1.0;
+                const double pen = (PI || j < p) ? 1.0 : 0.0;
+                const double Gp = G + pen, Gn = G - pen;
                 double viol = 0.0;
                 if (wp == 0.0) {
                     if (Gp < 0) viol = -Gp;
@@ -318,8 +332,10 @@ __global__ __launch_bounds__(WMREG > 0 ? SV_COOP_THREADS : SV_THREADS) void logr
             const int u = 4 * tid + e;
             const bool valid = u < A;
             wp[e] = valid ? ggP[2 * (size_t)u + 1] : 0.0;
-            inF[e] = valid && wp[e] != 0.0;
-            sg[e] = wp[e] > 0.0 ? 1.0 : -1.0;
+            // (the free intercept is always in F, has no sign term and may cross zero: sg = 0)
+            const bool freee = !PI && valid && ggFeat[valid ? u : 0] == p;
+            inF[e] = valid && (wp[e] != 0.0 || freee);
+            sg[e] = freee ? 0.0 : wp[e] > 0.0 ? 1.0 : -1.0;
             r[e] = inF[e] ? -(ggG[valid ? u : 0] + sg[e]) : 0.0;
             pd[e] = r[e];
             dl[e] = 0.0;
@@ -331,7 +347,7 @@ __global__ __launch_bounds__(WMREG > 0 ? SV_COOP_THREADS : SV_THREADS) void logr
             int cnt = 0;
             for (int base = 0; base < A; base += 64) {
                 const int u = base + lane;
-                const bool f = u < A && ggP[2 * (size_t)(u < A ? u : 0) + 1] != 0.0;
+                const bool f = u < A && (ggP[2 * (size_t)(u < A ? u : 0) + 1] != 0.0 || (!PI && ggFeat[u < A ? u : 0] == p));
                 const uint64_t m = __ballot(f);
                 if (f) flist[cnt + __popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)u;
                 cnt += __popcll(m);
@@ -402,7 +418,7 @@ __global__ __launch_bounds__(WMREG > 0 ? SV_COOP_THREADS : SV_THREADS) void logr
         double tmax = 1.0;
 #pragma unroll
         for (int e = 0; e < 4; e++)
-            if (inF[e] && (wp[e] + dl[e]) * sg[e] <= 0.0) tmax = fmin(tmax, -wp[e] / dl[e]);
+            if (inF[e] && (PI || sg[e] != 0.0) && (wp[e] + dl[e]) * sg[e] <= 0.0) tmax = fmin(tmax, -wp[e] / dl[e]);
 #pragma unroll
         for (int d = 32; d > 0; d >>= 1) tmax = fmin(tmax, psk_shfl_xor_f64(tmax, d));
         if (lane == 0) s_part[slot][wave] = tmax;
@@ -416,7 +432,7 @@ __global__ __launch_bounds__(WMREG > 0 ? SV_COOP_THREADS : SV_THREADS) void logr
             const int u = 4 * tid + e;
             if (u < A) {
                 if (inF[e]) {
-                    const bool hits = (wp[e] + dl[e]) * sg[e] <= 0.0 && -wp[e] / dl[e] <= tmax;
+                    const bool hits = (PI || sg[e] != 0.0) && (wp[e] + dl[e]) * sg[e] <= 0.0 && -wp[e] / dl[e] <= tmax;
                     ggP[2 * (size_t)u + 1] = hits ? 0.0 : wp[e] + tmax * dl[e];
                 }
                 ggG[u] += tmax * Qd[e];
@@ -736,8 +752,10 @@ __global__ __launch_bounds__(WMREG > 0 ? SV_COOP_THREADS : SV_THREADS) void logr
 #ifdef PSK_SV_STATS
                     if (lane == 0 && !live && I > 0) s_stat_dead++;
 #endif
-                    const bool shrink = live && zero && aG < omt;   // out of the sweeps until the whole set is taken up again
-                    const double vz = vmax(aG - 1.0, 0.0), vn = fabs(G + copysign(1.0, wp));
+                    // (the slot's penalty, 1 or -- the free intercept -- 0, comes with wave 0's record; a free slot is never shrunk)
+                    const double pen = PI ? 1.0 : (double)reinterpret_cast<const float *>(rec + 9)[v];
+                    const bool shrink = live && zero && aG < omt && (PI || pen != 0.0);   // out of the sweeps until the whole set is taken up again
+                    const double vz = vmax(aG - pen, 0.0), vn = fabs(G + copysign(pen, wp));
                     const double viol = live ? (zero ? vz : vn) : 0.0;   // (0 for the visit that shrinks: |G| < 1)
                     Gmax = vmax(Gmax, viol);
                     Gnorm1 += viol;
@@ -839,9 +857,11 @@ __global__ __launch_bounds__(WMREG > 0 ? SV_COOP_THREADS : SV_THREADS) void logr
             // (v_max / v_min as they are: fmax() and fmin() first quieten their operands, an instruction each)
             auto vmax = [](double x, double y) __attribute__((always_inline)) { double r; asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y)); return r; };
             auto vmin = [](double x, double y) __attribute__((always_inline)) { double r; asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y)); return r; };
-            auto step = [&](double G, double Hi, double wp) __attribute__((always_inline)) {
+            // (pen: the slot's penalty, 0 for the free intercept of PI = false: the threshold pen / H is then 0, the step -G / H)
+            auto step = [&](double G, double Hi, double wp, double pen) __attribute__((always_inline)) {
                 const double u = fma(-G, Hi, wp);
-                const double wnew = u - vmin(vmax(u, -Hi), Hi);
+                const double th = PI ? Hi : Hi * pen;
+                const double wnew = u - vmin(vmax(u, -th), th);
                 return vmin(vmax(wnew - wp, -10.0), 10.0);
             };
             double zpa = 0.0, zpb = 0.0;   // the steps of the pair before
@@ -863,6 +883,8 @@ __global__ __launch_bounds__(WMREG > 0 ? SV_COOP_THREADS : SV_THREADS) void logr
             };
             int m_a = __builtin_amdgcn_readlane(ordv, 0), m_b = __builtin_amdgcn_readlane(ordv, 1);
             d2 P_a = *reinterpret_cast<const d2 *>(ggP + 2 * (size_t)m_a + dz), P_b = *reinterpret_cast<const d2 *>(ggP + 2 * (size_t)m_b + dz);
+            auto pen_of = [&](int m) __attribute__((always_inline)) { return PI ? 1.0 : (ggFeat[m + dz] == p ? 0.0 : 1.0); };
+            double pen_a = pen_of(m_a), pen_b = pen_of(m_b);
             if (lane == 0) {   // pair 0: g[a], g[b] themselves, and the one entry of Q that links b to a
                 *reinterpret_cast<d2 *>(ggPub + 6) = d2{ggG[m_a], 0.0};
                 *reinterpret_cast<d2 *>(ggPub + 6 + 2) = d2{ggG[m_b], 0.0};
@@ -877,6 +899,7 @@ __global__ __launch_bounds__(WMREG > 0 ? SV_COOP_THREADS : SV_THREADS) void logr
                 const float q_ba = reinterpret_cast<const float *>(pub + 4)[0];
                 const int m_c = next_slot(), m_d = next_slot();
                 const d2 P_c = *reinterpret_cast<const d2 *>(ggP + 2 * (size_t)m_c + dz), P_d = *reinterpret_cast<const d2 *>(ggP + 2 * (size_t)m_d + dz);
+                const double pen_c = pen_of(m_c), pen_d = pen_of(m_d);
                 const double G_a = fma(zpb, (double)__int_as_float(__double2hiint(ea[1])), fma(zpa, (double)__int_as_float(__double2loint(ea[1])), ea[0]));
 #ifdef PSK_GG_CHECK
                 if (fit == 0 && (gg_chk++ % 509) == 0 && gg_chk < 30000) {   // G against its definition Gr[m] + sum_k Q[k][m] d_k
@@ -886,7 +909,7 @@ __global__ __launch_bounds__(WMREG > 0 ? SV_COOP_THREADS : SV_THREADS) void logr
                     if (lane == 0) printf("gg check a: interval %d slot %d G %.12e true %.12e diff %.3e\n", gg_chk, m_a, G_a, acc, G_a - acc);
                 }
 #endif
-                const double z_a = step(G_a, P_a[0], P_a[1]);
+                const double z_a = step(G_a, P_a[0], P_a[1], pen_a);
                 const double G_b = fma(z_a, (double)q_ba, fma(zpb, (double)__int_as_float(__double2hiint(eb[1])), fma(zpa, (double)__int_as_float(__double2loint(eb[1])), eb[0])));
 #ifdef PSK_GG_CHECK
                 if (fit == 0 && (gg_chk % 509) == 1 && gg_chk < 30000) {   // the same for b: w of slot a is not written yet, its step is added by hand
@@ -896,7 +919,7 @@ __global__ __launch_bounds__(WMREG > 0 ? SV_COOP_THREADS : SV_THREADS) void logr
                     if (lane == 0) printf("gg check b: interval %d slot %d G %.12e true %.12e diff %.3e\n", gg_chk, m_b, G_b, acc, G_b - acc);
                 }
 #endif
-                const double z_b = step(G_b, P_b[0], P_b[1]);
+                const double z_b = step(G_b, P_b[0], P_b[1], pen_b);
                 if (lane == 0) {
                     double *rec = ggRec + 10 * par;
                     *reinterpret_cast<d2 *>(rec) = d2{z_a, z_b};
@@ -905,11 +928,13 @@ __global__ __launch_bounds__(WMREG > 0 ? SV_COOP_THREADS : SV_THREADS) void logr
                     *reinterpret_cast<d2 *>(rec + 6) = P_b;
                     reinterpret_cast<int *>(rec + 8)[0] = m_a;
                     reinterpret_cast<int *>(rec + 8)[1] = m_b;
+                    if constexpr (!PI) { reinterpret_cast<float *>(rec + 9)[0] = (float)pen_a; reinterpret_cast<float *>(rec + 9)[1] = (float)pen_b; }
                     ggP[2 * (size_t)m_a + 1] = P_a[1] + z_a;
                     ggP[2 * (size_t)m_b + 1] = P_b[1] + z_b;
                 }
                 zpa = z_a; zpb = z_b;
                 P_a = P_c; P_b = P_d;
+                pen_a = pen_c; pen_b = pen_d;
                 m_a = m_c; m_b = m_d;
             };
             for (int T = 0;; T += DEPTH) {
@@ -1108,7 +1133,8 @@ __global__ __launch_bounds__(WMREG > 0 ? SV_COOP_THREADS : SV_THREADS) void logr
             double hd = 0.0, tmp = 0.0;
             if (grad4) {
                 const double grad = Gr[j], wj = w[j];
-                const double Gp = grad + 1.0, Gn = grad - 1.0;
+                const double pen = (PI || j < p) ? 1.0 : 0.0;
+            const double Gp = grad + pen, Gn = grad - pen;
                 double viol = 0.0;
                 if (wj == 0.0) {
                     if (Gp < 0) viol = -Gp;
@@ -1139,7 +1165,8 @@ __global__ __launch_bounds__(WMREG > 0 ? SV_COOP_THREADS : SV_THREADS) void logr
             tmp = psk_wave_sum_f64_dpp(tmp);
             const double grad = -tmp + FLD(&xjneg[j]);
             const double wj = FLD(&w[j]);
-            const double Gp = grad + 1.0, Gn = grad - 1.0;
+            const double pen = (PI || j < p) ? 1.0 : 0.0;
+            const double Gp = grad + pen, Gn = grad - pen;
             double viol = 0.0;
             if (wj == 0.0) {
                 if (Gp < 0) viol = -Gp;
@@ -1263,8 +1290,10 @@ __global__ __launch_bounds__(WMREG > 0 ? SV_COOP_THREADS : SV_THREADS) void logr
                 double rs = 0.0;
 #pragma unroll
                 for (int q = 0; q < NS; q++) {
-                    inF[q] = (lane + 64 * q < active) && wpr[q] != 0.0;
-                    sg[q] = wpr[q] > 0.0 ? 1.0 : -1.0;
+                    // (the free intercept is always in F, has no sign term and may cross zero: sg = 0)
+                    const bool freeq = !PI && (lane + 64 * q < active) && fjs[q] == p;
+                    inF[q] = (lane + 64 * q < active) && (wpr[q] != 0.0 || freeq);
+                    sg[q] = freeq ? 0.0 : wpr[q] > 0.0 ? 1.0 : -1.0;
                     r[q] = inF[q] ? -(g[q] + sg[q]) : 0.0;
                     pd[q] = r[q];
                     dl[q] = 0.0;
@@ -1317,14 +1346,14 @@ __global__ __launch_bounds__(WMREG > 0 ? SV_COOP_THREADS : SV_THREADS) void logr
                 double tmax = 1.0;
 #pragma unroll
                 for (int q = 0; q < NS; q++)
-                    if (inF[q] && (wpr[q] + dl[q]) * sg[q] <= 0.0) tmax = fmin(tmax, -wpr[q] / dl[q]);
+                    if (inF[q] && (PI || sg[q] != 0.0) && (wpr[q] + dl[q]) * sg[q] <= 0.0) tmax = fmin(tmax, -wpr[q] / dl[q]);
 #pragma unroll
                 for (int d = 32; d > 0; d >>= 1) tmax = fmin(tmax, psk_shfl_xor_f64(tmax, d));
                 if (!(tmax > 0.0)) return false;
 #pragma unroll
                 for (int q = 0; q < NS; q++) {
                     if (inF[q]) {
-                        const bool hits = (wpr[q] + dl[q]) * sg[q] <= 0.0 && -wpr[q] / dl[q] <= tmax;
+                        const bool hits = (PI || sg[q] != 0.0) && (wpr[q] + dl[q]) * sg[q] <= 0.0 && -wpr[q] / dl[q] <= tmax;
                         wpr[q] = hits ? 0.0 : wpr[q] + tmax * dl[q];
                     }
                     g[q] += tmax * Qd[q];
@@ -1354,7 +1383,8 @@ __global__ __launch_bounds__(WMREG > 0 ? SV_COOP_THREADS : SV_THREADS) void logr
                     for (int q = 0; q < NS; q++)
                         qcol[q] = Qm[PACKED ? (kq[q] > m ? tri[q] + m : tri_m + kq[q]) : sq_m + kq[q]];
                     const double G = pick_d(g, m), H = pick_d(h, m), Hi = pick_d(hinv, m), wp = pick_d(wpr, m);
-                    const double Gp = G + 1.0, Gn = G - 1.0;
+                    const double pen = (PI || pick_i(fjs, m) != p) ? 1.0 : 0.0;
+                    const double Gp = G + pen, Gn = G - pen;
                     double viol = 0.0;
                     if (wp == 0.0) {
                         if (Gp < 0) viol = -Gp;
@@ -1460,7 +1490,7 @@ __global__ __launch_bounds__(WMREG > 0 ? SV_COOP_THREADS : SV_THREADS) void logr
             if constexpr (FORM == 1) {
             // the Gram matrix in global memory (gg_run above); its LDS area takes the place of the Gram block
             if (lane == 0) {
-                s_cd.inner_eps = inner_eps; s_cd.Gnorm1_init = Gnorm1_init; s_cd.l = l;
+                s_cd.inner_eps = PI ? inner_eps : PSK_GG_FREE_INNER * inner_eps; s_cd.Gnorm1_init = Gnorm1_init; s_cd.l = l;
                 s_cd.active = active; s_cd.cmd = 4;
             }
             __syncthreads();   // releases waves 1..3 (helper_loop)
@@ -1525,7 +1555,8 @@ __global__ __launch_bounds__(WMREG > 0 ? SV_COOP_THREADS : SV_THREADS) void logr
                     G += b * D[i] * xTd[i];
                 }
                 G = psk_wave_sum_f64_dpp(G) + FLD(&Gr[j]) + (wp - FLD(&w[j])) * nu;
-                const double Gp = G + 1.0, Gn = G - 1.0;
+                const double pen = (PI || j < p) ? 1.0 : 0.0;
+                const double Gp = G + pen, Gn = G - pen;
                 double viol = 0.0;
                 if (wp == 0.0) {
                     if (Gp < 0) viol = -Gp;
@@ -1570,7 +1601,7 @@ __global__ __launch_bounds__(WMREG > 0 ? SV_COOP_THREADS : SV_THREADS) void logr
         for (int j = 0; j < P1; j++) {
             const double wp = FLD(&wpd[j]);
             delta += FLD(&Gr[j]) * (wp - FLD(&w[j]));
-            w_norm_new += fabs(wp);
+            if (PI || j < p) w_norm_new += fabs(wp);
         }
         delta += (w_norm_new - w_norm);
         double negsum = 0.0;
@@ -1621,7 +1652,7 @@ __global__ __launch_bounds__(WMREG > 0 ? SV_COOP_THREADS : SV_THREADS) void logr
             for (int j = 0; j < P1; j++) {
                 const double v = 0.5 * (FLD(&w[j]) + FLD(&wpd[j]));
                 if (lane == 0) wpd[j] = v;
-                w_norm_new += fabs(v);
+                if (PI || j < p) w_norm_new += fabs(v);
             }
             delta *= 0.5;
             negsum *= 0.5;
@@ -1676,16 +1707,17 @@ __global__ __launch_bounds__(WMREG > 0 ? SV_COOP_THREADS : SV_THREADS) void logr
 template <int FORM>
 hipError_t l1_bits_launch(const psk_l1_bits_launch &a)
 {
-    auto pick = [&](auto all) {
-        constexpr bool A = decltype(all)::value;
+    auto pick = [&](auto all, auto pi) {
+        constexpr bool A = decltype(all)::value, P = decltype(pi)::value;
         if constexpr (FORM == 0)
-            return a.wmreg == 0 ? logreg_newglmnet_bits_kernel<A, 0, FORM> : a.wmreg == 16 ? logreg_newglmnet_bits_kernel<A, 16, FORM>
-                 : a.wmreg == 32 ? logreg_newglmnet_bits_kernel<A, 32, FORM> : logreg_newglmnet_bits_kernel<A, 64, FORM>;
+            return a.wmreg == 0 ? logreg_newglmnet_bits_kernel<A, 0, FORM, P> : a.wmreg == 16 ? logreg_newglmnet_bits_kernel<A, 16, FORM, P>
+                 : a.wmreg == 32 ? logreg_newglmnet_bits_kernel<A, 32, FORM, P> : logreg_newglmnet_bits_kernel<A, 64, FORM, P>;
         else
-            return a.wmreg == 16 ? logreg_newglmnet_bits_kernel<A, 16, FORM>
-                 : a.wmreg == 32 ? logreg_newglmnet_bits_kernel<A, 32, FORM> : logreg_newglmnet_bits_kernel<A, 64, FORM>;
+            return a.wmreg == 16 ? logreg_newglmnet_bits_kernel<A, 16, FORM, P>
+                 : a.wmreg == 32 ? logreg_newglmnet_bits_kernel<A, 32, FORM, P> : logreg_newglmnet_bits_kernel<A, 64, FORM, P>;
     };
-    auto kern = a.all_lds ? pick(std::true_type{}) : pick(std::false_type{});
+    auto pick_pi = [&](auto all) { return a.pen_icpt ? pick(all, std::true_type{}) : pick(all, std::false_type{}); };
+    auto kern = a.all_lds ? pick_pi(std::true_type{}) : pick_pi(std::false_type{});
     if (a.lds_bytes > 64 * 1024) {
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                                  (int)a.lds_bytes);

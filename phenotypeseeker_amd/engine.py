@@ -458,6 +458,12 @@ class PskContext:
         return self._fit(self._lib.psk_logreg_l1_fit, "psk_logreg_l1_fit", X, y01, np.int32, fold, fit_param, fit_fold,
                          float(tol), int(max_iter))
 
+    def logreg_l1_free_fit(self, X, y01, fold, fit_param, fit_fold, tol=1e-4, max_iter=1000):
+        """L1 logistic fits with a free intercept (psk_logreg_l1_free_fit): the objective of scikit-learn's saga solver,
+        ||w||_1 + C sum log(1 + exp(-y (w.x + b))), same batching, routes and knobs as logreg_l1_fit."""
+        return self._fit(self._lib.psk_logreg_l1_free_fit, "psk_logreg_l1_free_fit", X, y01, np.int32, fold, fit_param, fit_fold,
+                         float(tol), int(max_iter))
+
     def lasso_fit(self, X, y, fold, fit_param, fit_fold, tol=1e-4, max_iter=1000):
         return self._fit(self._lib.psk_lasso_fit, "psk_lasso_fit", X, y, np.float64, fold, fit_param, fit_fold, float(tol),
                          int(max_iter))

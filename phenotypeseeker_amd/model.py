@@ -4,7 +4,8 @@ Lasso (modeling.py:994-1014, :1075-1085, :1208-1216, :975-979) -- exposing the a
 reference reads: predict / predict_proba / score, cv_results_['mean_test_score' |
 'std_test_score' | 'params'], best_params_, best_estimator_.coef_ (modeling.py:1226-1247,
 :1427-1436; prediction.py:126-129,:168-172).  All fits of a grid search (grid x folds + the
-refit) are solved on the GPU in one psk_logreg_l1_fit / psk_lasso_fit launch.  `--penalty L2`
+refit) are solved on the GPU in one psk_logreg_l1_fit / psk_lasso_fit launch
+(L1LogisticRegression(solver='saga'), the free intercept: psk_logreg_l1_free_fit).  `--penalty L2`
 (modeling.py:1001-1002, :1015-1019) maps to RidgeRegression / L2LogisticRegression over
 psk_ridge_fit / psk_logreg_l2_fit in the same way, `-bc SVM` (modeling.py:1025-1029) to SVC over
 psk_svc_fit, whose folds are scored from the decision values the engine returns, and `-bc DT` (modeling.py:1032-1033) to

@@ -41,13 +41,18 @@ class _Linear(_Estimator):
 
 
 class L1LogisticRegression(_Linear):
-    """liblinear-style L1 logistic regression: ||w||_1 + |b| + C sum log(1+exp(-y(w.x+b)))."""
+    """L1 logistic regression, LogisticRegression(penalty='l1', solver=...) (modeling.py:1011-1014).  solver='liblinear':
+    ||w||_1 + |b| + C sum log(1+exp(-y(w.x+b))), the intercept a penalised constant feature (psk_logreg_l1_fit);
+    solver='saga': ||w||_1 + C sum log(1+exp(-y(w.x+b))), the intercept free (psk_logreg_l1_free_fit) -- another model, not
+    another route to the same one.  Either way the fit is the optimum of the objective the solver minimises."""
     _is_classifier = True
     _dedupe = True  # an L1 optimum may sit on any copy of a repeated column: solve each pattern once
 
-    def __init__(self, C=1.0, tol=1e-4, max_iter=1000):
+    def __init__(self, C=1.0, tol=1e-4, max_iter=1000, solver="liblinear"):
+        if solver not in ("liblinear", "saga"):
+            raise ValueError("solver must be 'liblinear' or 'saga' for the L1 penalty, got %r" % (solver,))
         self.C, self.tol, self.max_iter = C, tol, max_iter
-        self.penalty, self.solver = "l1", "liblinear"
+        self.penalty, self.solver = "l1", solver
         self.classes_ = np.array([0, 1])
         self.coef_ = None
         self.intercept_ = None
@@ -59,13 +64,17 @@ class L1LogisticRegression(_Linear):
             parts.append("C=%r" % self.C)
         if repr(self.max_iter) != "100":
             parts.append("max_iter=%r" % self.max_iter)
-        parts += ["penalty='l1'", "solver='liblinear'"]
+        parts += ["penalty='l1'", "solver=%r" % self.solver]
         if self.tol != 1e-4:
             parts.append("tol=%r" % self.tol)
         return "LogisticRegression(%s)" % ", ".join(parts)
 
+    def _clone(self, **params):
+        return type(self)(solver=self.solver, **params)
+
     def _engine_fit(self, ctx, X, y, folds, fit_param, fit_fold):
-        return ctx.logreg_l1_fit(X, y.astype(np.int32), folds, fit_param, fit_fold, self.tol, int(self.max_iter))
+        fit = ctx.logreg_l1_free_fit if self.solver == "saga" else ctx.logreg_l1_fit
+        return fit(X, y.astype(np.int32), folds, fit_param, fit_fold, self.tol, int(self.max_iter))
 
     def _set(self, coef, icpt):
         self.coef_ = np.asarray(coef, dtype=np.float64).reshape(1, -1)
@@ -121,9 +130,6 @@ class L2LogisticRegression(L1LogisticRegression):
         if self.tol != 1e-4:
             parts.append("tol=%r" % self.tol)
         return "LogisticRegression(%s)" % ", ".join(parts)
-
-    def _clone(self, **params):
-        return type(self)(solver=self.solver, **params)
 
     def _engine_fit(self, ctx, X, y, folds, fit_param, fit_fold):
         return ctx.logreg_l2_fit(X, y.astype(np.int32), folds, fit_param, fit_fold, self.tol, int(self.max_iter),

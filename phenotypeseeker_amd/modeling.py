@@ -343,7 +343,8 @@ class Input:
                    n_iter, n_splits_cv_inner, testset_size, train_on_whole, logreg_solver, jump_to, pca,
                    real_counts, omit_B, kmerDB):
         """Same positional signature as the reference (:141-183).  Options that select estimators
-        outside the hot path (SVM/RF/DT/NB, elastic net, saga, PCA) are rejected here; `-bc SVM`, `-bc DT`, `-bc RF` and
+        outside the hot path (SVM/RF/DT/NB, elastic net, saga with the L1 penalty, PCA) are rejected here; `--logreg_solver saga`
+        passes with `--penalty L1` under `-bc log` with PSK_L1_SAGA (the free-intercept objective, psk_logreg_l1_free_fit); `-bc SVM`, `-bc DT`, `-bc RF` and
         `-bc NB` pass with their knobs (PSK_SVM, PSK_DT, PSK_RF, PSK_NB; `--kernel rbf` with PSK_SVM_RBF as well), `--pca` with
         PSK_PCA for a binary phenotype under `-bc log` and `-bc SVM`, and with PSK_TREE_PCA as well under `-bc DT` and `-bc RF`,
         `--penalty L1+L2` (or `elasticnet`) with `--l1_ratio` in [0, 1] with PSK_ENET for a continuous phenotype, `-bc XGBC` with a
@@ -461,14 +462,18 @@ class Input:
                                  "(SVM/RF/DT/NB are outside the accelerated path)." % binary_classifier)
             else:
                 phenotypes.model_name_long, phenotypes.model_name_short = "logistic regression", "log_reg"
-            # get_logreg_solver (:245-264): L1 -> liblinear (saga's objective leaves the intercept free and
-            # is not implemented); L2 -> lbfgs by default, all five names share one strictly convex optimum
+            # get_logreg_solver (:245-264): L1 -> liblinear, or with PSK_L1_SAGA saga, whose objective leaves the intercept
+            # free: another model (L1LogisticRegression, model_linear.py); L2 -> lbfgs by default, all five names share one
+            # strictly convex optimum
             is_log = phenotypes.binary_classifier == "log"
             if is_log and phenotypes.penalty == "L1":
-                if logreg_solver not in (None, "liblinear"):
+                if logreg_solver == "saga" and _lib.env_flag("PSK_L1_SAGA"):
+                    phenotypes.logreg_solver = "saga"
+                elif logreg_solver not in (None, "liblinear"):
                     raise SystemExit("Logistic Regression with L1 penalty on the GPU engine implements the "
                                      "liblinear objective only, got {}.".format(logreg_solver))
-                phenotypes.logreg_solver = "liblinear"
+                else:
+                    phenotypes.logreg_solver = "liblinear"
             elif is_log and phenotypes.penalty == "L2":
                 if logreg_solver is None:
                     logreg_solver = "lbfgs"
@@ -828,7 +833,7 @@ class phenotypes:
                 return SVC(kernel=self.kernel, probability=True, max_iter=self.max_iter, tol=self.tol), "C", grid
             if self.penalty == "L2":
                 return L2LogisticRegression(tol=self.tol, max_iter=self.max_iter, solver=self.logreg_solver), "C", grid
-            return L1LogisticRegression(tol=self.tol, max_iter=self.max_iter), "C", grid
+            return L1LogisticRegression(tol=self.tol, max_iter=self.max_iter, solver=self.logreg_solver or "liblinear"), "C", grid
         if self.penalty == "L2":
             return RidgeRegression(tol=self.tol, max_iter=self.max_iter), "alpha", [np.float64(a) for a in self.alphas]
         if self.penalty == "L1+L2":
